@@ -8,10 +8,13 @@ One "step" = one pass of the hot path over the synthetic workload, inputs reside
 Workload at N=1 GPU = BASELINE.json configs[1]: 100^3 7-point Poisson (double), 1x1x1 grid, geometric
 nested-dissection perm_c (MY_PERMC), Equil=NO, RowPerm=NOROWPERM, IterRefine=NOREFINE.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and reports them (value, ms_per_step, factor / solve
+times, residual of the last step's solution).  --full adds everything that needs passes of its own: the profiled factorisations behind
+`roofline`, the refinement row, the nrhs = 16 solve, the scaling points, `configs4`, the `cpu_baseline` legs and, at N > 1, `phases` and
+`predicted`.  --dump-outputs DIR writes the last timed step's solution x (what a caller of the path receives) as DIR/*.npy.
 """
 import argparse, json, os, subprocess, sys, tempfile, time
 
@@ -23,6 +26,21 @@ import numpy as np  # noqa: E402
 PEAK_FP64_MFMA_TFLOPS = 78.6   # MI355X dense fp64 matrix peak (256 CU x 4 SIMD x 32 flop/clk x 2.4 GHz)
 PEAK_HBM_GBS = 8000.0
 HBM_BYTES = 288e9              # per MI355X
+DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: larger solutions are written as a fixed, seeded sample of their rows
+
+
+def dump_outputs(out_dir, x):
+    """The solution of the last timed step in the original row order, as float64 .npy files: x (n x nrhs), or x_real and x_imag for
+    complex16.  Beyond DUMP_BYTES_MAX in all, the same fixed, seeded sample of rows of each, with its row indices in x_rows."""
+    x = np.asarray(x)
+    parts = {"x_real": x.real, "x_imag": x.imag} if np.iscomplexobj(x) else {"x": x}
+    row_bytes = 8 * sum(p.shape[1] for p in parts.values())
+    if x.shape[0] * row_bytes > DUMP_BYTES_MAX:
+        rows = np.sort(np.random.default_rng(0).choice(x.shape[0], DUMP_BYTES_MAX // (row_bytes + 8), replace=False))
+        parts = {k: p[rows] for k, p in parts.items()}
+        parts["x_rows"] = rows
+    for k, p in parts.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(p, dtype=np.float64))
 
 
 def kernel_source_hash():
@@ -384,7 +402,7 @@ def main():
     ap.add_argument("--cpu-n", type=int, default=40)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs4", action="store_true",
-                    help="skip the `configs4` block of the default line (BASELINE.json configs[4]: complex16 1000 x 1000 grid operator, 5 steps)")
+                    help="skip the `configs4` block of the --full line (BASELINE.json configs[4]: complex16 1000 x 1000 grid operator, 5 steps)")
     ap.add_argument("--configs4-n", type=int, default=1000, help="grid side of the configs4 block (1000 = BASELINE.json configs[4]; the CPU flow test lowers it)")
     ap.add_argument("--cpu-grid-n", type=int, default=50,
                     help="grid side of the 2x2x2 leg of the CPU baseline (8 MPI ranks x host_cores/8 threads of the real reference) on the vendored CBLAS; 0 = skip")
@@ -394,7 +412,14 @@ def main():
                     help="poisson3d = BASELINE configs[1] (default, the metric's config); zgrid2d = configs[4] family "
                          "(complex16 2-D grid operator, use --n 1000); audikw_like = configs[3] stand-in (use --n 68)")
     ap.add_argument("--matrix", default=None, help="MatrixMarket file instead of a generated workload (e.g. SuiteSparse audikw_1.mtx), ordered by sluamd_order_nd")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what needs passes of its own: profiled factorisations (roofline), refinement, nrhs = 16 solve, scaling points, "
+                         "configs4, CPU baselines, and at N > 1 the phase times and the scaling model's prediction (the --no-* options trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the solution of the last timed step as DIR/x.npy (float64; x_real / x_imag for complex16; a seeded sample of rows beyond 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.maxsup is None: args.maxsup = 64 if args.workload == "zgrid2d" else 256
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -402,8 +427,8 @@ def main():
         import socket
         sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()
         argv = ["--grid-side" if a == "--n" else a for a in sys.argv[1:]]   # torchrun's parser trips over the prefix "--n"
-        os.execvp(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                   "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + argv)
+        raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                          "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + argv))
 
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -587,26 +612,32 @@ def main():
     n_warm = max(2, args.warmup)
     if args.matrix:
         args.workload = args.matrix
-    clock = ClockSampler(local_rank)
-    clock.__enter__()
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)      # an unusable directory fails before the measurement, not after it
+    clock = ClockSampler(local_rank) if args.full else None
+    if clock:
+        clock.__enter__()
     M = measure(args.n, args.steps, n_warm, args.workload)
     n, rp, ci, v, xt, b, symb, h, grid, thresh = (M[k] for k in ("n", "rp", "ci", "v", "xt", "b", "symb", "h", "grid", "thresh"))
     t_setup, info, x, fact_ms, solve_ms, elapsed, res, err = (M[k] for k in ("t_setup", "info", "x", "fact_ms", "solve_ms", "elapsed", "res", "err"))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x)
 
-    # one extra profiled step: per-kernel-family HIP-event times on the compute stream
-    # (three passes at N = 1: roofline.frac is reported from the FASTEST with the spread beside it, so that box-to-box and run-to-run differences read off the line)
-    h.set_profile(True)                  # N > 1: collective like every factorisation (serial schedule on every rank)
-    prof_passes = []
-    for _ in range(3 if world == 1 else 1):
-        h.reset_values(); h.pdgstrf3d(thresh)
-        prof_passes.append(h.stats())
-    stp = min(prof_passes, key=lambda q: q["t_schur_ms"])
-    h.set_profile(False)
-    clock.__exit__()
+    if args.full:
+        # one extra profiled step: per-kernel-family HIP-event times on the compute stream
+        # (three passes at N = 1: roofline.frac is reported from the FASTEST with the spread beside it, so that box-to-box and run-to-run differences read off the line)
+        h.set_profile(True)                  # N > 1: collective like every factorisation (serial schedule on every rank)
+        prof_passes = []
+        for _ in range(3 if world == 1 else 1):
+            h.reset_values(); h.pdgstrf3d(thresh)
+            prof_passes.append(h.stats())
+        stp = min(prof_passes, key=lambda q: q["t_schur_ms"])
+        h.set_profile(False)
+        clock.__exit__()
 
     # accuracy row: one untimed pass of IterRefine=SLU_DOUBLE (pdgsrfs3d on the device) on the last solution
     accuracy = None
-    if world == 1 and not zwork:
+    if args.full and world == 1 and not zwork:
         try:
             h.attach_matrix(n, rp, ci, v, symb.perm_c)
             L.sluamd_device_synchronize(); t_r = time.perf_counter()
@@ -623,22 +654,6 @@ def main():
     F = symb.flops if world > 1 else st["flops_schur_exact"] + st["flops_panel"]   # whole-matrix flop count either way (per-rank stats are local)
     ms_per_step = 1e3 * elapsed / args.steps
     value = F * args.steps / elapsed / 1e9
-    schur_tf = st["flops_schur_exact"] / (stp["t_schur_ms"] * 1e-3) / 1e12 if stp["t_schur_ms"] > 0 else 0.0
-    # HBM traffic of the dominant kernel from PMC counters: cannot be collected inside this process (rocprofv3 --pmc
-    # needs its own passes), so the value measured on this same command line is kept under profiles/ with its provenance
-    traffic, traffic_src, traffic_stale = None, None, None
-    pmc_path = os.path.join(ROOT, "profiles", "r06_pmc_schur.json")
-    if world == 1 and args.n == 100 and not zwork and os.path.exists(pmc_path):
-        try:
-            pj = json.load(open(pmc_path))
-            if pj.get("kernel_source_sha16") == kernel_source_hash():
-                traffic = pj["traffic_bytes_per_factorisation"] / max(1, stp["schur_launches"])   # per launch, like `achieved`
-                traffic_src = "profiles/r06_pmc_schur.json: " + pj["source"]
-            else:
-                traffic_stale = True     # the kernels changed since the counters were collected: scripts/collect_pmc.sh regenerates them
-        except Exception:
-            pass
-    alg_bytes_per_launch = st["schur_bytes_alg"] / max(1, stp["schur_launches"])   # 16 B per updated element
     out = {
         "metric": "LU factorization GFLOP/s (pdgstrf3d) + solve time",
         "value": value, "unit": "GFLOP/s", "n_gpus": world, "steps": args.steps, "warmup": n_warm,
@@ -662,27 +677,46 @@ def main():
                    f"panel exchange / ancestor reduction / solve exchanges by the library's C driver over {'RCCL (ncclSend/ncclRecv)' if dist_backend_used[0] == 'rccl' else 'host-staged gloo callbacks' + (' -- RCCL communicator creation FAILED: ' + comm_cache['rccl_error'] if comm_cache.get('rccl_error') else '')}"},
         "flops_per_step": F, "flops_schur_padded": st["flops_schur_padded"],
         "factor_gflops_kernel_only": F / (np.mean(fact_ms) * 1e-3) / 1e9,
-        "max_abs_err_vs_xtrue": err, "info": int(info), "accuracy": accuracy,
+        "max_abs_err_vs_xtrue": err, "info": int(info),
         "levels": st["num_levels"], "fused_level_pairs": st["reserved_i"], "launches_per_factor": st["num_launches"], "setup_breakdown": M["setup_breakdown"],
-        "device_clock": clock.summary(),
         "bytes_device_this_rank": int(st["bytes_device"]),
-        "roofline": {"bound": "mfma", "kernel": "k_schur<Z> (the double kernel on the real embedding of the complex update: fused gather + fp64 MFMA + scatter; 8 real flop per complex multiply-add)" if zwork else
-                     "k_schur (fused gather + fp64 MFMA GEMM + scatter)",
-                     "achieved": schur_tf, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s",
-                     "frac": schur_tf / PEAK_FP64_MFMA_TFLOPS, "traffic": traffic, "traffic_unit": "bytes per launch",
-                     "traffic_source": traffic_src, "traffic_stale": traffic_stale, "algorithmic_bytes_per_launch": alg_bytes_per_launch,
-                     "launches": int(stp["schur_launches"]),
-                     "avg_launch_ms": stp["t_schur_ms"] / max(1, stp["schur_launches"]),
-                     "flops_per_launch": st["flops_schur_exact"] / max(1, stp["schur_launches"]),
-                     "schur_ms": stp["t_schur_ms"], "panel_ms": stp["t_panel_ms"], "profiled_factor_ms": stp["t_factor_ms"],
-                     "frac_min": min(st["flops_schur_exact"] / (q["t_schur_ms"] * 1e-3) / 1e12 / PEAK_FP64_MFMA_TFLOPS for q in prof_passes if q["t_schur_ms"] > 0) if prof_passes and prof_passes[0]["t_schur_ms"] > 0 else None,
-                     "frac_max": max(st["flops_schur_exact"] / (q["t_schur_ms"] * 1e-3) / 1e12 / PEAK_FP64_MFMA_TFLOPS for q in prof_passes if q["t_schur_ms"] > 0) if prof_passes and prof_passes[0]["t_schur_ms"] > 0 else None,
-                     "profiled_passes": len(prof_passes)},
     }
+    if args.full:
+        schur_tf = st["flops_schur_exact"] / (stp["t_schur_ms"] * 1e-3) / 1e12 if stp["t_schur_ms"] > 0 else 0.0
+        # HBM traffic of the dominant kernel from PMC counters: cannot be collected inside this process (rocprofv3 --pmc
+        # needs its own passes), so the value measured on this same command line is kept under profiles/ with its provenance
+        traffic, traffic_src, traffic_stale = None, None, None
+        pmc_path = os.path.join(ROOT, "profiles", "r06_pmc_schur.json")
+        if world == 1 and args.n == 100 and not zwork and os.path.exists(pmc_path):
+            try:
+                pj = json.load(open(pmc_path))
+                if pj.get("kernel_source_sha16") == kernel_source_hash():
+                    traffic = pj["traffic_bytes_per_factorisation"] / max(1, stp["schur_launches"])   # per launch, like `achieved`
+                    traffic_src = "profiles/r06_pmc_schur.json: " + pj["source"]
+                else:
+                    traffic_stale = True     # the kernels changed since the counters were collected: scripts/collect_pmc.sh regenerates them
+            except Exception:
+                pass
+        alg_bytes_per_launch = st["schur_bytes_alg"] / max(1, stp["schur_launches"])   # 16 B per updated element
+        out.update({
+            "accuracy": accuracy, "device_clock": clock.summary(),
+            "roofline": {"bound": "mfma", "kernel": "k_schur<Z> (the double kernel on the real embedding of the complex update: fused gather + fp64 MFMA + scatter; 8 real flop per complex multiply-add)" if zwork else
+                         "k_schur (fused gather + fp64 MFMA GEMM + scatter)",
+                         "achieved": schur_tf, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s",
+                         "frac": schur_tf / PEAK_FP64_MFMA_TFLOPS, "traffic": traffic, "traffic_unit": "bytes per launch",
+                         "traffic_source": traffic_src, "traffic_stale": traffic_stale, "algorithmic_bytes_per_launch": alg_bytes_per_launch,
+                         "launches": int(stp["schur_launches"]),
+                         "avg_launch_ms": stp["t_schur_ms"] / max(1, stp["schur_launches"]),
+                         "flops_per_launch": st["flops_schur_exact"] / max(1, stp["schur_launches"]),
+                         "schur_ms": stp["t_schur_ms"], "panel_ms": stp["t_panel_ms"], "profiled_factor_ms": stp["t_factor_ms"],
+                         "frac_min": min(st["flops_schur_exact"] / (q["t_schur_ms"] * 1e-3) / 1e12 / PEAK_FP64_MFMA_TFLOPS for q in prof_passes if q["t_schur_ms"] > 0) if prof_passes and prof_passes[0]["t_schur_ms"] > 0 else None,
+                         "frac_max": max(st["flops_schur_exact"] / (q["t_schur_ms"] * 1e-3) / 1e12 / PEAK_FP64_MFMA_TFLOPS for q in prof_passes if q["t_schur_ms"] > 0) if prof_passes and prof_passes[0]["t_schur_ms"] > 0 else None,
+                         "profiled_passes": len(prof_passes)},
+        })
     # the same Schur time split by tile configuration: `roofline` above is ALL Schur launches against the MFMA peak (the number to compare across
     # rounds); the 128 x 128 instantiation -- supernodes of >= 96 columns, the MFMA-bound part by SURVEY 8(d)'s own criterion (s_k >~ 120) -- and the
     # 64 x 64 configuration of the narrow supernodes at the bottom of the tree (HBM / latency-bound: fraction of the HBM peak on its algorithmic bytes)
-    tb = stp.get("t_schur_big_ms", 0.0)
+    tb = stp.get("t_schur_big_ms", 0.0) if args.full else 0.0
     if world == 1 and tb > 0 and stp["t_schur_ms"] > tb:
         fb, bb = st["flops_schur_exact_big"], st["schur_bytes_alg_big"]
         ts = stp["t_schur_ms"] - tb
@@ -703,7 +737,7 @@ def main():
     esz = 16 if zwork else 8
     solve_bytes = esz * float(st["nnz_L"] + st["nnz_U"])
     solve_gbs = solve_bytes / (np.mean(solve_ms) * 1e-3) / 1e9 if np.mean(solve_ms) > 0 else 0.0
-    if world == 1 and not zwork and h is not None:
+    if args.full and world == 1 and not zwork and h is not None:
         # second roofline point of the sweep kernels: nrhs = 16 in ONE call -- the reference's pdgstrs3d takes any nrhs and its lsum updates are
         # GEMMs there (pdgstrs_lsum.c:414-960); the factors are still read once per solve when the right-hand sides ride along (8 B per entry per solve), so the
         # achieved bytes / s against the HBM peak is the comparable figure; `ms_per_rhs` shows what a block of right-hand sides buys
@@ -728,7 +762,7 @@ def main():
                                  "achieved": solve_gbs, "peak": 8000.0, "unit": "GB/s", "frac": solve_gbs / 8000.0,
                                  "algorithmic_bytes_per_solve": solve_bytes,
                                  "note": "%d levels; one launch per level and sweep where a level holds <= 32 supernodes, two elsewhere (100^3: 223 launches per solve); 4-5.5 TB/s on the levels that hold the data, ~9.5 us per single-supernode level of the top separator" % st["num_levels"]}
-    if world > 1:   # the dominant kernel is profiled in the N=1 run of this same command (here: this rank's share under the serial schedule)
+    if args.full and world > 1:   # the dominant kernel is profiled in the N=1 run of this same command (here: this rank's share under the serial schedule)
         out["roofline"].update(achieved=None, frac=None, avg_launch_ms=None, flops_per_launch=None, algorithmic_bytes_per_launch=None,
                                note="per-kernel roofline is measured by the N=1 run (bench.py --gpus 1); N>1 lines report whole-job throughput; "
                                     "schur_ms / panel_ms / launches are rank 0's, from its extra profiled (serial-schedule) factorisation")
@@ -741,7 +775,7 @@ def main():
                          "note": "one extra factorisation under the serial (profiling) schedule, HIP events, max over ranks: exchange = the XY "
                                  "panel-exchange phases (dDiagFactIBCast + L / U panel broadcasts; part of panel_ms), reduce = the Z ancestor "
                                  "reduction (dreduceAllAncestors3d); the timed steps overlap the exchanges with the Schur tiles of the previous level"}
-    if world > 1:
+    if args.full and world > 1:
         out["predicted"] = predicted_block(h, n, symb.flops, float(np.mean(fact_ms)))
     # ---- scaling point: the same job one size up, reported beside the headline configuration at EVERY N (100^3 is a
     # 0.3 s job -- its N > 1 runs are exchange-latency-bound; 150^3 is 3 s of work and fits one GPU at 90 GB).  `value` stays the
@@ -775,7 +809,7 @@ def main():
     # 0.3 s job -- its N > 1 runs are exchange-latency-bound).  `value` stays the headline configuration so that the driver's efficiency figure
     # compares equal jobs; these blocks let it be recomputed on 150^3 (90 GB of factors, ~3 s per step) and on 180^3 (188 GB: the largest cube
     # ONE GPU holds, so T_1 exists -- the strong-scaling problem of VERDICT r4 item 6-iii; 4.5e14 flop, ~9 s per step on one GPU).
-    if args.workload == "poisson3d" and not args.no_scaling_point:
+    if args.full and args.workload == "poisson3d" and not args.no_scaling_point:
         for key, side, nsteps in (("scaling_point", args.scale_n, max(1, min(args.steps, 2))), ("strong_scaling_point", args.scale_n2, 1)):
             if not side or side == args.n:
                 continue
@@ -792,7 +826,7 @@ def main():
     # ---- configs4: BASELINE.json configs[4] (pzdrive3d complex16, cg20 family scaled 50x per grid side = 1000 x 1000 5-point complex grid
     # operator, 1 GPU) measured by the SAME default command, so that the driver's record carries it:
     # 5 timed steps after 2 warm-up steps, MFMA fraction of k_schur<Z> from one extra profiled factorisation, HBM fraction of the solve
-    if world == 1 and args.workload == "poisson3d" and not args.no_configs4:
+    if args.full and world == 1 and args.workload == "poisson3d" and not args.no_configs4:
         if h is not None:
             h.destroy(); symb.free(); h, symb = None, None
         try:
@@ -823,7 +857,7 @@ def main():
             raise
         except Exception as e:
             out["configs4"] = {"error": str(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "poisson3d":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "poisson3d":
         try:
             out["cpu_baseline"] = cpu_baseline(args.cpu_n, args.leaf, args.relax, args.maxsup, grid_n=args.cpu_grid_n, mkl_n=args.cpu_mkl_n, mkl_grid_n=args.cpu_mkl_grid_n)
         except Exception as e:

@@ -124,7 +124,7 @@ def test_bench_script_flow_on_the_emulation(ngpu, tmp_path):
     import json
     env = dict(os.environ, SLUAMD_LIB=os.path.join(ROOT, "oracle", "libsluamd_emul.so"), SLUAMD_DIST_BACKEND="gloo", OMP_NUM_THREADS="1")
     env.pop("SLUAMD_EMUL_SCHED", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ngpu), "--grid-side", "12", "--steps", "2", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ngpu), "--grid-side", "12", "--steps", "2", "--warmup", "2", "--full",
                         "--no-cpu-baseline", "--scale-n", "14", "--scale-n2", "16", "--configs4-n", "40"], env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -151,6 +151,39 @@ def test_bench_script_flow_on_the_emulation(ngpu, tmp_path):
         pr = j["predicted"]                # the scaling model's figure for this very run, from the ranks' own plan tables
         assert "error" not in pr and pr["pdgstrf3d_ms_reductions_exposed"] >= pr["pdgstrf3d_ms_reductions_hidden"] > 0 and 0 < pr["predicted_efficiency"] <= 1.0
     assert ("1x1x1" if ngpu == 1 else "1x1x2" if ngpu == 2 else "2x2x2") in j["config"]["workload"]
+
+
+@pytest.mark.parametrize("ngpu", [1, 2])
+def test_plain_bench_run_times_its_steps_and_dumps_the_solution(ngpu, tmp_path):
+    """bench.py without --full on CPU (emulation library): the headline keys, exactly --steps timed steps, none of the blocks that take passes
+    of their own, and --dump-outputs writing the last step's solution -- the same x on every run, since the inputs are fixed."""
+    import json
+    import numpy as np
+    from superlu_dist_amd import matgen
+    env = dict(os.environ, SLUAMD_LIB=os.path.join(ROOT, "oracle", "libsluamd_emul.so"), SLUAMD_DIST_BACKEND="gloo", OMP_NUM_THREADS="1",
+               SLUAMD_BENCH_TRACE="1")     # one "step wall" line per timed step on stderr (per rank)
+    env.pop("SLUAMD_EMUL_SCHED", None)
+    xs = []
+    for run in range(2):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ngpu), "--grid-side", "12", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / f"out{run}")], env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-1500:]
+        j = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in j, key
+        assert r.stderr.count("step wall") == 3 * ngpu
+        assert j["steps"] == 3 and j["n_gpus"] == ngpu and j["value"] > 0 and j["ms_per_step"] > 0 and j["residual"] < 1e-10
+        for key in ("roofline", "accuracy", "device_clock", "solve_nrhs16", "scaling_point", "strong_scaling_point", "configs4", "cpu_baseline",
+                    "phases", "predicted"):
+            assert key not in j, key
+        assert sorted(os.listdir(tmp_path / f"out{run}")) == ["x.npy"]
+        xs.append(np.load(tmp_path / f"out{run}" / "x.npy"))
+    n, rp, ci, v = matgen.poisson3d(12)
+    xt, _ = matgen.xtrue_rhs(n, rp, ci, v, 1)
+    assert xs[0].dtype == np.float64 and xs[0].shape == (n, 1)
+    assert np.abs(xs[0] - xt).max() < 1e-10 and np.abs(xs[0] - xs[1]).max() < 1e-12
 
 
 def test_bench_falls_back_to_staged_exchanges_when_the_rccl_communicator_cannot_be_created(tmp_path):
