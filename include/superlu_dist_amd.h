@@ -274,6 +274,19 @@ int sluamd_pdgsrfs3d(sluamd_handle_t h, const double *B, int64_t ldb, double *X,
                      int32_t *steps);
 int sluamd_pdgsrfs3d_dev(sluamd_handle_t h, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs,
                          double *berr, int32_t *steps);
+/* complex16 twins: pzgsrfs3d (SRC/complex16/pzgsrfs.c:365-514), the residual with abs1(z) = |re| + |im| as in pzgsmv.  Same
+ * semantics as the double calls; nzval, B, X are doublecomplex, ldb / ldx counted in complex elements.  zAttachMatrix needs a
+ * complex16 handle (dAttachMatrix a double one); a refinement call whose precision is not that of the handle and of the attached
+ * matrix, or with no matrix attached, returns SLUAMD_EINVAL.  nrhs == 0 returns 0 with *steps = 0.
+ * Grid handles (both precisions): the replicated form of sluamd_pdgstrs3d -- every rank attaches the complete matrix, passes the
+ * complete B and X and gets the complete refined X back; the calls are collective, and each step's continue / stop decision is a
+ * min-all-reduce over the grid, so all ranks take the same number of steps. */
+int sluamd_zAttachMatrix(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind,
+                         const sluamd_doublecomplex *nzval, const sluamd_int_t *perm_c);
+int sluamd_pzgsrfs3d(sluamd_handle_t h, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X, int64_t ldx,
+                     int32_t nrhs, double *berr, int32_t *steps);
+int sluamd_pzgsrfs3d_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
+                         int64_t ldx, int32_t nrhs, double *berr, int32_t *steps);
 
 /* ------------------------------------------------------------------------------------------------
  * Process grids: nprow x npcol x npdep ranks, one rank per GPU (gridinfo3d_t, superlu_defs.h:385-420).

@@ -48,6 +48,7 @@ EXPORTS = [
     "sluamd_symb_view", "sluamd_symb_grid_footprint", "sluamd_ddistribute_host", "sluamd_dCreateLUHandleFromSymb", "sluamd_symb_free",
     "sluamd_zCreateLUHandle", "sluamd_zSetValues", "sluamd_pzgstrf3d", "sluamd_zCopyLU2Host", "sluamd_pzgstrs3d",
     "sluamd_dAttachMatrix", "sluamd_pdgsrfs3d", "sluamd_pdgsrfs3d_dev",
+    "sluamd_zAttachMatrix", "sluamd_pzgsrfs3d", "sluamd_pzgsrfs3d_dev",
     "sluamd_comm_rccl_unique_id", "sluamd_comm_create_rccl", "sluamd_comm_create_callbacks", "sluamd_comm_create_local",
     "sluamd_comm_selftest", "sluamd_comm_rank", "sluamd_comm_size", "sluamd_comm_destroy", "sluamd_dCreateLUHandleGrid",
     "sluamd_dCreateLUHandleFromSymbGrid", "sluamd_zCreateLUHandleGrid", "sluamd_zCreateLUHandleFromSymbGrid",
@@ -121,6 +122,12 @@ def bind(L):
     L.sluamd_dAttachMatrix.argtypes = [C.c_void_p, C.c_int32, P_int, P_int, P_dbl, P_int]
     L.sluamd_pdgsrfs3d.argtypes = [C.c_void_p, P_dbl, C.c_int64, P_dbl, C.c_int64, C.c_int32, P_dbl, P_int]
     L.sluamd_pdgsrfs3d_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, P_dbl, P_int]
+    # complex16 refinement: only in the product library (the CPU test build of the host sources has no complex refinement kernels)
+    if hasattr(L, "sluamd_zAttachMatrix"):
+        L.sluamd_zAttachMatrix.argtypes = [C.c_void_p, C.c_int32, P_int, P_int, C.c_void_p, P_int]
+    for name in ("sluamd_pzgsrfs3d", "sluamd_pzgsrfs3d_dev"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, P_dbl, P_int]
     L.sluamd_comm_rccl_unique_id.argtypes = [C.c_void_p]
     L.sluamd_comm_create_rccl.argtypes = [C.POINTER(C.c_void_p), C.c_void_p] + [C.c_int] * 7
     L.sluamd_comm_create_callbacks.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CommCallbacks)] + [C.c_int] * 6
@@ -141,6 +148,14 @@ def load():
                            "there is no CPU fallback for the hot path")
     _lib = bind(C.CDLL(_SO))
     return _lib
+
+
+def entry(name):
+    """The library's function `name`; RuntimeError naming it when this build of the library does not export it."""
+    L = load()
+    if not hasattr(L, name):
+        raise RuntimeError(f"{name}: entry point missing from {L._name}")
+    return getattr(L, name)
 
 
 def check(rc, what=""):

@@ -6,6 +6,7 @@
 #include <cstring>
 #include "sluamd_comm.h"
 #include "sluamd_plan.h"
+#include "sluamd_refine.h"
 
 using namespace sluamd;
 
@@ -504,98 +505,73 @@ int sluamd_pdgstrs3d(sluamd_handle_t h, double *x, int64_t ldx, int32_t nrhs)
     return 0;
 }
 
-// ---- iterative refinement: pdgsrfs3d (SRC/double/pdgsrfs.c:345-510), SURVEY 8(f)-2 ----
-static void free_rfs(Handle *H)
+}  // extern "C"
+
+// ---- iterative refinement: pdgsrfs3d (SRC/double/pdgsrfs.c:345-510); the driver: sluamd_refine.h ----
+namespace sluamd {
+void free_rfs(Handle *H)
 {
     void **ps[] = {(void **) &H->d_rfs_rp, (void **) &H->d_rfs_ci, (void **) &H->d_rfs_pc, (void **) &H->d_rfs_av, (void **) &H->d_rfs_work, (void **) &H->d_rfs_s};
     for (void **p : ps) { if (*p) hipFree(*p); *p = nullptr; }
     H->rfs_nnz = 0;
+    H->rfs_z = false;
 }
 
-int sluamd_dAttachMatrix(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const double *nzval,
-                         const sluamd_int_t *perm_c)
+int attach_rfs(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const void *nzval,
+               const sluamd_int_t *perm_c, bool z, const char *who)
 {
     if (!h || !rowptr || !colind || !nzval || !perm_c || n != h->H.hs.n) { set_error("bad matrix arguments"); return SLUAMD_EINVAL; }
-    if (h->H.z) { set_error("iterative refinement is double precision only"); return SLUAMD_EINVAL; }
+    if (h->H.z != z) { set_error(z ? "double handle: call sluamd_dAttachMatrix" : "complex16 handle: call sluamd_zAttachMatrix"); return SLUAMD_EINVAL; }
     Handle *H = &h->H;
     HIPCHK(hipSetDevice(H->device));
     const int64_t nnz = rowptr[n];
+    const size_t vs = z ? 2 : 1;      // doubles per value
     free_rfs(H);
-    auto bail = [&](const char *what) { set_error(std::string(what) + " failed in sluamd_dAttachMatrix"); free_rfs(H); return SLUAMD_EHIP; };
+    auto bail = [&](const char *what) { set_error(std::string(what) + " failed in " + who); free_rfs(H); return SLUAMD_EHIP; };
     if (hipMalloc((void **) &H->d_rfs_rp, sizeof(int) * (n + 1)) != hipSuccess) return bail("hipMalloc");
     if (hipMalloc((void **) &H->d_rfs_ci, sizeof(int) * std::max<int64_t>(nnz, 1)) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void **) &H->d_rfs_av, sizeof(double) * std::max<int64_t>(nnz, 1)) != hipSuccess) return bail("hipMalloc");
+    if (hipMalloc((void **) &H->d_rfs_av, sizeof(double) * vs * std::max<int64_t>(nnz, 1)) != hipSuccess) return bail("hipMalloc");
     if (hipMalloc((void **) &H->d_rfs_pc, sizeof(int) * n) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void **) &H->d_rfs_work, sizeof(double) * 3 * (size_t) n) != hipSuccess) return bail("hipMalloc");   // r_perm | b | x
+    if (hipMalloc((void **) &H->d_rfs_work, sizeof(double) * vs * 3 * (size_t) n) != hipSuccess) return bail("hipMalloc");   // r_perm | b | x
     if (hipMalloc((void **) &H->d_rfs_s, sizeof(unsigned long long)) != hipSuccess) return bail("hipMalloc");
     if (hipMemcpy(H->d_rfs_rp, rowptr, sizeof(int) * (n + 1), hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
     if (hipMemcpy(H->d_rfs_ci, colind, sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
-    if (hipMemcpy(H->d_rfs_av, nzval, sizeof(double) * nnz, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
+    if (hipMemcpy(H->d_rfs_av, nzval, sizeof(double) * vs * nnz, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
     if (hipMemcpy(H->d_rfs_pc, perm_c, sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
     H->rfs_nnz = nnz;
+    H->rfs_z = z;
     return 0;
 }
+}  // namespace sluamd
 
-// d_B, d_X: device-resident, original ordering, column-major; X holds the initial solution and is refined in place
+extern "C" int sluamd_dAttachMatrix(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind,
+                                    const double *nzval, const sluamd_int_t *perm_c)
+{
+    return attach_rfs(h, n, rowptr, colind, nzval, perm_c, false, "sluamd_dAttachMatrix");
+}
+
+namespace {
+struct DRfs {   // the double kernels of the refinement driver (sluamd_refine.h)
+    static constexpr bool z = false;
+    static constexpr const char *attach = "sluamd_dAttachMatrix", *other = "sluamd_pzgsrfs3d";
+    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
+    {
+        eng::rfs_residual(s, (int) H->hs.n, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, x, b, H->d_rfs_pc, r_perm, H->d_rfs_s, safe1, safe2);
+    }
+    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x) { eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc, dx_perm, x); }
+};
+}  // namespace
+
+extern "C" {
+
 int sluamd_pdgsrfs3d_dev(sluamd_handle_t h, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    if (!h || !d_B || !d_X || !berr || nrhs < 0 || ldb < h->H.hs.n || ldx < h->H.hs.n) { set_error("bad refinement arguments"); return SLUAMD_EINVAL; }
-    Handle *H = &h->H;
-    if (!H->d_rfs_rp) { set_error("no matrix attached: call sluamd_dAttachMatrix first"); return SLUAMD_EINVAL; }
-    HIPCHK(hipSetDevice(H->device));
-    const int n = (int) H->hs.n;
-    const int ITMAX = 20;                                   // pdgsrfs.c:371
-    const double eps = 0x1p-53, safmin = 2.2250738585072014e-308;
-    const double safe1 = (double) (n + 1) * safmin, safe2 = safe1 / eps;
-    double *r_perm = H->d_rfs_work;
-    hipStream_t s = H->stream;
-    int count = 0;
-    for (int j = 0; j < nrhs; ++j) {
-        const double *Bc = d_B + (size_t) j * ldb;
-        double *Xc = d_X + (size_t) j * ldx;
-        double lstres = 3.0;
-        count = 0;
-        for (;;) {
-            HIPCHK(hipMemsetAsync(H->d_rfs_s, 0, sizeof(unsigned long long), s));
-            eng::rfs_residual(s, n, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, Xc, Bc, H->d_rfs_pc, r_perm, H->d_rfs_s, safe1, safe2);
-            double sv = 0.0;
-            HIPCHK(hipMemcpyAsync(&sv, H->d_rfs_s, sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            berr[j] = sv;
-            if (sv > eps && sv * 2 <= lstres && count < ITMAX) {
-                int rc = run_solve_dev(H, r_perm, n, 1);
-                if (rc) return rc;
-                eng::rfs_update(s, n, H->d_rfs_pc, r_perm, Xc);
-                lstres = sv;
-                ++count;
-            } else break;
-        }
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-    if (steps) *steps = count;
-    return 0;
+    return rfs_dev<DRfs>(h, d_B, ldb, d_X, ldx, nrhs, berr, steps);
 }
 
 int sluamd_pdgsrfs3d(sluamd_handle_t h, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    if (!h || !B || !X || !berr || nrhs < 0 || ldb < h->H.hs.n || ldx < h->H.hs.n) { set_error("bad refinement arguments"); return SLUAMD_EINVAL; }
-    if (nrhs == 0) { if (steps) *steps = 0; return 0; }
-    Handle *H = &h->H;
-    if (!H->d_rfs_rp) { set_error("no matrix attached: call sluamd_dAttachMatrix first"); return SLUAMD_EINVAL; }
-    HIPCHK(hipSetDevice(H->device));
-    const int64_t n = H->hs.n;
-    double *d_b = H->d_rfs_work + n, *d_x = H->d_rfs_work + 2 * (size_t) n;
-    int last = 0;
-    for (int j = 0; j < nrhs; ++j) {   // one column at a time through the two resident work vectors
-        HIPCHK(hipMemcpy(d_b, B + (size_t) j * ldb, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_x, X + (size_t) j * ldx, sizeof(double) * n, hipMemcpyHostToDevice));
-        int rc = sluamd_pdgsrfs3d_dev(h, d_b, n, d_x, n, 1, berr + j, &last);
-        if (rc) return rc;
-        HIPCHK(hipMemcpy(X + (size_t) j * ldx, d_x, sizeof(double) * n, hipMemcpyDeviceToHost));
-    }
-    if (steps) *steps = last;
-    return 0;
+    return rfs_host<DRfs>(h, B, ldb, X, ldx, nrhs, berr, steps);
 }
 
 void sluamd_dDestroyLUHandle(sluamd_handle_t h)

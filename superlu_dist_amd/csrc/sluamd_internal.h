@@ -366,9 +366,11 @@ struct Handle {
     double *d_xtmp = nullptr; int64_t xtmp_cap = 0;   // exchange staging of the distributed solve / ancestor reduction
     double *d_w = nullptr; int64_t w_cap = 0;         // second vector of the 1 x 1-layer sweeps (out-of-place diagonal solves: forward solution, backward accumulators)
     int64_t *d_apos = nullptr; double *d_aval = nullptr; int64_t a_nnz = 0;  // A's entries for device-side (re)distribution
-    // iterative refinement (sluamd_dAttachMatrix): the ORIGINAL matrix in CSR + perm_c, and work vectors
+    // iterative refinement (sluamd_dAttachMatrix / sluamd_zAttachMatrix): the ORIGINAL matrix in CSR + perm_c, and work vectors
+    // (values and vectors in doubles: 2 per value when rfs_z)
     int *d_rfs_rp = nullptr, *d_rfs_ci = nullptr, *d_rfs_pc = nullptr; double *d_rfs_av = nullptr;
     double *d_rfs_work = nullptr; unsigned long long *d_rfs_s = nullptr; int64_t rfs_nnz = 0;
+    bool rfs_z = false;                                     // the attached matrix is complex16
     void *h_pinned = nullptr; size_t pinned_bytes = 0;      // bounded pinned staging buffer (value upload / download)
     bool z = false;                                         // complex16 (doublecomplex) values: 16-byte elements
     bool dinv_ready = false;                                // T.dinv holds the inverses for the current factors
@@ -493,6 +495,11 @@ void zbwd_update(hipStream_t s, const DevTables &T, const int *nodes, const int 
 void zsweep_fused(hipStream_t s, bool lower, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, void *w, int64_t ldx, int nrhs,
                   int max_nsupc, int *tickets);
 void zscatter_values(hipStream_t s, void *val, const int64_t *pos, const void *a, int64_t nnz);
+// iterative refinement (pzgsrfs3d): the twins of rfs_residual / rfs_update on interleaved doublecomplex values, x, b, r_perm, dx_perm.
+// Referenced only by sluamd_zrefine.cpp (the CPU test build of the host sources has no restatement of them)
+void zrfs_residual(hipStream_t s, int n, const int *rp, const int *ci, const void *av, const void *x, const void *b, const int *pc,
+                   void *r_perm, unsigned long long *s_out, double safe1, double safe2);
+void zrfs_update(hipStream_t s, int n, const int *pc, const void *dx_perm, void *x);
 }  // namespace eng
 
 }  // namespace sluamd

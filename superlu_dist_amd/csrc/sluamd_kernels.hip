@@ -3199,6 +3199,17 @@ void zscatter_values(hipStream_t s, void *val, const int64_t *pos, const void *a
 {
     if (nnz > 0) hipLaunchKernelGGL(kz_scatter_values, dim3((unsigned) ((nnz + 255) / 256)), dim3(256), 0, s, reinterpret_cast<zc *>(val), pos, reinterpret_cast<const zc *>(a), nnz);
 }
+void zrfs_residual(hipStream_t s, int n, const int *rp, const int *ci, const void *av, const void *x, const void *b, const int *pc,
+                   void *r_perm, unsigned long long *s_out, double safe1, double safe2)
+{
+    if (n > 0)
+        hipLaunchKernelGGL(k_zrfs_residual, dim3((n + 255) / 256), dim3(256), 0, s, n, rp, ci, reinterpret_cast<const zc *>(av), reinterpret_cast<const zc *>(x),
+                           reinterpret_cast<const zc *>(b), pc, reinterpret_cast<zc *>(r_perm), s_out, safe1, safe2);
+}
+void zrfs_update(hipStream_t s, int n, const int *pc, const void *dx_perm, void *x)
+{
+    if (n > 0) hipLaunchKernelGGL(k_zrfs_update, dim3((n + 255) / 256), dim3(256), 0, s, n, pc, reinterpret_cast<const zc *>(dx_perm), reinterpret_cast<zc *>(x));
+}
 
 }  // namespace eng
 }  // namespace sluamd

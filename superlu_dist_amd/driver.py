@@ -238,6 +238,7 @@ class LUHandle:
 
     def copy_to_host(self, store=None):
         store = store or self.store
+        _check_store_dtype(store, self.z)
         L = _lib.load()
         _lib.check((L.sluamd_zCopyLU2Host if self.z else L.sluamd_dCopyLU2Host)(self._h, C.byref(store.view)), "sluamd_[dz]CopyLU2Host")
         return store
@@ -273,20 +274,21 @@ class LUHandle:
         _lib.check(_lib.load().sluamd_dResetValues(self._h), "sluamd_dResetValues")
 
     def attach_matrix(self, n, rowptr, colind, nzval, perm_c):
-        """Device copy of the ORIGINAL matrix (CSR) + perm_c for pdgsrfs3d."""
-        rp = np.ascontiguousarray(rowptr, dtype=np.int32); ci = np.ascontiguousarray(colind, dtype=np.int32)
-        v = np.ascontiguousarray(nzval, dtype=np.float64); pc = np.ascontiguousarray(perm_c, dtype=np.int32)
-        _lib.check(_lib.load().sluamd_dAttachMatrix(self._h, int(n), _pi(rp), _pi(ci), _pd(v), _pi(pc)), "sluamd_dAttachMatrix")
+        """Device copy of the ORIGINAL matrix (CSR) + perm_c for pdgsrfs3d (sluamd_dAttachMatrix, or sluamd_zAttachMatrix on a complex16 handle)."""
+        _attach_matrix(self._h, self.z, n, rowptr, colind, nzval, perm_c)
 
     def pdgsrfs3d(self, b, x):
-        """Iterative refinement of x (original ordering) for the attached matrix; returns (x, berr[nrhs], steps)."""
-        b = np.asfortranarray(np.array(b, dtype=np.float64)); x = np.asfortranarray(np.array(x, dtype=np.float64))
-        if b.ndim == 1:
-            b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
-        berr = np.zeros(b.shape[1]); steps = C.c_int32(0)
-        _lib.check(_lib.load().sluamd_pdgsrfs3d(self._h, _pd(b), b.shape[0], _pd(x), x.shape[0], b.shape[1], _pd(berr),
-                                                C.byref(steps)), "sluamd_pdgsrfs3d")
-        return x, berr, steps.value
+        """Iterative refinement of x (original ordering) for the attached matrix; returns (x, berr[nrhs], steps).
+        pzgsrfs3d on a complex16 handle (complex b and x)."""
+        return _gsrfs3d(self._h, self.z, b, x)
+
+    pzgsrfs3d = pdgsrfs3d
+
+    def pdgsrfs3d_dev(self, d_b, ldb, d_x, ldx, nrhs):
+        """sluamd_p[dz]gsrfs3d_dev: b, x device pointers (column-major, ld in values); x refined in place.  Returns (berr[nrhs], steps)."""
+        return _gsrfs3d_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs)
+
+    pzgsrfs3d_dev = pdgsrfs3d_dev
 
     def set_profile(self, on=True):
         _lib.load().sluamd_set_profile(self._h, int(on))
@@ -330,6 +332,43 @@ class LUHandle:
             pass
 
 
+def _check_store_dtype(store, z):
+    """The copy writes the handle's values into the store's arrays: a real store holds half the bytes of a complex16 handle's factors."""
+    if bool(store.z) != bool(z):
+        raise ValueError(f"copy_to_host: the store holds {'complex128' if store.z else 'float64'} values, the handle "
+                         f"{'complex16' if z else 'double'} factors")
+
+
+def _attach_matrix(h, z, n, rowptr, colind, nzval, perm_c):
+    rp = np.ascontiguousarray(rowptr, dtype=np.int32); ci = np.ascontiguousarray(colind, dtype=np.int32)
+    pc = np.ascontiguousarray(perm_c, dtype=np.int32)
+    if z:
+        v = np.ascontiguousarray(nzval, dtype=np.complex128)
+        _lib.check(_lib.entry("sluamd_zAttachMatrix")(h, int(n), _pi(rp), _pi(ci), v.ctypes.data_as(C.c_void_p), _pi(pc)), "sluamd_zAttachMatrix")
+    else:
+        v = np.ascontiguousarray(nzval, dtype=np.float64)
+        _lib.check(_lib.load().sluamd_dAttachMatrix(h, int(n), _pi(rp), _pi(ci), _pd(v), _pi(pc)), "sluamd_dAttachMatrix")
+
+
+def _gsrfs3d(h, z, b, x):
+    dt = np.complex128 if z else np.float64
+    b = np.asfortranarray(np.array(b, dtype=dt)); x = np.asfortranarray(np.array(x, dtype=dt))
+    if b.ndim == 1:
+        b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
+    berr = np.zeros(b.shape[1]); steps = C.c_int32(0)
+    name = "sluamd_pzgsrfs3d" if z else "sluamd_pdgsrfs3d"
+    _lib.check(_lib.entry(name)(h, b.ctypes.data_as(C.c_void_p) if z else _pd(b), b.shape[0], x.ctypes.data_as(C.c_void_p) if z else _pd(x),
+                                x.shape[0], b.shape[1], _pd(berr), C.byref(steps)), name)
+    return x, berr, steps.value
+
+
+def _gsrfs3d_dev(h, z, d_b, ldb, d_x, ldx, nrhs):
+    berr = np.zeros(max(int(nrhs), 1)); steps = C.c_int32(0)
+    name = "sluamd_pzgsrfs3d_dev" if z else "sluamd_pdgsrfs3d_dev"
+    _lib.check(_lib.entry(name)(h, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), _pd(berr), C.byref(steps)), name)
+    return berr[:int(nrhs)], steps.value
+
+
 def _forest_view(forests):
     """forests = dict(maxLvl, myTreeIdxs, myZeroTrIdxs, nodeLists=[array or None per forest])"""
     fv = ForestView()
@@ -359,8 +398,8 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
               keep=False, refine=False):
     """Solve A x = b through the GPU hot path: symbolic (host) -> device-resident distribute -> pdgstrf3d ->
     pdgstrs3d, with Equil = NO, RowPerm = NOROWPERM, ColPerm = MY_PERMC/NATURAL, IterRefine = NOREFINE
-    (the timing configuration of BASELINE.md section 4); refine=True adds IterRefine = SLU_DOUBLE (pdgsrfs3d on the device,
-    double precision only) and puts `berr` / `refine_steps` into the stats.  Returns (x, info, stats[, handle, symb])."""
+    (the timing configuration of BASELINE.md section 4); refine=True adds IterRefine = SLU_DOUBLE (pdgsrfs3d on the device;
+    pzgsrfs3d for complex nzval) and puts `berr` / `refine_steps` into the stats.  Returns (x, info, stats[, handle, symb])."""
     symb = Symbolic(n, rowptr, colind, perm_c, relax, maxsup)
     h = LUHandle.from_symbolic(symb, nzval, replace_tiny=replace_tiny)
     thresh = pivot_thresh(n, rowptr, colind, nzval) if anorm is None else 0.5 * float(np.finfo(np.float32).eps) * anorm

@@ -196,7 +196,22 @@ class GridHandle:
                       None if po is None else po.ctypes.data_as(_lib.P_int)), "sluamd_p[dz]gstrs3d_dist")
         return B
 
+    def attach_matrix(self, n, rowptr, colind, nzval, perm_c):
+        """The COMPLETE original matrix (CSR) + perm_c for the refinement, on every rank (sluamd_[dz]AttachMatrix)."""
+        from .driver import _attach_matrix
+        _attach_matrix(self._h, self.z, n, rowptr, colind, nzval, perm_c)
+
+    def pdgsrfs3d(self, b, x):
+        """Iterative refinement, replicated form (collective): the complete b and initial x (original ordering) on every rank;
+        returns (the complete refined x, berr[nrhs], steps) -- the same on every rank.  pzgsrfs3d on a complex16 handle."""
+        from .driver import _gsrfs3d
+        return _gsrfs3d(self._h, self.z, b, x)
+
+    pzgsrfs3d = pdgsrfs3d
+
     def copy_to_host(self, store):
+        from .driver import _check_store_dtype
+        _check_store_dtype(store, self.z)
         L = _lib.load()
         _lib.check((L.sluamd_zCopyLU2Host if self.z else L.sluamd_dCopyLU2Host)(self._h, C.byref(store.view)), "sluamd_[dz]CopyLU2Host")
         return store
