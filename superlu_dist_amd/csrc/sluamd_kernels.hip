@@ -2972,6 +2972,15 @@ static inline int sweep_variant(int nwork, int mx, int nrhs = 1)    // 0 / 1 / 5
     if (nrhs >= 2 && g_sweep_wide_v == 5) return 1;      // the blocked right-hand-side units need more than build 5's 80 registers (they spill there)
     return g_sweep_wide_v;
 }
+// SLUAMD_SOLVE_DEBUG: one stderr line per sweep launch -- which build (the case labels of SWEEP_DISPATCH below: 0 / 1 / 5 wide, 10 = SWEEP_N0 narrow) ran how
+// many units -- what the tests of the builds read
+static const bool g_sweep_debug = getenv("SLUAMD_SOLVE_DEBUG") != nullptr;
+static inline int sweep_variant_logged(const char *family, int nwork, int mx, int nrhs, int nrhs_rule)
+{
+    const int v = sweep_variant(nwork, mx, nrhs_rule);
+    if (g_sweep_debug) fprintf(stderr, "[sluamd sweep] family=%s build=%d units=%d mx=%d nrhs=%d\n", family, v, nwork, mx, nrhs);
+    return v;
+}
 //                 threads  row blocks  loads/batch (fwd, diag)  columns/batch (bwd)  all batches in flight  waves per SIMD
 #define SWEEP_V0   1024,    4,          16,                      4,                   true,                  4
 #define SWEEP_V1   512,     4,          16,                      4,                   true,                  2
@@ -3042,28 +3051,28 @@ void fwd_update(hipStream_t s, const DevTables &T, const int *nodes, const int *
                 const int2 *units, const int4 *recs)
 {
     if (nwork <= 0) return;
-    SWEEP_DISPATCH(sweep_variant(nwork, mx, nrhs), fwd(s, T, nodes, prefix, nn, nwork, xsrc, x, ldx, nrhs, mx, units, recs))
+    SWEEP_DISPATCH(sweep_variant_logged("fwd_update", nwork, mx, nrhs, nrhs), fwd(s, T, nodes, prefix, nn, nwork, xsrc, x, ldx, nrhs, mx, units, recs))
 }
 
 void bwd_update(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, const double *xcols, double *x, int64_t ldx, int nrhs, int mx,
                 const int2 *units, const int4 *recs)
 {
     if (nwork <= 0) return;
-    SWEEP_DISPATCH(sweep_variant(nwork, mx, nrhs), bwd(s, T, nodes, prefix, nn, nwork, xcols, x, ldx, nrhs, units, recs))
+    SWEEP_DISPATCH(sweep_variant_logged("bwd_update", nwork, mx, nrhs, nrhs), bwd(s, T, nodes, prefix, nn, nwork, xcols, x, ldx, nrhs, units, recs))
 }
 
 void sweep_step(hipStream_t s, bool lower, const DevTables &T, const int2 *dunits, int ndu, const int2 *units, int nunits,
                 double *xa, double *xb, int64_t ldx, int nrhs, int mx, const int4 *drecs, const int4 *urecs)
 {
     if (ndu + nunits <= 0) return;
-    SWEEP_DISPATCH(sweep_variant(ndu + nunits, mx, nrhs), sweep(s, lower, T, dunits, ndu, units, nunits, xa, xb, ldx, nrhs, mx, drecs, urecs))
+    SWEEP_DISPATCH(sweep_variant_logged("sweep_step", ndu + nunits, mx, nrhs, nrhs), sweep(s, lower, T, dunits, ndu, units, nunits, xa, xb, ldx, nrhs, mx, drecs, urecs))
 }
 
 void sweep_join(hipStream_t s, bool lower, const DevTables &T, const int4 *jrecs, int nj, const int4 *jaux, const int4 *urecs, int nunits,
                 double *xa, double *xb, int64_t ldx, int nrhs, int mx)
 {
     if (nj + nunits <= 0) return;
-    SWEEP_DISPATCH(sweep_variant(nj + nunits, mx), join(s, lower, T, jrecs, nj, jaux, urecs, nunits, xa, xb, ldx, nrhs, mx))
+    SWEEP_DISPATCH(sweep_variant_logged("sweep_join", nj + nunits, mx, nrhs, 1), join(s, lower, T, jrecs, nj, jaux, urecs, nunits, xa, xb, ldx, nrhs, mx))
 }
 
 void zero_nodes(hipStream_t s, const DevTables &T, const int *nodes, int nn, double *x, int64_t ldx, int nrhs)
