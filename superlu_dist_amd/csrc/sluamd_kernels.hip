@@ -14,6 +14,7 @@
 // column's part of block row k; the diagonal block may sit at the top of the L slot or in a scratch range
 // (DevTables::sn_dptr / sn_dlda / sn_ldiag).
 #include <hip/hip_runtime.h>
+#include <cassert>
 #include <cstdio>
 #include "sluamd_internal.h"
 
@@ -2026,6 +2027,220 @@ __global__ __launch_bounds__(NT) void k_solve_diag(DevTables T, const int *__res
     solve_diag_body<LOWER, NT>(T, nodes[blockIdx.x], x, x, ldx, nrhs, xs);
 }
 
+// ---- blocks of 16 right-hand sides: the MFMA form (RK = 16) of the three sweep units below -------------------------------------------------------------
+// The units, their records, their `chk` flags and their launches are those of fwd_update_body / bwd_update_body / diag_strip_body; what changes is the inner
+// product.  v_mfma_f64_16x16x4_f64 takes a 16-row tile of the factor as A (lane l: row l & 15, column k0 + (l >> 4): column-major panels, so four 128-byte
+// row runs per instruction), 16 right-hand sides of the staged x as B (lane l: x[k0 + (l >> 4)] of right-hand side l & 15) and leaves D[(l >> 4) + 4 reg][l & 15]:
+// ONE pass over the unit's factor entries serves 16 right-hand sides (the reference's GEMM of nbrow x nrhs x knsupc, pdgstrs_lsum.c:414-960, :1362-1832).
+// Surplus columns of the last block of an nrhs that is no multiple of 16: B is zero there and the sums are dropped.
+constexpr int SWEEP_RK_MFMA = 16;
+constexpr size_t SWEEP_DYN_LDS_MAX = 104 * 1024;      // hipFuncAttributeMaxDynamicSharedMemorySize of the sweep kernels
+// x_k staged as [right-hand side][nsp]: an odd stride keeps the 16 right-hand sides of a B read on different LDS banks.  The launch wrappers size the dynamic
+// segment by the same rule (sweep_xk_bytes).  The pad costs at most 8 nrhs bytes on top of the 96 KiB that max_rhs_chunk (sluamd_factor.cpp) allows for
+// mx x nrhs values, and the kernels' dynamic-LDS attribute is 104 KiB (SweepCfg::attrs): 96 KiB + 8 x 1024 bytes = 104 KiB, so blocks of more than 1024
+// right-hand sides (supernodes of at most 12 columns) are staged unpadded; sweep_xk_bytes asserts the sum
+__host__ __device__ __forceinline__ int sweep_xk_stride(int ns, int nrhs) { return nrhs <= 1024 ? (ns | 1) : ns; }
+// partial D tiles of the waves that share a 16-row tile (one array for the forward and the diagonal units of k_sweep: a workgroup runs one of them)
+template <int NT>
+__device__ __forceinline__ double *sweep_part_buf()
+{
+    constexpr int NKP = NT / 256;
+    __shared__ double s_part[NKP > 1 ? (NKP - 1) * 4 * 256 : 1];
+    return s_part;
+}
+
+// xout-tile of one 64-row strip: D = A[strip rows, c0 .. c1) x_k[c0 .. c1) for every block of 16 right-hand sides.  A: row 0 of the strip, column 0 (leading
+// dimension lda); nrow <= 64 valid rows.  Wave w owns the 16-row tile w & 3 and the K part w >> 2 of NT / 256 (one batch of NBT loads per lane covers 4 NBT
+// columns: a 256-column supernode with 1024 threads, as in the scalar builds); the parts are combined in LDS and part 0 hands every (register, right-hand
+// side, sum) of a valid row to `emit`.  `stage` fills xk; the first batch of A is in flight before it (it does not depend on x)
+template <int NT, int NBT, bool NTL, class Stage, class Emit>
+__device__ __forceinline__ void strip_mfma16(const double *A, size_t lda, int nrow, int c0, int c1, const double *xk, int nsp, int nrhs, Stage stage, Emit emit)
+{
+    constexpr int NKP = NT / 256;
+    constexpr int TBT = NKP == 4 ? 4 : NBT;        // later batches: 1024 threads cover 256 columns with the first one (128 VGPRs: short batches for what never runs there)
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int t = wave & 3, kp = wave >> 2, li = lane & 15, lk = lane >> 4;
+    const bool rvalid = 16 * t + li < nrow;
+    const bool tile_on = 16 * t < nrow;            // wave-uniform
+    const int cpp = ((c1 - c0 + 4 * NKP - 1) / (4 * NKP)) * 4;      // columns per K part: whole MFMA steps
+    const int ka = min(c1, c0 + kp * cpp), kb = min(c1, ka + cpp);
+    const double *Ar = A + 16 * t + li;
+    auto lda1 = [&](int c) { return NTL ? __builtin_nontemporal_load(Ar + (size_t) c * lda) : Ar[(size_t) c * lda]; };
+    double av0[NBT];
+#pragma unroll
+    for (int u = 0; u < NBT; ++u) { const int c = ka + 4 * u + lk; av0[u] = (rvalid && c < kb) ? lda1(c) : 0.0; }
+    stage();
+    __syncthreads();
+    double *part = sweep_part_buf<NT>();
+    for (int q0 = 0; q0 < nrhs; q0 += 16) {
+        const int q = q0 + li;
+        const bool qv = q < nrhs;
+        const double *xq = xk + (size_t) min(q, nrhs - 1) * nsp;
+        d4 acc = {0.0, 0.0, 0.0, 0.0};
+        if (tile_on) {
+#pragma unroll
+            for (int u = 0; u < NBT; ++u) {
+                const int c = ka + 4 * u + lk;
+                const double xv = xq[min(c, c1 - 1)];
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av0[u], (qv && c < kb) ? xv : 0.0, acc, 0, 0, 0);
+            }
+            for (int kk = ka + 4 * NBT; kk < kb; kk += 4 * TBT) {
+                double av[TBT];
+#pragma unroll
+                for (int u = 0; u < TBT; ++u) { const int c = kk + 4 * u + lk; av[u] = (rvalid && c < kb) ? lda1(c) : 0.0; }
+#pragma unroll
+                for (int u = 0; u < TBT; ++u) {
+                    const int c = kk + 4 * u + lk;
+                    const double xv = xq[min(c, c1 - 1)];
+                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], (qv && c < kb) ? xv : 0.0, acc, 0, 0, 0);
+                }
+            }
+        }
+        if (NKP > 1) {
+            if (kp > 0)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) part[((kp - 1) * 4 + t) * 256 + reg * 64 + lane] = acc[reg];
+            __syncthreads();
+        }
+        if (kp == 0 && tile_on) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                double v = acc[reg];
+#pragma unroll
+                for (int p2 = 0; p2 + 1 < NKP; ++p2) v += part[(p2 * 4 + t) * 256 + reg * 64 + lane];
+                if (qv && 16 * t + lk + 4 * reg < nrow) emit(reg, q, v);
+            }
+        }
+        if (NKP > 1) __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void stage_xk16(double *xk, int nsp, const double *xsrc, int fst, int ns, int64_t ldx, int nrhs, int nt)
+{
+    for (int idx = threadIdx.x; idx < ns * nrhs; idx += nt) { const int q = idx / ns, c = idx - q * ns; xk[(size_t) q * nsp + c] = xsrc[fst + c + (int64_t) q * ldx]; }
+}
+
+template <int NT, int NBT>
+__device__ __forceinline__ void fwd_update_mfma(const DevTables &T, int k, int strip, const double *xsrc, double *xdst, int64_t ldx, int nrhs, double *xk, const int4 *rec)
+{
+    int fst, ns, lda, row0;     // the unit's scalars: as fwd_update_body
+    int64_t loff, roff;
+    int chk = 0;
+    if (rec) {
+        const int4 a = rec[0], b = rec[1];
+        fst = a.x; ns = a.y & 0xffff; lda = a.z; row0 = a.w; chk = a.y >> 16;
+        loff = ((int64_t) b.y << 32) | (uint32_t) b.x; roff = ((int64_t) b.w << 32) | (uint32_t) b.z;
+    } else {
+        fst = T.xsup[k]; ns = T.xsup[k + 1] - fst; lda = T.sn_nsupr[k]; row0 = T.sn_ldiag[k] + strip * 64;
+        loff = T.sn_lval[k] + row0; roff = T.sn_lrow[k] + row0;
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int nrow = min(64, lda - row0);
+    int grow[4];                // D rows of this lane (K part 0 subtracts): flat row map and the `chk` rule of fwd_update_body
+    bool mine[4];
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int rr = 16 * (wave & 3) + (lane >> 4) + 4 * reg;
+        const bool ok = wave < 4 && rr < nrow;
+        grow[reg] = ok ? T.lrow[roff + rr] : 0;
+        mine[reg] = ok && !(chk && T.lrow_near[roff + rr] >= chk);
+    }
+    const int nsp = sweep_xk_stride(ns, nrhs);
+    strip_mfma16<NT, NBT, true>(T.val + loff, (size_t) lda, nrow, 0, ns, xk, nsp, nrhs, [&]() { stage_xk16(xk, nsp, xsrc, fst, ns, ldx, nrhs, NT); },
+                                [&](int reg, int q, double v) { if (mine[reg]) atomic_sub_f64(xdst + grow[reg] + (int64_t) q * ldx, v); });
+}
+
+template <bool LOWER, int NT, int NBT>
+__device__ __forceinline__ void diag_strip_mfma(const DevTables &T, int k, int strip, const double *xin, double *xout, int64_t ldx, int nrhs, double *xk, const int4 *rec)
+{
+    int fst, ns;                // as diag_strip_body
+    int64_t ioff;
+    if (rec) {
+        const int4 a = rec[0], b = rec[1];
+        fst = a.x; ns = a.y; strip = a.z;
+        ioff = LOWER ? (((int64_t) b.y << 32) | (uint32_t) b.x) : (((int64_t) b.w << 32) | (uint32_t) b.z);
+    } else {
+        fst = T.xsup[k]; ns = T.xsup[k + 1] - fst;
+        ioff = T.sn_inv[k] + (LOWER ? 0 : (int64_t) ns * ns);
+    }
+    const int c0 = LOWER ? 0 : strip * 64, c1 = LOWER ? min(ns, strip * 64 + 64) : ns;      // the other triangle holds explicit zeros: not read
+    const int nsp = sweep_xk_stride(ns, nrhs);
+    double *out = xout + fst + strip * 64 + 16 * ((threadIdx.x >> 6) & 3) + ((threadIdx.x & 63) >> 4);
+    strip_mfma16<NT, NBT, false>(T.inv + ioff + strip * 64, (size_t) ns, min(64, ns - strip * 64), c0, c1, xk, nsp, nrhs,
+                                 [&]() { stage_xk16(xk, nsp, xin, fst, ns, ldx, nrhs, NT); }, [&](int reg, int q, double v) { out[4 * reg + (int64_t) q * ldx] = v; });
+}
+
+// x_k -= U(k, chunk) x_cols: the rows of supernode k are the A rows (16-row tiles, one wave each, NT / 64 at a time), the chunk's <= 64 skyline columns are K
+// (the whole of it per wave: no partial sums), absent columns and the leading zeros of a segment (s_ld) are 0.0 in A; x is gathered through ucol_gc into LDS
+// for 16 right-hand sides at a time (zero for absent columns and surplus right-hand sides)
+template <int NT>
+__device__ __forceinline__ void bwd_update_mfma(const DevTables &T, int k, int chunk, const double *xcols, double *xrows, int64_t ldx, int nrhs, const int4 *rec)
+{
+    constexpr int NW = NT / 64;
+    __shared__ int s_cp[64], s_ld[64], s_gc[64];
+    __shared__ double s_xb[16][64 + 1];
+    int fst, ns, ncol;          // as bwd_update_body
+    int64_t ci0, uoff;
+    int chk = 0;
+    if (rec) {
+        const int4 a = rec[0], b = rec[1];
+        fst = a.x; ns = a.y & 0xffff; ncol = a.z; chk = a.y >> 16;
+        ci0 = ((int64_t) b.y << 32) | (uint32_t) b.x; uoff = ((int64_t) b.w << 32) | (uint32_t) b.z;
+    } else {
+        fst = T.xsup[k]; ns = T.xsup[k + 1] - fst; ncol = min(64, T.sn_ncolu[k] - chunk * 64);
+        ci0 = T.sn_ucol[k] + chunk * 64; uoff = T.sn_uval[k];
+    }
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+    if (tid < 64) {
+        const int64_t ci = ci0 + tid;
+        const bool cok = tid < ncol;
+        s_ld[tid] = (!cok || (chk && T.ucol_near[ci] >= chk)) ? ns : T.ucol_ld[ci]; s_cp[tid] = cok ? T.ucol_cp[ci] : 0; s_gc[tid] = cok ? T.ucol_gc[ci] : 0;
+    }
+    __syncthreads();
+    const double *Uv = T.val + uoff;
+    const int ntile = (ns + 15) >> 4;
+    auto load_tile = [&](double (&uv)[16], int tt) {
+        const int i = 16 * tt + li;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int c = 4 * u + lk, ld = s_ld[c];
+            uv[u] = (i >= ld && i < ns) ? __builtin_nontemporal_load(Uv + s_cp[c] - ld + i) : 0.0;
+        }
+    };
+    double uv0[16];             // the wave's first tile goes in flight before the gather of x, and serves every block of right-hand sides
+#pragma unroll
+    for (int u = 0; u < 16; ++u) uv0[u] = 0.0;
+    if (wave < ntile) load_tile(uv0, wave);
+    for (int q0 = 0; q0 < nrhs; q0 += 16) {
+        if (q0) __syncthreads();
+        for (int idx = tid; idx < 16 * 64; idx += NT) {
+            const int j = idx >> 6, c = idx & 63;
+            s_xb[j][c] = (c < ncol && q0 + j < nrhs) ? xcols[s_gc[c] + (int64_t) (q0 + j) * ldx] : 0.0;
+        }
+        __syncthreads();
+        const int q = q0 + li;
+        auto tile = [&](const double (&uv)[16], int tt) {
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int u = 0; u < 16; ++u)
+                if (4 * u < ncol) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(uv[u], s_xb[li][4 * u + lk], acc, 0, 0, 0);
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int i = 16 * tt + lk + 4 * reg;
+                const double sv = acc[reg];
+                if (i < ns && q < nrhs && sv != 0.0) atomic_sub_f64(xrows + fst + i + (int64_t) q * ldx, sv);
+            }
+        };
+        if (wave < ntile) tile(uv0, wave);
+        if constexpr (NW < 16)      // (16 waves hold the 16 tiles of the 256 rows a unit has at most: RB x 64 in the scalar form)
+            for (int tt = wave + NW; tt < ntile; tt += NW) {
+                double uv[16];
+                load_tile(uv, tt);
+                tile(uv, tt);
+            }
+    }
+}
+
 // The sweeps are bound by load latency and per-CU bandwidth, not by HBM (one dependent launch per level of the elimination
 // DAG), so the update kernels are shaped for parallelism: small work units (64 panel rows / 64 skyline columns -> several
 // hundred workgroups for a top-level supernode) of 1024 threads, every thread issuing ONE batch of <= 16 independent loads.
@@ -2034,9 +2249,10 @@ __global__ __launch_bounds__(NT) void k_solve_diag(DevTables T, const int *__res
 // 64-row strip); thread = (row, one of 16 column slices); x_k staged in LDS; fp64 atomics into x.
 // RK (round 6): right-hand sides per pass over the values.  1 = the loop of rounds 1-5 (every right-hand side re-reads the unit's factor entries: right for nrhs = 1);
 // 4 = a block of four right-hand sides rides along each batch of loads -- the reference's nrhs > 1 path is a GEMM there (pdgstrs_lsum.c:414-960) -- chosen by the
-// launch wrappers when nrhs >= 2: nrhs = 16 reads the factors 4 x instead of 16 x
+// launch wrappers when nrhs >= 2: nrhs = 16 reads the factors 4 x instead of 16 x; 16 = blocks of 16 right-hand sides accumulated by fp64 MFMA (fwd_update_mfma
+// and its kin above), chosen when nrhs >= SLUAMD_SWEEP_MFMA_MIN
 template <int NT, int NBT = 16, int RK = 1>   // NBT: loads per thread and batch (16: one batch covers a 256-column supernode with 1024 threads; 8: the builds for 8 waves per SIMD)
-__device__ __forceinline__ void fwd_update_body(const DevTables &T, int k, int strip, const double *xsrc /* solved x_k */, double *xdst /* lsum accumulators */,
+__device__ __forceinline__ void fwd_update_scalar(const DevTables &T, int k, int strip, const double *xsrc /* solved x_k */, double *xdst /* lsum accumulators */,
                                                 int64_t ldx, int nrhs, double *xk /* ns x nrhs */, const int4 *rec = nullptr)
 {
     constexpr int NP = NT / 64;     // column slices
@@ -2147,6 +2363,14 @@ __device__ __forceinline__ void fwd_update_body(const DevTables &T, int k, int s
     }
 }
 
+// the unit in the form RK names: 16 = the MFMA form, else the scalar one (only the chosen one is instantiated)
+template <int NT, int NBT = 16, int RK = 1>
+__device__ __forceinline__ void fwd_update_body(const DevTables &T, int k, int strip, const double *xsrc, double *xdst, int64_t ldx, int nrhs, double *xk, const int4 *rec = nullptr)
+{
+    if constexpr (RK == SWEEP_RK_MFMA) fwd_update_mfma<NT, NBT>(T, k, strip, xsrc, xdst, ldx, nrhs, xk, rec);
+    else fwd_update_scalar<NT, NBT, RK>(T, k, strip, xsrc, xdst, ldx, nrhs, xk, rec);
+}
+
 template <int NT, int NBT = 16, int MINW = NT / 256, int RK = 1>     // MINW: waves per SIMD the build is for (__launch_bounds__' second argument)
 __global__ __launch_bounds__(NT, MINW) void k_fwd_update(DevTables T, const int *__restrict__ nodes, const int *__restrict__ prefix,
                                                    int nn, const double *xsrc, double *xdst, int64_t ldx, int nrhs, const int2 *__restrict__ units,
@@ -2168,7 +2392,7 @@ template <int NT, int RBv = (NT == 1024 ? 4 : 1), int CBT = 4, bool UNR = true, 
 // RBv = 4 with NT = 512 / 256: supernodes of up to 256 columns in smaller workgroups (more of them resident per CU: levels of MANY units, where overlapping the phases
 // of a workgroup's life -- record, maps, values, reduction, atomics -- across workgroups counts for more than the length of one life);
 // CBT = columns per batch of loads (CBT x RBv loads per lane in flight), UNR = false: one batch in flight at a time (the builds for 8 waves per SIMD)
-__device__ __forceinline__ void bwd_update_body(const DevTables &T, int k, int chunk, const double *xcols /* solved x of the chunk's columns */,
+__device__ __forceinline__ void bwd_update_scalar(const DevTables &T, int k, int chunk, const double *xcols /* solved x of the chunk's columns */,
                                                 double *xrows /* accumulators of x_k */, int64_t ldx, int nrhs, const int4 *rec = nullptr)
 {
     constexpr int NWV = NT / 64, CPW = 64 / NWV, RB = RBv, UF = UNR ? 16 : 1;
@@ -2298,6 +2522,13 @@ __device__ __forceinline__ void bwd_update_body(const DevTables &T, int k, int c
     }
 }
 
+template <int NT, int RBv = (NT == 1024 ? 4 : 1), int CBT = 4, bool UNR = true, int RK = 1>
+__device__ __forceinline__ void bwd_update_body(const DevTables &T, int k, int chunk, const double *xcols, double *xrows, int64_t ldx, int nrhs, const int4 *rec = nullptr)
+{
+    if constexpr (RK == SWEEP_RK_MFMA) bwd_update_mfma<NT>(T, k, chunk, xcols, xrows, ldx, nrhs, rec);
+    else bwd_update_scalar<NT, RBv, CBT, UNR, RK>(T, k, chunk, xcols, xrows, ldx, nrhs, rec);
+}
+
 template <int NT, int RBv = (NT == 1024 ? 4 : 1), int CBT = 4, bool UNR = true, int MINW = NT / 256, int RK = 1>
 __global__ __launch_bounds__(NT, MINW) void k_bwd_update(DevTables T, const int *__restrict__ nodes, const int *__restrict__ prefix,
                                                    int nn, const double *xcols, double *xrows, int64_t ldx, int nrhs, const int2 *__restrict__ units,
@@ -2315,7 +2546,7 @@ __global__ __launch_bounds__(NT, MINW) void k_bwd_update(DevTables T, const int 
 // inverse through one CU (~10 us); as ns / 64 independent strips of the same GEMV shape as the panel update it takes what a launch
 // takes.  Independent only because input and output are different vectors (LevelSched sweeps ping-pong between x and a work vector).
 template <bool LOWER, int NT, int NBT = 16, int RK = 1>
-__device__ __forceinline__ void diag_strip_body(const DevTables &T, int k, int strip, const double *xin, double *xout, int64_t ldx, int nrhs,
+__device__ __forceinline__ void diag_strip_scalar(const DevTables &T, int k, int strip, const double *xin, double *xout, int64_t ldx, int nrhs,
                                                 double *xk /* ns x nrhs */, const int4 *rec = nullptr)
 {
     constexpr int NP = NT / 64;     // column slices
@@ -2418,6 +2649,13 @@ __device__ __forceinline__ void diag_strip_body(const DevTables &T, int k, int s
         }
         __syncthreads();
     }
+}
+
+template <bool LOWER, int NT, int NBT = 16, int RK = 1>
+__device__ __forceinline__ void diag_strip_body(const DevTables &T, int k, int strip, const double *xin, double *xout, int64_t ldx, int nrhs, double *xk, const int4 *rec = nullptr)
+{
+    if constexpr (RK == SWEEP_RK_MFMA) diag_strip_mfma<LOWER, NT, NBT>(T, k, strip, xin, xout, ldx, nrhs, xk, rec);
+    else diag_strip_scalar<LOWER, NT, NBT, RK>(T, k, strip, xin, xout, ldx, nrhs, xk, rec);
 }
 
 // One link of a sweep on a 1 x 1 layer in ONE launch: workgroups [0, ndu) run the diagonal-solve strips `dunits` of the next level of
@@ -2974,11 +3212,30 @@ static inline int sweep_variant(int nwork, int mx, int nrhs = 1)    // 0 / 1 / 5
 }
 // SLUAMD_SOLVE_DEBUG: one stderr line per sweep launch -- which build (the case labels of SWEEP_DISPATCH below: 0 / 1 / 5 wide, 10 = SWEEP_N0 narrow) ran how
 // many units -- what the tests of the builds read
+// -- and, last, how many right-hand sides ride along one pass over a unit's factor entries (rk = 1 / SWEEP_RK / 16)
 static const bool g_sweep_debug = getenv("SLUAMD_SOLVE_DEBUG") != nullptr;
-static inline int sweep_variant_logged(const char *family, int nwork, int mx, int nrhs, int nrhs_rule)
+#ifndef SLUAMD_SWEEP_RK
+#define SLUAMD_SWEEP_RK 4
+#endif
+constexpr int SWEEP_RK = SLUAMD_SWEEP_RK;      // right-hand sides per pass over the factor entries in the scalar nrhs >= 2 builds of the update / diagonal-strip units
+static_assert(SWEEP_RK != SWEEP_RK_MFMA, "RK = 16 names the MFMA form");
+// SLUAMD_SWEEP_MFMA_MIN: the smallest nrhs that runs the MFMA form (blocks of 16 right-hand sides); 0 = never (the RK = 4 builds for every nrhs >= 2)
+static const int g_sweep_mfma_min = getenv("SLUAMD_SWEEP_MFMA_MIN") ? (atoi(getenv("SLUAMD_SWEEP_MFMA_MIN")) > 0 ? std::max(2, atoi(getenv("SLUAMD_SWEEP_MFMA_MIN"))) : 0) : 16;      // (blocks start at two right-hand sides)
+static inline int sweep_rk(int nrhs) { return (g_sweep_mfma_min > 0 && nrhs >= g_sweep_mfma_min) ? SWEEP_RK_MFMA : nrhs >= 2 ? SWEEP_RK : 1; }
+// dynamic LDS of the units that stage x_k (the MFMA form pads its rows: sweep_xk_stride)
+static_assert(96 * 1024 + 8 * 1024 <= SWEEP_DYN_LDS_MAX, "max_rhs_chunk's 96 KiB plus the pad of <= 1024 right-hand sides must fit the dynamic-LDS attribute");
+static inline size_t sweep_xk_bytes(int mx, int nrhs)
 {
-    const int v = sweep_variant(nwork, mx, nrhs_rule);
-    if (g_sweep_debug) fprintf(stderr, "[sluamd sweep] family=%s build=%d units=%d mx=%d nrhs=%d\n", family, v, nwork, mx, nrhs);
+    const size_t plain = sizeof(double) * (size_t) nrhs * mx, padded = sizeof(double) * (size_t) nrhs * sweep_xk_stride(mx, nrhs);
+    assert(padded <= plain + 8 * 1024 && (plain > 96 * 1024 || padded <= SWEEP_DYN_LDS_MAX));      // a chunk that fits max_rhs_chunk's 96 KiB fits the attribute with its pad
+    return sweep_rk(nrhs) == SWEEP_RK_MFMA ? padded : plain;
+}
+// `blocked`: the family has blocked forms (sweep_join has none: one right-hand side per pass).  rk is what SweepCfg launches for build v: build 5 has no MFMA form
+static inline int sweep_launched_rk(int v, int nrhs, bool blocked) { const int rk = blocked ? sweep_rk(nrhs) : 1; return (v == 5 && rk == SWEEP_RK_MFMA) ? SWEEP_RK : rk; }
+static inline int sweep_variant_logged(const char *family, int nwork, int mx, int nrhs, bool blocked)
+{
+    const int v = sweep_variant(nwork, mx, blocked ? nrhs : 1);
+    if (g_sweep_debug) fprintf(stderr, "[sluamd sweep] family=%s build=%d units=%d mx=%d nrhs=%d rk=%d\n", family, v, nwork, mx, nrhs, sweep_launched_rk(v, nrhs, blocked));
     return v;
 }
 //                 threads  row blocks  loads/batch (fwd, diag)  columns/batch (bwd)  all batches in flight  waves per SIMD
@@ -2986,27 +3243,32 @@ static inline int sweep_variant_logged(const char *family, int nwork, int mx, in
 #define SWEEP_V1   512,     4,          16,                      4,                   true,                  2
 #define SWEEP_V5   512,     4,          8,                       2,                   false,                 6
 #define SWEEP_N0   256,     1,          16,                      4,                   true,                  1
-#ifndef SLUAMD_SWEEP_RK
-#define SLUAMD_SWEEP_RK 4
-#endif
-constexpr int SWEEP_RK = SLUAMD_SWEEP_RK;      // right-hand sides per pass over the factor entries in the nrhs >= 2 builds of the update / diagonal-strip units
 template <int NT, int RBv, int NBT, int CBT, bool UNR, int MINW> struct SweepCfg {
+    static constexpr int RKM = UNR ? SWEEP_RK_MFMA : SWEEP_RK;     // (build 5, UNR = false, never runs blocks of right-hand sides: sweep_variant)
     static void fwd(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, const double *xsrc, double *x, int64_t ldx, int nrhs, int mx,
                     const int2 *units, const int4 *recs)
     {
-        if (nrhs >= 2) hipLaunchKernelGGL((k_fwd_update<NT, NBT, MINW, SWEEP_RK>), dim3(nwork), dim3(NT), (size_t) mx * nrhs * sizeof(double), s, T, nodes, prefix, nn, xsrc, x, ldx, nrhs, units, recs);
-        else hipLaunchKernelGGL((k_fwd_update<NT, NBT, MINW>), dim3(nwork), dim3(NT), (size_t) mx * nrhs * sizeof(double), s, T, nodes, prefix, nn, xsrc, x, ldx, nrhs, units, recs);
+        const size_t lds = sweep_xk_bytes(mx, nrhs);
+        if (sweep_rk(nrhs) == SWEEP_RK_MFMA) hipLaunchKernelGGL((k_fwd_update<NT, NBT, MINW, RKM>), dim3(nwork), dim3(NT), lds, s, T, nodes, prefix, nn, xsrc, x, ldx, nrhs, units, recs);
+        else if (nrhs >= 2) hipLaunchKernelGGL((k_fwd_update<NT, NBT, MINW, SWEEP_RK>), dim3(nwork), dim3(NT), lds, s, T, nodes, prefix, nn, xsrc, x, ldx, nrhs, units, recs);
+        else hipLaunchKernelGGL((k_fwd_update<NT, NBT, MINW>), dim3(nwork), dim3(NT), lds, s, T, nodes, prefix, nn, xsrc, x, ldx, nrhs, units, recs);
     }
     static void bwd(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, const double *xcols, double *x, int64_t ldx, int nrhs,
                     const int2 *units, const int4 *recs)
     {
-        if (nrhs >= 2) hipLaunchKernelGGL((k_bwd_update<NT, RBv, CBT, UNR, MINW, SWEEP_RK>), dim3(nwork), dim3(NT), 0, s, T, nodes, prefix, nn, xcols, x, ldx, nrhs, units, recs);
+        if (sweep_rk(nrhs) == SWEEP_RK_MFMA) hipLaunchKernelGGL((k_bwd_update<NT, RBv, CBT, UNR, MINW, RKM>), dim3(nwork), dim3(NT), 0, s, T, nodes, prefix, nn, xcols, x, ldx, nrhs, units, recs);
+        else if (nrhs >= 2) hipLaunchKernelGGL((k_bwd_update<NT, RBv, CBT, UNR, MINW, SWEEP_RK>), dim3(nwork), dim3(NT), 0, s, T, nodes, prefix, nn, xcols, x, ldx, nrhs, units, recs);
         else hipLaunchKernelGGL((k_bwd_update<NT, RBv, CBT, UNR, MINW>), dim3(nwork), dim3(NT), 0, s, T, nodes, prefix, nn, xcols, x, ldx, nrhs, units, recs);
     }
     static void sweep(hipStream_t s, bool lower, const DevTables &T, const int2 *dunits, int ndu, const int2 *units, int nunits, double *xa, double *xb, int64_t ldx, int nrhs,
                       int mx, const int4 *drecs, const int4 *urecs)
     {
-        const size_t lds = (size_t) mx * nrhs * sizeof(double);
+        const size_t lds = sweep_xk_bytes(mx, nrhs);
+        if (sweep_rk(nrhs) == SWEEP_RK_MFMA) {
+            if (lower) hipLaunchKernelGGL((k_sweep<true, NT, RBv, NBT, CBT, UNR, MINW, RKM>), dim3(ndu + nunits), dim3(NT), lds, s, T, dunits, ndu, units, xa, xb, ldx, nrhs, drecs, urecs);
+            else hipLaunchKernelGGL((k_sweep<false, NT, RBv, NBT, CBT, UNR, MINW, RKM>), dim3(ndu + nunits), dim3(NT), lds, s, T, dunits, ndu, units, xa, xb, ldx, nrhs, drecs, urecs);
+            return;
+        }
         if (nrhs >= 2) {
             if (lower) hipLaunchKernelGGL((k_sweep<true, NT, RBv, NBT, CBT, UNR, MINW, SWEEP_RK>), dim3(ndu + nunits), dim3(NT), lds, s, T, dunits, ndu, units, xa, xb, ldx, nrhs, drecs, urecs);
             else hipLaunchKernelGGL((k_sweep<false, NT, RBv, NBT, CBT, UNR, MINW, SWEEP_RK>), dim3(ndu + nunits), dim3(NT), lds, s, T, dunits, ndu, units, xa, xb, ldx, nrhs, drecs, urecs);
@@ -3024,13 +3286,18 @@ template <int NT, int RBv, int NBT, int CBT, bool UNR, int MINW> struct SweepCfg
     }
     static int attrs()
     {
-        HIPCHK(hipFuncSetAttribute((const void *) k_sweep_join<true, NT, RBv, NBT, CBT, UNR, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *) k_fwd_update<NT, NBT, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *) k_sweep<true, NT, RBv, NBT, CBT, UNR, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *) k_sweep<false, NT, RBv, NBT, CBT, UNR, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *) k_fwd_update<NT, NBT, MINW, SWEEP_RK>, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *) k_sweep<true, NT, RBv, NBT, CBT, UNR, MINW, SWEEP_RK>, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void *) k_sweep<false, NT, RBv, NBT, CBT, UNR, MINW, SWEEP_RK>, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
+        HIPCHK(hipFuncSetAttribute((const void *) k_sweep_join<true, NT, RBv, NBT, CBT, UNR, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+        HIPCHK(hipFuncSetAttribute((const void *) k_fwd_update<NT, NBT, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+        HIPCHK(hipFuncSetAttribute((const void *) k_sweep<true, NT, RBv, NBT, CBT, UNR, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+        HIPCHK(hipFuncSetAttribute((const void *) k_sweep<false, NT, RBv, NBT, CBT, UNR, MINW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+        HIPCHK(hipFuncSetAttribute((const void *) k_fwd_update<NT, NBT, MINW, SWEEP_RK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+        HIPCHK(hipFuncSetAttribute((const void *) k_sweep<true, NT, RBv, NBT, CBT, UNR, MINW, SWEEP_RK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+        HIPCHK(hipFuncSetAttribute((const void *) k_sweep<false, NT, RBv, NBT, CBT, UNR, MINW, SWEEP_RK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+        if (RKM != SWEEP_RK) {
+            HIPCHK(hipFuncSetAttribute((const void *) k_fwd_update<NT, NBT, MINW, RKM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+            HIPCHK(hipFuncSetAttribute((const void *) k_sweep<true, NT, RBv, NBT, CBT, UNR, MINW, RKM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+            HIPCHK(hipFuncSetAttribute((const void *) k_sweep<false, NT, RBv, NBT, CBT, UNR, MINW, RKM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) SWEEP_DYN_LDS_MAX));
+        }
         return 0;
     }
 };
@@ -3051,28 +3318,28 @@ void fwd_update(hipStream_t s, const DevTables &T, const int *nodes, const int *
                 const int2 *units, const int4 *recs)
 {
     if (nwork <= 0) return;
-    SWEEP_DISPATCH(sweep_variant_logged("fwd_update", nwork, mx, nrhs, nrhs), fwd(s, T, nodes, prefix, nn, nwork, xsrc, x, ldx, nrhs, mx, units, recs))
+    SWEEP_DISPATCH(sweep_variant_logged("fwd_update", nwork, mx, nrhs, true), fwd(s, T, nodes, prefix, nn, nwork, xsrc, x, ldx, nrhs, mx, units, recs))
 }
 
 void bwd_update(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, const double *xcols, double *x, int64_t ldx, int nrhs, int mx,
                 const int2 *units, const int4 *recs)
 {
     if (nwork <= 0) return;
-    SWEEP_DISPATCH(sweep_variant_logged("bwd_update", nwork, mx, nrhs, nrhs), bwd(s, T, nodes, prefix, nn, nwork, xcols, x, ldx, nrhs, units, recs))
+    SWEEP_DISPATCH(sweep_variant_logged("bwd_update", nwork, mx, nrhs, true), bwd(s, T, nodes, prefix, nn, nwork, xcols, x, ldx, nrhs, units, recs))
 }
 
 void sweep_step(hipStream_t s, bool lower, const DevTables &T, const int2 *dunits, int ndu, const int2 *units, int nunits,
                 double *xa, double *xb, int64_t ldx, int nrhs, int mx, const int4 *drecs, const int4 *urecs)
 {
     if (ndu + nunits <= 0) return;
-    SWEEP_DISPATCH(sweep_variant_logged("sweep_step", ndu + nunits, mx, nrhs, nrhs), sweep(s, lower, T, dunits, ndu, units, nunits, xa, xb, ldx, nrhs, mx, drecs, urecs))
+    SWEEP_DISPATCH(sweep_variant_logged("sweep_step", ndu + nunits, mx, nrhs, true), sweep(s, lower, T, dunits, ndu, units, nunits, xa, xb, ldx, nrhs, mx, drecs, urecs))
 }
 
 void sweep_join(hipStream_t s, bool lower, const DevTables &T, const int4 *jrecs, int nj, const int4 *jaux, const int4 *urecs, int nunits,
                 double *xa, double *xb, int64_t ldx, int nrhs, int mx)
 {
     if (nj + nunits <= 0) return;
-    SWEEP_DISPATCH(sweep_variant_logged("sweep_join", nj + nunits, mx, nrhs, 1), join(s, lower, T, jrecs, nj, jaux, urecs, nunits, xa, xb, ldx, nrhs, mx))
+    SWEEP_DISPATCH(sweep_variant_logged("sweep_join", nj + nunits, mx, nrhs, false), join(s, lower, T, jrecs, nj, jaux, urecs, nunits, xa, xb, ldx, nrhs, mx))
 }
 
 void zero_nodes(hipStream_t s, const DevTables &T, const int *nodes, int nn, double *x, int64_t ldx, int nrhs)
