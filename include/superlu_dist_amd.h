@@ -167,6 +167,26 @@ int sluamd_pzgstrf3d(sluamd_handle_t h, double thresh, int *info);
 int sluamd_zCopyLU2Host(sluamd_handle_t h, const sluamd_zLUview_t *lu);
 int sluamd_pzgstrs3d(sluamd_handle_t h, sluamd_doublecomplex *x, int64_t ldx, int32_t nrhs);
 
+/* Transposed and conjugate-transposed solves with the resident factors: x (n x nrhs, column-major, leading dimension ldx, rows in
+ * the ordering of the factored matrix -- the convention of sluamd_pdgstrs3d) is overwritten by the solution of (L U)^T y = x
+ * (SLUAMD_TRANS) or (L U)^H y = x (SLUAMD_CONJ; the same as SLUAMD_TRANS on a double handle).  No second factorisation and no copy
+ * of the factors: the sweeps read the panels and skylines along their columns (U^T forward over the DAG levels ascending, L^T
+ * backward over them descending; the levels are longest paths over the L and the U blocks, so one schedule orders both systems).
+ * The reference's pdgstrs3d has no such solve (pdgssvx3d reads options->Trans for the equilibration only).
+ * SLUAMD_NOTRANS calls sluamd_pdgstrs3d[_dev] / sluamd_pzgstrs3d and nothing else; it also gives complex16 handles a
+ * device-pointer solve.  Errors: trans outside {0, 1, 2} or a handle of the other precision: SLUAMD_EINVAL.  GRID HANDLES of
+ * more than one rank: SLUAMD_EINVAL for SLUAMD_TRANS / SLUAMD_CONJ (sluamd_last_error() says that transposed solves need a
+ * 1 x 1 x 1 handle) -- the transposed sweeps broadcast along the other grid axis and need exchange plans of their own; not
+ * built.  nrhs == 0 returns 0.  stats.t_solve_ms and stats.solve_launches are filled as by the untransposed solve: per chunk of
+ * right-hand sides one diagonal and one update launch per DAG level and sweep (4 x levels). */
+#define SLUAMD_NOTRANS 0
+#define SLUAMD_TRANS   1
+#define SLUAMD_CONJ    2   /* conjugate transpose; identical to SLUAMD_TRANS on double handles */
+int sluamd_pdgstrs3d_trans(sluamd_handle_t h, int trans, double *x, int64_t ldx, int32_t nrhs);
+int sluamd_pdgstrs3d_trans_dev(sluamd_handle_t h, int trans, double *d_x, int64_t ldx, int32_t nrhs);
+int sluamd_pzgstrs3d_trans(sluamd_handle_t h, int trans, sluamd_doublecomplex *x, int64_t ldx, int32_t nrhs);
+int sluamd_pzgstrs3d_trans_dev(sluamd_handle_t h, int trans, sluamd_doublecomplex *d_x, int64_t ldx, int32_t nrhs);
+
 /* Replaces dDestroyLUgpuHandle (LUgpuCHandle_interface_impl.cu:30). */
 void sluamd_dDestroyLUHandle(sluamd_handle_t h);
 

@@ -49,6 +49,7 @@ EXPORTS = [
     "sluamd_zCreateLUHandle", "sluamd_zSetValues", "sluamd_pzgstrf3d", "sluamd_zCopyLU2Host", "sluamd_pzgstrs3d",
     "sluamd_dAttachMatrix", "sluamd_pdgsrfs3d", "sluamd_pdgsrfs3d_dev",
     "sluamd_zAttachMatrix", "sluamd_pzgsrfs3d", "sluamd_pzgsrfs3d_dev",
+    "sluamd_pdgstrs3d_trans", "sluamd_pdgstrs3d_trans_dev", "sluamd_pzgstrs3d_trans", "sluamd_pzgstrs3d_trans_dev",
     "sluamd_comm_rccl_unique_id", "sluamd_comm_create_rccl", "sluamd_comm_create_callbacks", "sluamd_comm_create_local",
     "sluamd_comm_selftest", "sluamd_comm_rank", "sluamd_comm_size", "sluamd_comm_destroy", "sluamd_dCreateLUHandleGrid",
     "sluamd_dCreateLUHandleFromSymbGrid", "sluamd_zCreateLUHandleGrid", "sluamd_zCreateLUHandleFromSymbGrid",
@@ -128,6 +129,10 @@ def bind(L):
     for name in ("sluamd_pzgsrfs3d", "sluamd_pzgsrfs3d_dev"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, P_dbl, P_int]
+    # transposed / conjugate-transposed solves: only in the product library (the CPU test build has no transposed sweeps)
+    for name in ("sluamd_pdgstrs3d_trans", "sluamd_pdgstrs3d_trans_dev", "sluamd_pzgstrs3d_trans", "sluamd_pzgstrs3d_trans_dev"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int32]
     L.sluamd_comm_rccl_unique_id.argtypes = [C.c_void_p]
     L.sluamd_comm_create_rccl.argtypes = [C.POINTER(C.c_void_p), C.c_void_p] + [C.c_int] * 7
     L.sluamd_comm_create_callbacks.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CommCallbacks)] + [C.c_int] * 6

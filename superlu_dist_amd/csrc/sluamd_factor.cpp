@@ -633,9 +633,8 @@ static int xseg_exchange(Handle *H, double *d_x, int64_t ldx, int nrhs, const st
 // (Measured and rejected: the far units on side streams -- each event record / wait costs the chain ~6 us; the feeding units
 // run by the diagonal workgroup itself -- serial 64-row strips, 7.05 -> 8.1 ms.)
 
-static int max_rhs_chunk(const Handle *H);
 // second vector of the sweeps below: the diagonal solves are out of place (strips of one supernode = independent workgroups)
-static int ensure_w(Handle *H, int64_t doubles)
+int ensure_w(Handle *H, int64_t doubles)
 {
     if (doubles <= H->w_cap) return 0;
     if (H->d_w) hipFree(H->d_w);
@@ -847,7 +846,7 @@ static int solve_bwd_z(Handle *H, int z, double *d_x, int64_t ldx, int nrhs)
     return 0;
 }
 
-static int max_rhs_chunk(const Handle *H)
+int max_rhs_chunk(const Handle *H)
 {   // x_k is staged in LDS by the diagonal solve / forward update: max_nsupc x nrhs values next to <= 50 KiB of static arrays
     // (k_sweep), 160 KiB per workgroup
     const int per = H->max_nsupc * (H->z ? 16 : 8);

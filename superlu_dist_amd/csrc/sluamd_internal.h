@@ -500,6 +500,17 @@ void zscatter_values(hipStream_t s, void *val, const int64_t *pos, const void *a
 void zrfs_residual(hipStream_t s, int n, const int *rp, const int *ci, const void *av, const void *x, const void *b, const int *pc,
                    void *r_perm, unsigned long long *s_out, double safe1, double safe2);
 void zrfs_update(hipStream_t s, int n, const int *pc, const void *dx_perm, void *x);
+// transposed / conjugate-transposed sweeps on a 1 x 1 x 1 handle, in place in ONE vector (sluamd_tkernels.inc).  Referenced only by sluamd_tsolve.cpp (the CPU
+// test build of the host sources has no restatement of them).  `upper`: the U^T step (forward sweep) -- y_k = Uinv_k^T x_k, complex16: substitution on U_kk^T
+// (conj: its conjugate) -- else the L^T step (backward sweep).  fwd_update_t: x[gc] -= U_k[:, c]^T y_k, units = (supernode, chunk of 64 non-empty columns) of
+// bwd_prefix; bwd_update_t: x_k[c] -= L_k[below, c]^T x[lrow], units = (supernode, 64-row strip) of fwd_prefix, complex16: 256-row strips of zfwd_prefix
+int tsolve_setup();   // one-time function attributes of these kernels (dynamic LDS limits); the driver calls it before its first launch
+void solve_diag_t(hipStream_t s, bool upper, const DevTables &T, const int *nodes, int nn, double *x, int64_t ldx, int nrhs, int max_nsupc);
+void fwd_update_t(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, double *x, int64_t ldx, int nrhs, int max_nsupc);
+void bwd_update_t(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, double *x, int64_t ldx, int nrhs);
+void zsolve_diag_t(hipStream_t s, bool upper, bool conj, const DevTables &T, const int *nodes, int nn, void *x, int64_t ldx, int nrhs, int max_nsupc);
+void zfwd_update_t(hipStream_t s, bool conj, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, int64_t ldx, int nrhs, int max_nsupc);
+void zbwd_update_t(hipStream_t s, bool conj, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, int64_t ldx, int nrhs);
 }  // namespace eng
 
 }  // namespace sluamd

@@ -96,5 +96,7 @@ int run_solve_dist(Handle *H, double *d_b, int64_t ldb, int nrhs, int64_t m_loc,
 int run_solve_local(Handle *H, double *d_x, int64_t ldx, int nrhs);   // single-rank sweep over every schedule (refinement)
 int ensure_dinv(Handle *H);
 int ensure_inv(Handle *H);
+int ensure_w(Handle *H, int64_t doubles);   // second vector of the sweeps (Handle::d_w)
+int max_rhs_chunk(const Handle *H);         // right-hand sides per pass of the sweeps: x_k of the widest supernode staged in 96 KiB of LDS
 
 }  // namespace sluamd

@@ -243,13 +243,18 @@ class LUHandle:
         _lib.check((L.sluamd_zCopyLU2Host if self.z else L.sluamd_dCopyLU2Host)(self._h, C.byref(store.view)), "sluamd_[dz]CopyLU2Host")
         return store
 
-    def pdgstrs3d(self, x):
-        """pdgstrs3d, or pzgstrs3d on a complex16 handle."""
+    def pdgstrs3d(self, x, trans="N"):
+        """pdgstrs3d, or pzgstrs3d on a complex16 handle.  trans = "T" / "C": the transposed / conjugate-transposed solve (L U)^T y = x,
+        (L U)^H y = x with the same factors (sluamd_p[dz]gstrs3d_trans; 1 x 1 x 1 handles)."""
+        t = _trans_code(trans)
         x = np.asfortranarray(np.array(x, dtype=np.complex128 if self.z else np.float64))
         if x.ndim == 1:
             x = np.asfortranarray(x[:, None])
         L = _lib.load()
-        if self.z:
+        if t:
+            name = "sluamd_pzgstrs3d_trans" if self.z else "sluamd_pdgstrs3d_trans"
+            _lib.check(_lib.entry(name)(self._h, t, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1]), name)
+        elif self.z:
             _lib.check(L.sluamd_pzgstrs3d(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1]), "sluamd_pzgstrs3d")
         else:
             _lib.check(L.sluamd_pdgstrs3d(self._h, _pd(x), x.shape[0], x.shape[1]), "sluamd_pdgstrs3d")
@@ -267,8 +272,14 @@ class LUHandle:
                                                      None if pm is None else _pi(pm), None if pm is None else _pi(pm)), "sluamd_pdgstrs3d_dist")
         return B
 
-    def pdgstrs3d_dev(self, ptr, ldx, nrhs):
-        _lib.check(_lib.load().sluamd_pdgstrs3d_dev(self._h, C.c_void_p(ptr), ldx, nrhs), "sluamd_pdgstrs3d_dev")
+    def pdgstrs3d_dev(self, ptr, ldx, nrhs, trans="N"):
+        """the solve on a device pointer (ldx in values); complex16 handles and trans = "T" / "C" go through sluamd_p[dz]gstrs3d_trans_dev"""
+        t = _trans_code(trans)
+        if t or self.z:
+            name = "sluamd_pzgstrs3d_trans_dev" if self.z else "sluamd_pdgstrs3d_trans_dev"
+            _lib.check(_lib.entry(name)(self._h, t, C.c_void_p(ptr), ldx, nrhs), name)
+        else:
+            _lib.check(_lib.load().sluamd_pdgstrs3d_dev(self._h, C.c_void_p(ptr), ldx, nrhs), "sluamd_pdgstrs3d_dev")
 
     def reset_values(self):
         _lib.check(_lib.load().sluamd_dResetValues(self._h), "sluamd_dResetValues")
@@ -330,6 +341,14 @@ class LUHandle:
             self.destroy()
         except Exception:
             pass
+
+
+def _trans_code(trans):
+    """"N" | "T" | "C" -> SLUAMD_NOTRANS / SLUAMD_TRANS / SLUAMD_CONJ"""
+    try:
+        return {"N": 0, "T": 1, "C": 2}[str(trans).upper()]
+    except KeyError:
+        raise ValueError(f"trans must be 'N', 'T' or 'C', not {trans!r}") from None
 
 
 def _check_store_dtype(store, z):
@@ -395,11 +414,13 @@ def pivot_thresh(n, rowptr, colind, nzval):
 
 
 def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, replace_tiny=False, anorm=None,
-              keep=False, refine=False):
-    """Solve A x = b through the GPU hot path: symbolic (host) -> device-resident distribute -> pdgstrf3d ->
+              keep=False, refine=False, trans="N"):
+    """Solve A x = b -- trans = "T": A^T x = b, "C": A^H x = b, with the same factorisation of A -- through the GPU hot path: symbolic (host) -> device-resident distribute -> pdgstrf3d ->
     pdgstrs3d, with Equil = NO, RowPerm = NOROWPERM, ColPerm = MY_PERMC/NATURAL, IterRefine = NOREFINE
     (the timing configuration of BASELINE.md section 4); refine=True adds IterRefine = SLU_DOUBLE (pdgsrfs3d on the device;
     pzgsrfs3d for complex nzval) and puts `berr` / `refine_steps` into the stats.  Returns (x, info, stats[, handle, symb])."""
+    if refine and _trans_code(trans):
+        raise ValueError("refine=True with trans != 'N': refining a transposed system needs a transposed SpMV (not built)")
     symb = Symbolic(n, rowptr, colind, perm_c, relax, maxsup)
     h = LUHandle.from_symbolic(symb, nzval, replace_tiny=replace_tiny)
     thresh = pivot_thresh(n, rowptr, colind, nzval) if anorm is None else 0.5 * float(np.finfo(np.float32).eps) * anorm
@@ -409,7 +430,7 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
         b = np.asfortranarray(b[:, None])
     xp = np.zeros_like(b, order="F")
     xp[symb.perm_c, :] = b                                     # Pc*b
-    y = h.pdgstrs3d(xp)
+    y = h.pdgstrs3d(xp, trans=trans)                           # the factors are of A1 = Pc A Pc^T: A^T x = b is A1^T (Pc x) = Pc b, the same permutation on both sides
     x = np.asfortranarray(y[symb.perm_c, :])                   # Pc^T y
     st = h.stats()
     if refine:
