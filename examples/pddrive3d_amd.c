@@ -131,12 +131,14 @@ static int read_matrix_market(const char *path, int64_t *n_out, int **rp_out, in
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s N [-nd] | file.dat | file.mtx\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s N [-nd] [--equil] | file.dat [--equil] | file.mtx [--equil]\n", argv[0]); return 2; }
     if (sluamd_device_count() < 1) { fprintf(stderr, "no HIP device: this library has no CPU fallback\n"); return 3; }
     int64_t n; int *rp, *ci; double *v;
     char *end;
     const long N = strtol(argv[1], &end, 10);
     int use_nd = argc > 2 && !strcmp(argv[2], "-nd");
+    int equil = 0;                                            /* --equil: Equil = YES (pdgsequ + pdlaqgs on the device, scaled solve) */
+    for (int a = 2; a < argc; ++a) if (!strcmp(argv[a], "--equil")) equil = 1;
     const size_t len = strlen(argv[1]);
     if (*end == '\0' && N > 0) { if (poisson3d((int) N, &n, &rp, &ci, &v)) return 2; }
     else if (len > 4 && !strcmp(argv[1] + len - 4, ".mtx")) {
@@ -171,6 +173,12 @@ int main(int argc, char **argv)
     CHECK(sluamd_dCreateLUHandleFromSymb(&h, symb, rp, ci, v, perm_c, &opt));
 
     int info = 0;
+    sluamd_equil_t eq;
+    if (equil) {   /* scales the handle's matrix; anorm of the scaled matrix comes back (pdgssvx3d.c:673-729) */
+        CHECK(sluamd_dEquilibrate(h, (sluamd_int_t) n, rp, ci, v, perm_c, &eq));
+        printf("EQUIL: equed = %c  rowcnd %.3e  colcnd %.3e  amax %.3e  info %d\n", "NRCB"[eq.equed], eq.rowcnd, eq.colcnd, eq.amax, eq.info);
+        anorm = eq.anorm;
+    }
     const double thresh = 1.1920928955078125e-07 * anorm;   /* smach_dist("Epsilon") * anorm, pdgstrf3d.c:132 */
     CHECK(sluamd_pdgstrf3d(h, thresh, &info));
     if (info) { printf("INFO = %d returned from pdgstrf3d (zero pivot)\n", info); return 1; }
@@ -178,13 +186,16 @@ int main(int argc, char **argv)
     /* solve through pdgstrs3d's own boundary: b in the ORIGINAL row order in, x in the original order out (B_to_X / X_to_B with
      * perm_c run inside the library; a single rank holds all n rows) */
     double *x = (double *) malloc(sizeof(double) * n);
-    memcpy(x, b, sizeof(double) * n);
-    CHECK(sluamd_pdgstrs3d_dist(h, x, n, 1, n, 0, perm_c, perm_c));
-
-    /* IterRefine = SLU_DOUBLE */
     double berr = 0.0; int32_t steps = 0;
-    CHECK(sluamd_dAttachMatrix(h, (sluamd_int_t) n, rp, ci, v, perm_c));
-    CHECK(sluamd_pdgsrfs3d(h, b, n, x, n, 1, &berr, &steps));
+    if (equil) {   /* the expert driver's solve phase: B scaled by R, solve, refinement on the scaled system, X scaled by C */
+        CHECK(sluamd_pdgssvx3d_solve(h, SLUAMD_NOTRANS, b, n, x, n, 1, 1, &berr, &steps));
+    } else {
+        memcpy(x, b, sizeof(double) * n);
+        CHECK(sluamd_pdgstrs3d_dist(h, x, n, 1, n, 0, perm_c, perm_c));
+        /* IterRefine = SLU_DOUBLE */
+        CHECK(sluamd_dAttachMatrix(h, (sluamd_int_t) n, rp, ci, v, perm_c));
+        CHECK(sluamd_pdgsrfs3d(h, b, n, x, n, 1, &berr, &steps));
+    }
 
     double err = 0.0, xn = 0.0, rn = 0.0, bn = 0.0;
     for (int64_t i = 0; i < n; ++i) {

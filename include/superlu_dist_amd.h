@@ -308,6 +308,64 @@ int sluamd_pzgsrfs3d(sluamd_handle_t h, const sluamd_doublecomplex *B, int64_t l
 int sluamd_pzgsrfs3d_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
                          int64_t ldx, int32_t nrhs, double *berr, int32_t *steps);
 
+/* ---- Equil = YES: row / column equilibration on the device and the solve phase of the expert driver in the caller's ordering and
+ * scaling (pdgsequ + pdlaqgs at the head of pdgssvx3d, SRC/double/pdgssvx3d.c:673-729; B scaled by R before the solve, :1450-1465;
+ * X scaled by C after it, :1806-1821, the roles swapped for a transposed system).  For handles made by
+ * sluamd_[dz]CreateLUHandleFromSymb[Grid]: there A's values exist on the host only in the caller's CSR, not in store form.
+ *
+ * sluamd_[dz]Equilibrate takes the arrays the handle was created from and attaches them like sluamd_[dz]AttachMatrix.  It computes
+ * R[i] = 1 / max_j |a_ij| and C[j] = 1 / max_i |a_ij| R[i] with the smlnum / bignum clamps, rowcnd, colcnd and amax (pdgsequ.c:126-215;
+ * complex16: abs1(z) = |re| + |im|, pzgsequ.c:136, :182), bit for bit what the host routine computes (maxima are exact).  info > 0 (row
+ * i exactly zero: i + 1; column j: n + j + 1; pdgsequ.c:158-164, :202-208): it stops there with equed = SLUAMD_EQUED_N, nothing scaled,
+ * and returns 0 like the reference.  Otherwise equed is decided as pdlaqgs does (THRESH = 0.1, small = 2^-1022 / 2^-52, large = 1 / small;
+ * pdlaqgs.c:89-146), the ATTACHED values are scaled in place -- R: a r[i]; C: a c[j]; B: (a r[i]) c[j] in exactly that order, both
+ * precisions (pzlaqgs.c:141 forms r[i] c[j] first; the order here cannot overflow in the product of the two scalings) --, R and C stay
+ * on the device, and the scaled values are distributed into the store: the handle is then UNFACTORED and holds the scaled matrix, and a
+ * later sluamd_dResetValues restores the scaled values, not the original ones.  anorm: the 1-norm (maximum column sum of the moduli;
+ * complex16: the true modulus, as pzlangs) of the matrix the handle now holds, for thresh = eps_single * anorm; it is summed with fp64
+ * atomics, so its low bits depend on the order: relative error of the summation <= k 2^-52 for a longest column of k entries; the
+ * complex16 moduli come from the device's hypot, each within about one unit in the last place (2^-52) on top of that.
+ * Errors, all SLUAMD_EINVAL with a message: a handle not created from the symbolic structure, n or rowptr[n] not those of the creation,
+ * a handle of the other precision, a second call on the same handle.
+ * Grid handles: every rank holds the complete A and computes the same R and C on its own (no communication; bitwise equal results).
+ * After an equilibration the refinement entry points sluamd_p[dz]gsrfs3d[_dev] keep their contract: they refine the ATTACHED system,
+ * which is now the scaled one (B' = R o B, X = C o X'); sluamd_[dz]AttachMatrix afterwards replaces the attached matrix. */
+#define SLUAMD_EQUED_N 0
+#define SLUAMD_EQUED_R 1
+#define SLUAMD_EQUED_C 2
+#define SLUAMD_EQUED_B 3
+typedef struct sluamd_equil {
+    int32_t equed;            /* SLUAMD_EQUED_N / _R / _C / _B */
+    int32_t info;             /* 0; i+1: row i is exactly zero; n+j+1: column j is */
+    double rowcnd, colcnd, amax;   /* what pdgsequ returns; a ratio it did not reach (info > 0) is 0 */
+    double anorm;             /* 1-norm of the matrix the handle now holds (scaled unless equed == N) */
+} sluamd_equil_t;
+int sluamd_dEquilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind,
+                        const double *nzval, const sluamd_int_t *perm_c, sluamd_equil_t *out);
+int sluamd_zEquilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind,
+                        const sluamd_doublecomplex *nzval, const sluamd_int_t *perm_c, sluamd_equil_t *out);
+/* R[n] and C[n] to the host (either may be NULL); both precisions; all ones where that side was not scaled (also before any
+ * equilibration) */
+int sluamd_GetScalings(sluamd_handle_t h, double *r, double *c);
+/* The solve phase of the expert driver: B and X in the ORIGINAL ordering and scaling, column-major, ld in values; B is not modified.
+ * Needs an attached matrix (for perm_c: sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix); works with or without equilibration.
+ *   xp[perm_c[i], j] = s_in[i] B[i, j];  the existing solve (sluamd_p[dz]gstrs3d_trans_dev) on xp;  X[i, j] = s_out[i] y[perm_c[i], j]
+ * with SLUAMD_NOTRANS: s_in = R (if row-scaled), s_out = C (if column-scaled); SLUAMD_TRANS / SLUAMD_CONJ: s_in = C, s_out = R.
+ * refine != 0: the refinement loop of sluamd_p[dz]gsrfs3d runs on the scaled system between solve and unscaling, as in the reference
+ * (this path makes five passes over the n x nrhs block instead of two: X' gathered unscaled, B' = s_in o B formed in the work block for
+ * the residuals, X unscaled in place at the end; each entry point also synchronises its stream once beside the waits of the wrapped calls);
+ * berr[nrhs] and *steps as there (both may be NULL when refine == 0).  refine with SLUAMD_TRANS / SLUAMD_CONJ: SLUAMD_EINVAL (no transposed
+ * SpMV).  Grid handles: the replicated form (complete B in, complete X out, collective); SLUAMD_TRANS / SLUAMD_CONJ there:
+ * SLUAMD_EINVAL, as for sluamd_p[dz]gstrs3d_trans.  nrhs == 0 returns 0. */
+int sluamd_pdgssvx3d_solve(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs,
+                           int refine, double *berr, int32_t *steps);
+int sluamd_pdgssvx3d_solve_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs,
+                               int refine, double *berr, int32_t *steps);
+int sluamd_pzgssvx3d_solve(sluamd_handle_t h, int trans, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X,
+                           int64_t ldx, int32_t nrhs, int refine, double *berr, int32_t *steps);
+int sluamd_pzgssvx3d_solve_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
+                               int64_t ldx, int32_t nrhs, int refine, double *berr, int32_t *steps);
+
 /* ------------------------------------------------------------------------------------------------
  * Process grids: nprow x npcol x npdep ranks, one rank per GPU (gridinfo3d_t, superlu_defs.h:385-420).
  *

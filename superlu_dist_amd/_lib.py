@@ -41,6 +41,12 @@ class Stats(C.Structure):
                 ("t_schur_big_ms", C.c_double), ("flops_schur_exact_big", C.c_double), ("schur_bytes_alg_big", C.c_double)]
 
 
+class Equil(C.Structure):
+    """sluamd_equil_t"""
+    _fields_ = [("equed", C.c_int32), ("info", C.c_int32), ("rowcnd", C.c_double), ("colcnd", C.c_double), ("amax", C.c_double),
+                ("anorm", C.c_double)]
+
+
 EXPORTS = [
     "sluamd_default_options", "sluamd_dCreateLUHandle", "sluamd_dSetValues", "sluamd_pdgstrf3d",
     "sluamd_dCopyLU2Host", "sluamd_pdgstrs3d", "sluamd_pdgstrs3d_dev", "sluamd_pdgstrs3d_dist", "sluamd_pzgstrs3d_dist", "sluamd_dDestroyLUHandle",
@@ -50,6 +56,8 @@ EXPORTS = [
     "sluamd_dAttachMatrix", "sluamd_pdgsrfs3d", "sluamd_pdgsrfs3d_dev",
     "sluamd_zAttachMatrix", "sluamd_pzgsrfs3d", "sluamd_pzgsrfs3d_dev",
     "sluamd_pdgstrs3d_trans", "sluamd_pdgstrs3d_trans_dev", "sluamd_pzgstrs3d_trans", "sluamd_pzgstrs3d_trans_dev",
+    "sluamd_dEquilibrate", "sluamd_zEquilibrate", "sluamd_GetScalings",
+    "sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev",
     "sluamd_comm_rccl_unique_id", "sluamd_comm_create_rccl", "sluamd_comm_create_callbacks", "sluamd_comm_create_local",
     "sluamd_comm_selftest", "sluamd_comm_rank", "sluamd_comm_size", "sluamd_comm_destroy", "sluamd_dCreateLUHandleGrid",
     "sluamd_dCreateLUHandleFromSymbGrid", "sluamd_zCreateLUHandleGrid", "sluamd_zCreateLUHandleFromSymbGrid",
@@ -133,6 +141,15 @@ def bind(L):
     for name in ("sluamd_pdgstrs3d_trans", "sluamd_pdgstrs3d_trans_dev", "sluamd_pzgstrs3d_trans", "sluamd_pzgstrs3d_trans_dev"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int32]
+    # equilibration and the expert driver's solve phase: only in the product library (the CPU test build has no equilibration kernels)
+    for name in ("sluamd_dEquilibrate", "sluamd_zEquilibrate"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int32, P_int, P_int, C.c_void_p, P_int, C.POINTER(Equil)]
+    if hasattr(L, "sluamd_GetScalings"):
+        L.sluamd_GetScalings.argtypes = [C.c_void_p, P_dbl, P_dbl]
+    for name in ("sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int, P_dbl, P_int]
     L.sluamd_comm_rccl_unique_id.argtypes = [C.c_void_p]
     L.sluamd_comm_create_rccl.argtypes = [C.POINTER(C.c_void_p), C.c_void_p] + [C.c_int] * 7
     L.sluamd_comm_create_callbacks.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CommCallbacks)] + [C.c_int] * 6

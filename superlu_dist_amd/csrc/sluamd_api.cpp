@@ -243,17 +243,20 @@ static int create_from_symb(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_
         if ((rc = scatter_positions(*H, *sy, t, rowptr, colind, perm_c_final, pos))) return fail(rc);
         H->setup.lap("scatter_positions");
         const int w = z ? 2 : 1;   // doubles per value
-        std::vector<int64_t> pos2; std::vector<double> val2;
-        pos2.reserve(pos.size()); val2.reserve(pos.size() * w);
+        std::vector<int64_t> pos2; std::vector<double> val2; std::vector<int> ent2;   // ent2: index in the caller's CSR (32 bits: the ABI's indices are, so nnz(A) < 2^31)
+        pos2.reserve(pos.size()); val2.reserve(pos.size() * w); ent2.reserve(pos.size());
         for (size_t e = 0; e < pos.size(); ++e)
-            if (pos[e] >= 0) { pos2.push_back(pos[e]); for (int q = 0; q < w; ++q) val2.push_back(nzval[e * w + q]); }
+            if (pos[e] >= 0) { pos2.push_back(pos[e]); ent2.push_back((int) e); for (int q = 0; q < w; ++q) val2.push_back(nzval[e * w + q]); }
         const int64_t nnz = (int64_t) pos2.size();
         const size_t esz = z ? 16 : 8;
         if (hipMalloc((void **) &H->d_apos, sizeof(int64_t) * std::max<int64_t>(nnz, 1)) != hipSuccess ||
+            hipMalloc((void **) &H->d_aent, sizeof(int) * std::max<int64_t>(nnz, 1)) != hipSuccess ||
             hipMalloc((void **) &H->d_aval, esz * std::max<int64_t>(nnz, 1)) != hipSuccess) { set_error("hipMalloc failed"); return fail(SLUAMD_ENOMEM); }
         H->a_nnz = nnz;
+        H->a_csr_nnz = (int64_t) pos.size();
         if (nnz) {
             if (hipMemcpy(H->d_apos, pos2.data(), sizeof(int64_t) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(H->d_aent, ent2.data(), sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(H->d_aval, val2.data(), esz * nnz, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); return fail(SLUAMD_EHIP); }
             if (z) eng::zscatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, nnz);
             else eng::scatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, nnz);
@@ -592,6 +595,10 @@ void sluamd_dDestroyLUHandle(sluamd_handle_t h)
     if (H->d_w) hipFree(H->d_w);
     if (H->d_apos) hipFree(H->d_apos);
     if (H->d_aval) hipFree(H->d_aval);
+    if (H->d_aent) hipFree(H->d_aent);
+    if (H->d_eq_r) hipFree(H->d_eq_r);
+    if (H->d_eq_c) hipFree(H->d_eq_c);
+    if (H->d_eq_work) hipFree(H->d_eq_work);
     if (H->h_pinned) hipHostFree(H->h_pinned);
     if (H->d_bloc) hipFree(H->d_bloc);
     for (void *q : H->dist.bufs) hipFree(q);

@@ -1,0 +1,221 @@
+// sluamd_equil.cpp -- Equil = YES for handles created from the symbolic structure: pdgsequ + pdlaqgs on the device (SRC/double/pdgsequ.c:126-215,
+// SRC/double/pdlaqgs.c:89-146; complex16: pzgsequ.c / pzlaqgs.c) and the solve phase of the expert driver in the caller's ordering and scaling
+// (pdgssvx3d.c:1450-1465 B scaled before the solve, :1806-1821 X after it).  Contract: include/superlu_dist_amd.h.
+// A file of its own: the CPU test build (oracle/Makefile) links a fixed list of the host sources against a CPU restatement of the older kernels only, so
+// no file of that list may reference the equilibration kernels (eng::eq_*).
+//
+// The device computes what is large (maxima per row and column, scaling, column sums, gather into the store order); the decisions of pdgsequ / pdlaqgs
+// are a handful of scalar comparisons on the host between the launches.  The solve wraps the existing drivers: sluamd_p[dz]gstrs3d_trans_dev between two
+// fused permute-and-scale launches, sluamd_p[dz]gsrfs3d_dev for the refinement (three more passes over the block there, see solve_dev) -- the multi-right-hand-side block forms, the grids' replicated form and
+// their error codes come with them.
+#include <cstring>
+#include "sluamd_refine.h"
+
+using namespace sluamd;
+
+namespace {
+
+typedef unsigned long long u64;
+double as_double(u64 b) { double d; memcpy(&d, &b, sizeof d); return d; }
+
+int equilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const void *nzval, const sluamd_int_t *perm_c,
+                sluamd_equil_t *out, bool z, const char *who)
+{
+    const std::string me = std::string(who) + ": ";
+    if (!h || !rowptr || !colind || !nzval || !perm_c || !out) { set_error(me + "null argument"); return SLUAMD_EINVAL; }
+    Handle *H = &h->H;
+    if (H->z != z) { set_error(me + (z ? "double handle: call sluamd_dEquilibrate" : "complex16 handle: call sluamd_zEquilibrate")); return SLUAMD_EINVAL; }
+    if (!H->d_aent || H->a_csr_nnz < 0) { set_error(me + "the handle was not created from the symbolic structure (sluamd_[dz]CreateLUHandleFromSymb[Grid]): the caller of a view-created handle scales its own values"); return SLUAMD_EINVAL; }
+    if (n != H->hs.n || rowptr[n] != H->a_csr_nnz) { set_error(me + "n or the number of entries differs from the matrix the handle was created from"); return SLUAMD_EINVAL; }
+    if (H->eq_done) { set_error(me + "the handle has been equilibrated already"); return SLUAMD_EINVAL; }
+    if (int rc = attach_rfs(h, n, rowptr, colind, nzval, perm_c, z, who)) return rc;
+    *out = sluamd_equil_t{SLUAMD_EQUED_N, 0, 0.0, 0.0, 0.0, 0.0};
+    if (n == 0) { out->rowcnd = out->colcnd = 1.0; H->eq_done = true; return 0; }      // pdgsequ.c:114-119
+    // eq_done is set on success only: a failed call leaves the handle open for another one, which attaches the caller's (unscaled) values afresh
+    struct Red { unsigned long long *p = nullptr; ~Red() { if (p) hipFree(p); } } red_guard;
+    if (H->d_eq_r) { hipFree(H->d_eq_r); H->d_eq_r = nullptr; }
+    if (H->d_eq_c) { hipFree(H->d_eq_c); H->d_eq_c = nullptr; }
+    hipStream_t s = H->stream;
+    const int64_t nnz = H->rfs_nnz;
+    u64 *d_red = nullptr;
+    HIPCHK(hipMalloc((void **) &H->d_eq_r, sizeof(double) * n));
+    HIPCHK(hipMalloc((void **) &H->d_eq_c, sizeof(double) * n));
+    HIPCHK(hipMalloc((void **) &d_red, 3 * sizeof(u64)));
+    red_guard.p = d_red;
+    // the three global values of one reduction launch: {min, max, first index of an exact zero}
+    u64 red[3];
+    auto reset = [&]() { const u64 init[3] = {~0ull, 0ull, ~0ull}; return hipMemcpyAsync(d_red, init, sizeof init, hipMemcpyHostToDevice, s) == hipSuccess ? hipStreamSynchronize(s) : hipErrorUnknown; };
+    auto fetch = [&]() { return hipMemcpyAsync(red, d_red, sizeof red, hipMemcpyDeviceToHost, s) == hipSuccess ? hipStreamSynchronize(s) : hipErrorUnknown; };
+    const double smlnum = 0x1p-1022, bignum = 1.0 / smlnum;          // dmach_dist("S")
+    int mode = 0;                                                   // bit 0: rows, bit 1: columns
+    do {
+        HIPCHK(reset());
+        eng::eq_rowmax(s, z, n, nnz, H->d_rfs_rp, H->d_rfs_av, H->d_eq_r, d_red);
+        HIPCHK(fetch());
+        double rcmin = std::min(bignum, as_double(red[0])), rcmax = as_double(red[1]);
+        out->amax = rcmax;
+        if (rcmin == 0.0) { out->info = (int32_t) red[2] + 1; break; }                     // pdgsequ.c:158-164
+        eng::eq_invert(s, n, H->d_eq_r, smlnum, bignum);
+        out->rowcnd = std::max(rcmin, smlnum) / std::min(rcmax, bignum);
+        HIPCHK(hipMemsetAsync(H->d_eq_c, 0, sizeof(double) * n, s));
+        eng::eq_colmax(s, z, n, nnz, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, H->d_eq_r, H->d_eq_c);
+        HIPCHK(reset());
+        eng::eq_reduce(s, n, H->d_eq_c, d_red);
+        HIPCHK(fetch());
+        rcmin = std::min(bignum, as_double(red[0])); rcmax = as_double(red[1]);
+        if (rcmin == 0.0) { out->info = n + (int32_t) red[2] + 1; break; }                 // pdgsequ.c:202-208
+        eng::eq_invert(s, n, H->d_eq_c, smlnum, bignum);
+        out->colcnd = std::max(rcmin, smlnum) / std::min(rcmax, bignum);
+        // pdlaqgs.c:107-146
+        const double THRESH = 0.1, small = smlnum / 0x1p-52, large = 1.0 / small;          // dmach("Safe minimum") / dmach("Precision")
+        if (out->rowcnd >= THRESH && out->amax >= small && out->amax <= large) mode = out->colcnd >= THRESH ? 0 : 2;
+        else mode = out->colcnd >= THRESH ? 1 : 3;
+    } while (0);
+    // scaling in place + the 1-norm of what is left (mode 0: the norm alone); the column sums go through the refinement's work vector
+    double *colsum = H->d_rfs_work;
+    HIPCHK(hipMemsetAsync(colsum, 0, sizeof(double) * n, s));
+    eng::eq_scale_norm(s, z, n, nnz, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, H->d_eq_r, H->d_eq_c, mode, colsum);
+    HIPCHK(reset());
+    eng::eq_reduce(s, n, colsum, d_red);
+    HIPCHK(fetch());
+    out->anorm = as_double(red[1]);
+    out->equed = mode == 0 ? SLUAMD_EQUED_N : mode == 1 ? SLUAMD_EQUED_R : mode == 2 ? SLUAMD_EQUED_C : SLUAMD_EQUED_B;
+    if (mode) {   // the store takes the scaled values (equed == N: it holds them already)
+        eng::eq_gather(s, z, H->a_nnz, H->d_aent, H->d_rfs_av, H->d_aval);
+        if (int rc = sluamd_dResetValues(h)) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    H->eq_row = (mode & 1) != 0; H->eq_col = (mode & 2) != 0;
+    H->eq_done = true;
+    return 0;
+}
+
+int ensure_work(Handle *H, int64_t doubles)
+{
+    if (doubles <= H->eq_work_cap) return 0;
+    if (H->d_eq_work) hipFree(H->d_eq_work);
+    H->d_eq_work = nullptr; H->eq_work_cap = 0;
+    HIPCHK(hipMalloc((void **) &H->d_eq_work, sizeof(double) * (size_t) doubles));
+    H->eq_work_cap = doubles;
+    return 0;
+}
+
+// the checks every entry point shares; 1: nothing to do (nrhs == 0)
+int check_solve(sluamd_handle_t h, int trans, const void *B, int64_t ldb, const void *X, int64_t ldx, int32_t nrhs, int refine, const double *berr,
+                int32_t *steps, bool z, const char *name)
+{
+    const std::string me = std::string(name) + ": ";
+    if (!h || !B || !X || nrhs < 0 || ldb < h->H.hs.n || ldx < h->H.hs.n || (refine && !berr)) { set_error(me + "bad solve arguments"); return SLUAMD_EINVAL; }
+    if (trans != SLUAMD_NOTRANS && trans != SLUAMD_TRANS && trans != SLUAMD_CONJ) { set_error(me + "trans must be SLUAMD_NOTRANS, SLUAMD_TRANS or SLUAMD_CONJ"); return SLUAMD_EINVAL; }
+    const Handle *H = &h->H;
+    if (H->z != z) { set_error(me + (z ? "double handle: call sluamd_pdgssvx3d_solve" : "complex16 handle: call sluamd_pzgssvx3d_solve")); return SLUAMD_EINVAL; }
+    if (!H->d_rfs_pc || H->rfs_z != z) { set_error(me + "no matrix attached (perm_c): call sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix first"); return SLUAMD_EINVAL; }
+    if (refine && trans != SLUAMD_NOTRANS) { set_error(me + "refining a transposed system needs a transposed SpMV (not built)"); return SLUAMD_EINVAL; }
+    if (trans != SLUAMD_NOTRANS && H->grid.size() > 1) { set_error(me + "transposed solves need a 1 x 1 x 1 handle"); return SLUAMD_EINVAL; }
+    if (steps) *steps = 0;
+    return nrhs == 0 ? 1 : 0;
+}
+
+// d_B, d_X: device, original ordering and scaling; xp: n x nrhs values of work space (ld n)
+int solve_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, int refine, double *berr, int32_t *steps,
+              double *xp)
+{
+    Handle *H = &h->H;
+    HIPCHK(hipSetDevice(H->device));
+    const bool z = H->z;
+    const int n = (int) H->hs.n;
+    hipStream_t s = H->stream;
+    const double *R = H->eq_row ? H->d_eq_r : nullptr, *Cs = H->eq_col ? H->d_eq_c : nullptr;
+    const double *s_in = trans == SLUAMD_NOTRANS ? R : Cs, *s_out = trans == SLUAMD_NOTRANS ? Cs : R;      // pdgssvx3d.c:1450-1465, :1806-1821
+    eng::eq_permscale(s, z, false, n, nrhs, H->d_rfs_pc, s_in, d_B, ldb, xp, n);
+    HIPCHK(hipGetLastError());
+    int rc = z ? sluamd_pzgstrs3d_trans_dev(h, trans, reinterpret_cast<sluamd_doublecomplex *>(xp), n, nrhs) : sluamd_pdgstrs3d_trans_dev(h, trans, xp, n, nrhs);
+    if (rc) return rc;
+    if (!refine) {
+        eng::eq_permscale(s, z, true, n, nrhs, H->d_rfs_pc, s_out, xp, n, d_X, ldx);
+    } else {   // the scaled system is refined, then X = s_out o X' (pdgssvx3d.c:1700-1821)
+        eng::eq_permscale(s, z, true, n, nrhs, H->d_rfs_pc, nullptr, xp, n, d_X, ldx);
+        eng::eq_permscale(s, z, false, n, nrhs, nullptr, s_in, d_B, ldb, xp, n);
+        HIPCHK(hipGetLastError());
+        rc = z ? sluamd_pzgsrfs3d_dev(h, reinterpret_cast<const sluamd_doublecomplex *>(xp), n, reinterpret_cast<sluamd_doublecomplex *>(d_X), ldx, nrhs, berr, steps)
+               : sluamd_pdgsrfs3d_dev(h, xp, n, d_X, ldx, nrhs, berr, steps);
+        if (rc) return rc;
+        if (s_out) eng::eq_permscale(s, z, true, n, nrhs, nullptr, s_out, d_X, ldx, d_X, ldx);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int solve_entry(sluamd_handle_t h, int trans, const void *B, int64_t ldb, void *X, int64_t ldx, int32_t nrhs, int refine, double *berr, int32_t *steps, bool z,
+                bool host, const char *name)
+{
+    const int c = check_solve(h, trans, B, ldb, X, ldx, nrhs, refine, berr, steps, z, name);
+    if (c) return c < 0 ? c : 0;
+    Handle *H = &h->H;
+    HIPCHK(hipSetDevice(H->device));
+    const int vs = z ? 2 : 1;
+    const int64_t n = H->hs.n, blk = n * nrhs * vs;              // doubles of one n x nrhs block
+    if (int rc = ensure_work(H, host ? 3 * blk : blk)) return rc;
+    if (!host) return solve_dev(h, trans, (const double *) B, ldb, (double *) X, ldx, nrhs, refine, berr, steps, H->d_eq_work);
+    double *d_b = H->d_eq_work + blk, *d_x = H->d_eq_work + 2 * blk;
+    const size_t row = sizeof(double) * (size_t) n * vs;
+    HIPCHK(hipMemcpy2D(d_b, row, B, sizeof(double) * (size_t) ldb * vs, row, (size_t) nrhs, hipMemcpyHostToDevice));
+    if (int rc = solve_dev(h, trans, d_b, n, d_x, n, nrhs, refine, berr, steps, H->d_eq_work)) return rc;
+    HIPCHK(hipMemcpy2D(X, sizeof(double) * (size_t) ldx * vs, d_x, row, row, (size_t) nrhs, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sluamd_dEquilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const double *nzval,
+                        const sluamd_int_t *perm_c, sluamd_equil_t *out)
+{
+    return equilibrate(h, n, rowptr, colind, nzval, perm_c, out, false, "sluamd_dEquilibrate");
+}
+
+int sluamd_zEquilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const sluamd_doublecomplex *nzval,
+                        const sluamd_int_t *perm_c, sluamd_equil_t *out)
+{
+    return equilibrate(h, n, rowptr, colind, nzval, perm_c, out, true, "sluamd_zEquilibrate");
+}
+
+int sluamd_GetScalings(sluamd_handle_t h, double *r, double *c)
+{
+    if (!h) { set_error("sluamd_GetScalings: null handle"); return SLUAMD_EINVAL; }
+    Handle *H = &h->H;
+    HIPCHK(hipSetDevice(H->device));
+    const size_t n = (size_t) H->hs.n;
+    if (r) { if (H->eq_row) HIPCHK(hipMemcpy(r, H->d_eq_r, sizeof(double) * n, hipMemcpyDeviceToHost)); else std::fill(r, r + n, 1.0); }
+    if (c) { if (H->eq_col) HIPCHK(hipMemcpy(c, H->d_eq_c, sizeof(double) * n, hipMemcpyDeviceToHost)); else std::fill(c, c + n, 1.0); }
+    return 0;
+}
+
+int sluamd_pdgssvx3d_solve(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, int refine, double *berr,
+                           int32_t *steps)
+{
+    return solve_entry(h, trans, B, ldb, X, ldx, nrhs, refine, berr, steps, false, true, "sluamd_pdgssvx3d_solve");
+}
+
+int sluamd_pdgssvx3d_solve_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, int refine, double *berr,
+                               int32_t *steps)
+{
+    return solve_entry(h, trans, d_B, ldb, d_X, ldx, nrhs, refine, berr, steps, false, false, "sluamd_pdgssvx3d_solve_dev");
+}
+
+int sluamd_pzgssvx3d_solve(sluamd_handle_t h, int trans, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X, int64_t ldx, int32_t nrhs,
+                           int refine, double *berr, int32_t *steps)
+{
+    return solve_entry(h, trans, B, ldb, X, ldx, nrhs, refine, berr, steps, true, true, "sluamd_pzgssvx3d_solve");
+}
+
+int sluamd_pzgssvx3d_solve_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X, int64_t ldx,
+                               int32_t nrhs, int refine, double *berr, int32_t *steps)
+{
+    return solve_entry(h, trans, d_B, ldb, d_X, ldx, nrhs, refine, berr, steps, true, false, "sluamd_pzgssvx3d_solve_dev");
+}
+
+}  // extern "C"

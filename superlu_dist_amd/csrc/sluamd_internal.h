@@ -366,6 +366,10 @@ struct Handle {
     double *d_xtmp = nullptr; int64_t xtmp_cap = 0;   // exchange staging of the distributed solve / ancestor reduction
     double *d_w = nullptr; int64_t w_cap = 0;         // second vector of the 1 x 1-layer sweeps (out-of-place diagonal solves: forward solution, backward accumulators)
     int64_t *d_apos = nullptr; double *d_aval = nullptr; int64_t a_nnz = 0;  // A's entries for device-side (re)distribution
+    int *d_aent = nullptr; int64_t a_csr_nnz = -1;            // ... and the index of each of them in the caller's CSR (handles created from the symbolic structure)
+    // equilibration (sluamd_[dz]Equilibrate, sluamd_equil.cpp): R and C on the device, what was applied, and the work block of the expert solve
+    double *d_eq_r = nullptr, *d_eq_c = nullptr; bool eq_done = false, eq_row = false, eq_col = false;
+    double *d_eq_work = nullptr; int64_t eq_work_cap = 0;     // [xp | B | X] of sluamd_p[dz]gssvx3d_solve (doubles)
     // iterative refinement (sluamd_dAttachMatrix / sluamd_zAttachMatrix): the ORIGINAL matrix in CSR + perm_c, and work vectors
     // (values and vectors in doubles: 2 per value when rfs_z)
     int *d_rfs_rp = nullptr, *d_rfs_ci = nullptr, *d_rfs_pc = nullptr; double *d_rfs_av = nullptr;
@@ -511,6 +515,17 @@ void bwd_update_t(hipStream_t s, const DevTables &T, const int *nodes, const int
 void zsolve_diag_t(hipStream_t s, bool upper, bool conj, const DevTables &T, const int *nodes, int nn, void *x, int64_t ldx, int nrhs, int max_nsupc);
 void zfwd_update_t(hipStream_t s, bool conj, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, int64_t ldx, int nrhs, int max_nsupc);
 void zbwd_update_t(hipStream_t s, bool conj, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, int64_t ldx, int nrhs);
+// equilibration on the attached CSR copy of A (sluamd_ekernels.inc; z: doublecomplex values).  Referenced only by sluamd_equil.cpp (the CPU test build of the
+// host sources has no restatement of them).  red: three 64-bit words {min bits, max bits, first index whose value is exactly 0}, set to {~0, 0, ~0} before
+// eq_rowmax / eq_reduce; eq_colmax needs c zero-filled, eq_scale_norm colsum zero-filled; mode bit 0: scale by r[i], bit 1: by c[j] (in that order)
+void eq_rowmax(hipStream_t s, bool z, int n, int64_t nnz, const int *rp, const void *av, double *r, unsigned long long *red);
+void eq_reduce(hipStream_t s, int n, const double *v, unsigned long long *red);
+void eq_invert(hipStream_t s, int n, double *v, double smlnum, double bignum);
+void eq_colmax(hipStream_t s, bool z, int n, int64_t nnz, const int *rp, const int *ci, const void *av, const double *r, double *c);
+void eq_scale_norm(hipStream_t s, bool z, int n, int64_t nnz, const int *rp, const int *ci, void *av, const double *r, const double *c, int mode, double *colsum);
+void eq_gather(hipStream_t s, bool z, int64_t cnt, const int *ent, const void *av, void *out);
+// gather = false: dst[perm[i], j] = scale[i] * src[i, j]; true: dst[i, j] = scale[i] * src[perm[i], j]; scale / perm may be null (ones / identity); ld in values
+void eq_permscale(hipStream_t s, bool z, bool gather, int n, int nrhs, const int *perm, const double *scale, const void *src, int64_t lds, void *dst, int64_t ldd);
 }  // namespace eng
 
 }  // namespace sluamd

@@ -180,6 +180,7 @@ class LUHandle:
         self._h = h
         self.store = store
         self.z = False
+        self.n = None if store is None else store.n       # order of the matrix (from_symbolic sets it)
 
     @staticmethod
     def _opts(replace_tiny=False, deterministic=False, device=-1, info_rule=0):
@@ -216,12 +217,13 @@ class LUHandle:
             _lib.check(L.sluamd_zCreateLUHandleFromSymb(C.byref(h), symb._h, _pi(symb.rowptr), _pi(symb.colind),
                                                         nz.ctypes.data_as(C.c_void_p), _pi(symb.perm_c), C.byref(o)),
                        "sluamd_zCreateLUHandleFromSymb")
-            obj = cls(h, None); obj.z = True
+            obj = cls(h, None); obj.z = True; obj.n = symb.n
             return obj
         nz = np.ascontiguousarray(nzval, dtype=np.float64)
         _lib.check(L.sluamd_dCreateLUHandleFromSymb(C.byref(h), symb._h, _pi(symb.rowptr), _pi(symb.colind), _pd(nz),
                                                     _pi(symb.perm_c), C.byref(o)), "sluamd_dCreateLUHandleFromSymb")
-        return cls(h, None)
+        obj = cls(h, None); obj.n = symb.n
+        return obj
 
     def set_values(self, store):
         L = _lib.load()
@@ -300,6 +302,24 @@ class LUHandle:
         return _gsrfs3d_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs)
 
     pzgsrfs3d_dev = pdgsrfs3d_dev
+
+    def equilibrate(self, n, rowptr, colind, nzval, perm_c):
+        """Equil = YES on a handle made by from_symbolic (sluamd_[dz]Equilibrate): pass the arrays the handle was created from.  Returns
+        dict(equed="N"|"R"|"C"|"B", info, rowcnd, colcnd, amax, anorm); the handle then holds the scaled matrix, unfactored."""
+        return _equilibrate(self._h, self.z, n, rowptr, colind, nzval, perm_c)
+
+    def scalings(self):
+        """(R, C) of the equilibration; all ones where that side was not scaled (sluamd_GetScalings)"""
+        return _scalings(self._h, self.n)
+
+    def gssvx_solve(self, b, trans="N", refine=False):
+        """The solve phase of the expert driver (sluamd_p[dz]gssvx3d_solve): b in the ORIGINAL ordering and scaling -> x likewise; needs
+        equilibrate() or attach_matrix() (for perm_c).  refine=True returns (x, berr, steps)."""
+        return _gssvx_solve(self._h, self.z, b, trans, refine)
+
+    def gssvx_solve_dev(self, d_b, ldb, d_x, ldx, nrhs, trans="N", refine=False):
+        """the same on device pointers (ld in values); d_b is not modified; returns (berr, steps) when refine"""
+        return _gssvx_solve_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans, refine)
 
     def set_profile(self, on=True):
         _lib.load().sluamd_set_profile(self._h, int(on))
@@ -388,6 +408,46 @@ def _gsrfs3d_dev(h, z, d_b, ldb, d_x, ldx, nrhs):
     return berr[:int(nrhs)], steps.value
 
 
+EQUED = "NRCB"      # SLUAMD_EQUED_N / _R / _C / _B
+
+
+def _equilibrate(h, z, n, rowptr, colind, nzval, perm_c):
+    rp = np.ascontiguousarray(rowptr, dtype=np.int32); ci = np.ascontiguousarray(colind, dtype=np.int32)
+    pc = np.ascontiguousarray(perm_c, dtype=np.int32)
+    v = np.ascontiguousarray(nzval, dtype=np.complex128 if z else np.float64)
+    e = _lib.Equil()
+    name = "sluamd_zEquilibrate" if z else "sluamd_dEquilibrate"
+    _lib.check(_lib.entry(name)(h, int(n), _pi(rp), _pi(ci), v.ctypes.data_as(C.c_void_p), _pi(pc), C.byref(e)), name)
+    return dict(equed=EQUED[e.equed], info=int(e.info), rowcnd=float(e.rowcnd), colcnd=float(e.colcnd), amax=float(e.amax), anorm=float(e.anorm))
+
+
+def _scalings(h, n):
+    r = np.empty(n); c = np.empty(n)
+    _lib.check(_lib.entry("sluamd_GetScalings")(h, _pd(r), _pd(c)), "sluamd_GetScalings")
+    return r, c
+
+
+def _gssvx_solve(h, z, b, trans, refine):
+    t = _trans_code(trans)
+    b = np.asfortranarray(np.array(b, dtype=np.complex128 if z else np.float64))
+    if b.ndim == 1:
+        b = np.asfortranarray(b[:, None])
+    x = np.zeros_like(b, order="F")
+    berr = np.zeros(max(b.shape[1], 1)); steps = C.c_int32(0)
+    name = "sluamd_pzgssvx3d_solve" if z else "sluamd_pdgssvx3d_solve"
+    _lib.check(_lib.entry(name)(h, t, b.ctypes.data_as(C.c_void_p), max(b.shape[0], 1), x.ctypes.data_as(C.c_void_p), max(x.shape[0], 1), b.shape[1],
+                                int(bool(refine)), _pd(berr), C.byref(steps)), name)
+    return (x, berr[:b.shape[1]], steps.value) if refine else x
+
+
+def _gssvx_solve_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans, refine):
+    berr = np.zeros(max(int(nrhs), 1)); steps = C.c_int32(0)
+    name = "sluamd_pzgssvx3d_solve_dev" if z else "sluamd_pdgssvx3d_solve_dev"
+    _lib.check(_lib.entry(name)(h, _trans_code(trans), C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), int(bool(refine)),
+                                _pd(berr), C.byref(steps)), name)
+    return (berr[:int(nrhs)], steps.value) if refine else None
+
+
 def _forest_view(forests):
     """forests = dict(maxLvl, myTreeIdxs, myZeroTrIdxs, nodeLists=[array or None per forest])"""
     fv = ForestView()
@@ -414,15 +474,20 @@ def pivot_thresh(n, rowptr, colind, nzval):
 
 
 def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, replace_tiny=False, anorm=None,
-              keep=False, refine=False, trans="N"):
+              keep=False, refine=False, trans="N", equil=False):
     """Solve A x = b -- trans = "T": A^T x = b, "C": A^H x = b, with the same factorisation of A -- through the GPU hot path: symbolic (host) -> device-resident distribute -> pdgstrf3d ->
     pdgstrs3d, with Equil = NO, RowPerm = NOROWPERM, ColPerm = MY_PERMC/NATURAL, IterRefine = NOREFINE
     (the timing configuration of BASELINE.md section 4); refine=True adds IterRefine = SLU_DOUBLE (pdgsrfs3d on the device;
-    pzgsrfs3d for complex nzval) and puts `berr` / `refine_steps` into the stats.  Returns (x, info, stats[, handle, symb])."""
+    pzgsrfs3d for complex nzval) and puts `berr` / `refine_steps` into the stats.  equil=True: Equil = YES -- the handle is equilibrated on
+    the device (LUHandle.equilibrate), thresh comes from the 1-norm of the scaled matrix, and the solve (and the refinement) runs through
+    LUHandle.gssvx_solve in the caller's ordering and scaling; `equed`, `rowcnd`, `colcnd`, `amax` and a positive `equil_info` go into the
+    stats; `anorm` is not used then.  Returns (x, info, stats[, handle, symb])."""
     if refine and _trans_code(trans):
         raise ValueError("refine=True with trans != 'N': refining a transposed system needs a transposed SpMV (not built)")
     symb = Symbolic(n, rowptr, colind, perm_c, relax, maxsup)
     h = LUHandle.from_symbolic(symb, nzval, replace_tiny=replace_tiny)
+    if equil:
+        return _gssvx3d_equil(h, symb, n, rowptr, colind, nzval, b, keep, refine, trans)
     thresh = pivot_thresh(n, rowptr, colind, nzval) if anorm is None else 0.5 * float(np.finfo(np.float32).eps) * anorm
     info = h.pdgstrf3d(thresh)
     b = np.asfortranarray(np.array(b, dtype=np.complex128 if np.iscomplexobj(nzval) else np.float64))
@@ -437,6 +502,24 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
         h.attach_matrix(n, rowptr, colind, nzval, symb.perm_c)
         x, berr, steps = h.pdgsrfs3d(b, x)
         st["berr"] = berr; st["refine_steps"] = steps
+    if keep:
+        return x, info, st, h, symb
+    h.destroy(); symb.free()
+    return x, info, st
+
+
+def _gssvx3d_equil(h, symb, n, rowptr, colind, nzval, b, keep, refine, trans):
+    """the Equil = YES path of pdgssvx3d: equilibrate on the device, thresh from the scaled matrix's 1-norm, factor, expert solve"""
+    eq = h.equilibrate(n, rowptr, colind, nzval, symb.perm_c)
+    info = h.pdgstrf3d(0.5 * float(np.finfo(np.float32).eps) * eq["anorm"])
+    out = h.gssvx_solve(b, trans=trans, refine=refine)
+    st = h.stats()
+    st.update(equed=eq["equed"], rowcnd=eq["rowcnd"], colcnd=eq["colcnd"], amax=eq["amax"])
+    if eq["info"] > 0:
+        st["equil_info"] = eq["info"]
+    x = out
+    if refine:
+        x, st["berr"], st["refine_steps"] = out
     if keep:
         return x, info, st, h, symb
     h.destroy(); symb.free()

@@ -209,6 +209,26 @@ class GridHandle:
 
     pzgsrfs3d = pdgsrfs3d
 
+    def equilibrate(self, n, rowptr, colind, nzval, perm_c):
+        """Equil = YES on a handle made by from_symbolic: every rank passes the complete matrix the handle was created from and computes
+        the same scalings on its own (sluamd_[dz]Equilibrate; no communication).  Returns the dict of LUHandle.equilibrate."""
+        from .driver import _equilibrate
+        return _equilibrate(self._h, self.z, n, rowptr, colind, nzval, perm_c)
+
+    def scalings(self):
+        from .driver import _scalings
+        return _scalings(self._h, self.n)
+
+    def gssvx_solve(self, b, trans="N", refine=False):
+        """The expert driver's solve phase, replicated form (collective): the complete b in the original ordering and scaling on every
+        rank -> the complete x (sluamd_p[dz]gssvx3d_solve); refine=True returns (x, berr, steps)."""
+        from .driver import _gssvx_solve
+        return _gssvx_solve(self._h, self.z, b, trans, refine)
+
+    def gssvx_solve_dev(self, d_b, ldb, d_x, ldx, nrhs, trans="N", refine=False):
+        from .driver import _gssvx_solve_dev
+        return _gssvx_solve_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans, refine)
+
     def copy_to_host(self, store):
         from .driver import _check_store_dtype
         _check_store_dtype(store, self.z)
