@@ -81,6 +81,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
     auto tail_level = [&](int l) { return trsm_tail > 0 && l >= S.nlevels - trsm_tail && S.lvl_off[l + 1] - S.lvl_off[l] == 1; };
     auto deferred_inv = [&](hipStream_t st, int l) {
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
+        eng::panel_site = {l, nn, -1, 1};
         eng::full_inv(st, T, S.d_nodes + n0, S.d_finv_prefix + po, nn, S.finv_prefix[po + nn], S.max_nsupc[l]);
         H->st.num_launches++;
     };
@@ -146,6 +147,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
         const int *nodes = S.d_nodes + n0;
         const int mx = S.max_nsupc[l];
+        eng::panel_site = {l, nn, -1, 0};
         if (!lv_lend.empty()) {   // the panels of this level must hold the partner layer's contributions before they are factored
             hipEvent_t e = red_wait_event(H, lv_lend[l], lv_uend[l]);
             if (e) hipStreamWaitEvent(ps, e, 0);
@@ -187,6 +189,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         const int o0 = S.ps_off[4 * l + 2 * part], o1 = S.ps_off[4 * l + 2 * part + 1], o2 = S.ps_off[4 * l + 2 * part + 2];
         const int nl = o1 - o0, nu = o2 - o1;
         if (nl + nu == 0) return;
+        eng::panel_site = {l, S.lvl_off[l + 1] - S.lvl_off[l], part, 0};
         if (gemm_panels && !tail_level(l)) eng::panel_gemm(st, T, nullptr, nullptr, nullptr, 0, nl, nu, mx, S.d_ps_units + o0);
         else eng::panel_trsm(st, T, nullptr, nullptr, nullptr, 0, nl, nu, 64, mx, S.d_ps_units + o0);
         H->st.num_launches++;
@@ -196,6 +199,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         const int *nodes = S.d_nodes + n0;
         const int mx = S.max_nsupc[l];
         const int nl = S.ltr_prefix[po + nn], nu = S.utr_prefix[po + nn];
+        eng::panel_site = {l, nn, -1, 0};
         ev_begin(H, H->ev_panel, H->ev_panel_used, ps);
         if (H->z) {   // zLPanelTrSolve / zUPanelTrSolve (ztrfCommWrapper.c): 64-row strips / 64-column chunks
             const int znl = S.zltr_prefix[po + nn], znu = S.bwd_prefix[po + nn];
@@ -548,6 +552,7 @@ int ensure_dinv(Handle *H)
     for (auto &S : H->sched)
         for (int l = 0; l < S.nlevels; ++l) {
             const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
+            eng::panel_site = {l, nn, -1, 2};       // on demand, after the factorisation
             eng::diag_inv(H->stream, H->T, S.d_nodes + n0, S.d_inv_prefix + po, nn, S.inv_prefix[po + nn]);
         }
     H->dinv_ready = true;
@@ -563,6 +568,7 @@ int ensure_inv(Handle *H)
     for (auto &S : H->sched)
         for (int l = 0; l < S.nlevels; ++l) {
             const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
+            eng::panel_site = {l, nn, -1, 2};
             eng::full_inv(H->stream, H->T, S.d_nodes + n0, S.d_finv_prefix + po, nn, S.finv_prefix[po + nn], S.max_nsupc[l]);
         }
     for (size_t gi = 0; gi < H->groups.size(); ++gi) group_inverse(H, (int) gi, H->stream);

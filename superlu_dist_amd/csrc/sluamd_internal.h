@@ -424,6 +424,11 @@ struct Handle {
 // ------------------------------------------------------------------------------------------------
 namespace eng {
 int setup();   // one-time function attributes (dynamic LDS limits)
+// SLUAMD_FACTOR_DEBUG: where the next panel-chain launch stands in the schedule -- DAG level, supernodes of the level, part of a split level (-1 = whole, 0, 1),
+// stream role (`bulk`: 0 = on the chain, 1 = deferred beside it on the bulk stream, 2 = on demand after the factorisation).  Written by the drivers in front of their eng:: calls, read only by the launch lines of the
+// wrappers (sluamd_kernels.hip) and only when the variable is set; thread-local: the ranks of a thread grid run their drivers side by side
+struct PanelSite { int level, nn, part, bulk; };
+inline thread_local PanelSite panel_site = {-1, 0, -1, 0};
 // flags: bit 0 = ReplaceTinyPivot, bit 1 = round-1 right-looking kernel, bit 2 = k_diag_lu2 built for the whole register file (tail levels).  Also leaves the inverted 32 x 32 diagonal sub-blocks of the
 // owned blocks in T.dinv (what diag_inv computes for blocks received from another rank)
 void diag_lu(hipStream_t s, const DevTables &T, const int *nodes, int nn, int max_nsupc, int flags, double thresh, int *info);

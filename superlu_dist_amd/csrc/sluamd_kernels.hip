@@ -2979,6 +2979,18 @@ int setup()
     return 0;
 }
 
+// SLUAMD_FACTOR_DEBUG: one stderr line per panel-chain launch -- which kernel form a wrapper chose for which level (panel_site: what the driver said about the
+// launch), with how many L strips and U chunks -- what the tests of the panel forms read.  Read once; nothing else depends on it
+static const bool g_factor_debug = getenv("SLUAMD_FACTOR_DEBUG") != nullptr;
+static void panel_line(const char *family, const char *form, int mx, int nl = 0, int nu = 0)
+{
+    if (!g_factor_debug) return;
+    const PanelSite p = panel_site;
+    char part[16] = "whole";
+    if (p.part >= 0) snprintf(part, sizeof part, "%d", p.part);
+    fprintf(stderr, "[sluamd panel] family=%s form=%s level=%d nn=%d mx=%d nl=%d nu=%d part=%s where=%s\n", family, form, p.level, p.nn, mx, nl, nu, part, p.bulk == 2 ? "demand" : p.bulk ? "bulk" : "chain");
+}
+
 void diag_lu(hipStream_t s, const DevTables &T, const int *nodes, int nn, int mx, int replace_tiny, double thresh, int *info)
 {
     if (nn <= 0) return;
@@ -2986,22 +2998,25 @@ void diag_lu(hipStream_t s, const DevTables &T, const int *nodes, int nn, int mx
     // bottom of the tree, thousands of blocks per launch) are throughput-bound, not latency-bound: the right-looking kernel with
     // its smaller footprint is faster there (0.85 vs 2.2 ms per launch at 100^3)
     if (!(replace_tiny & 2) && mx > 64) {
+        if (replace_tiny & 4) panel_line("diag_lu", "lu2_1", mx); else panel_line("diag_lu", "lu2_2", mx);
         if (replace_tiny & 4) hipLaunchKernelGGL(k_diag_lu2<1>, dim3(nn), dim3(256), DIAG_LU2_LDS, s, T, nodes, replace_tiny & 1, thresh, info);
         else hipLaunchKernelGGL(k_diag_lu2<2>, dim3(nn), dim3(256), DIAG_LU2_LDS, s, T, nodes, replace_tiny & 1, thresh, info);
         return;
     }
     replace_tiny &= 1;
     // (four blocks per 256-thread workgroup; one or two per workgroup measured the same beside the bulk tiles: 290.1-290.9 / 290.5-291.1 / 290.5 ms, gpurun call 9)
-    if (mx <= 64) hipLaunchKernelGGL(k_diag_lu_wave, dim3((nn + 3) / 4), dim3(256), 0, s, T, nodes, nn, replace_tiny, thresh, info);
-    else if (mx <= 128) hipLaunchKernelGGL(k_diag_lu<128>, dim3(nn), dim3(256), 0, s, T, nodes, replace_tiny, thresh, info);
-    else hipLaunchKernelGGL(k_diag_lu<256>, dim3(nn), dim3(256), 0, s, T, nodes, replace_tiny, thresh, info);
+    if (mx <= 64) { panel_line("diag_lu", "wave", mx); hipLaunchKernelGGL(k_diag_lu_wave, dim3((nn + 3) / 4), dim3(256), 0, s, T, nodes, nn, replace_tiny, thresh, info); }
+    else if (mx <= 128) { panel_line("diag_lu", "v1_128", mx); hipLaunchKernelGGL(k_diag_lu<128>, dim3(nn), dim3(256), 0, s, T, nodes, replace_tiny, thresh, info); }
+    else { panel_line("diag_lu", "v1_256", mx); hipLaunchKernelGGL(k_diag_lu<256>, dim3(nn), dim3(256), 0, s, T, nodes, replace_tiny, thresh, info); }
     if (mx <= 64) hipLaunchKernelGGL(k_diag_inv_all<4>, dim3(nn), dim3(128), 0, s, T, nodes);     // the contract: dinv of the owned blocks
     else hipLaunchKernelGGL(k_diag_inv_all<8>, dim3(nn), dim3(256), 0, s, T, nodes);
 }
 
 void diag_inv(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int ntask)
 {
-    if (ntask > 0) hipLaunchKernelGGL(k_diag_inv, dim3((ntask + 3) / 4), dim3(128), 0, s, T, nodes, prefix, nn);
+    if (ntask <= 0) return;
+    panel_line("diag_inv", "inv", 0);      // (the widest supernode of the level is not known here: mx=0)
+    hipLaunchKernelGGL(k_diag_inv, dim3((ntask + 3) / 4), dim3(128), 0, s, T, nodes, prefix, nn);
 }
 
 void panel_trsm(hipStream_t s, const DevTables &T, const int *nodes, const int *lprefix, const int *uprefix, int nn, int nl, int nu, int rs,
@@ -3009,8 +3024,8 @@ void panel_trsm(hipStream_t s, const DevTables &T, const int *nodes, const int *
 {
     if (nl + nu <= 0) return;
     const size_t lds = trsm_lds_bytes(rs, (mx + 31) & ~31);
-    if (rs == 32) hipLaunchKernelGGL(k_panel_trsm<32>, dim3(nl + nu), dim3(128), lds, s, T, nodes, lprefix, uprefix, nn, nl, units);
-    else hipLaunchKernelGGL(k_panel_trsm<64>, dim3(nl + nu), dim3(256), lds, s, T, nodes, lprefix, uprefix, nn, nl, units);
+    if (rs == 32) { panel_line("panel", "trsm32", mx, nl, nu); hipLaunchKernelGGL(k_panel_trsm<32>, dim3(nl + nu), dim3(128), lds, s, T, nodes, lprefix, uprefix, nn, nl, units); }
+    else { panel_line("panel", "trsm64", mx, nl, nu); hipLaunchKernelGGL(k_panel_trsm<64>, dim3(nl + nu), dim3(256), lds, s, T, nodes, lprefix, uprefix, nn, nl, units); }
 }
 
 #define SCHUR_LAUNCH(TM, TN, NWV, ZV, THREADS) \
@@ -3038,9 +3053,9 @@ void schur(hipStream_t s, int cfg, const DevTables &T, const int *nodes, const i
 void panel_gemm(hipStream_t s, const DevTables &T, const int *nodes, const int *lprefix, const int *uprefix, int nn, int nl, int nu, int mx, const int2 *units)
 {
     if (nl + nu <= 0) return;
-    if (mx <= 64) hipLaunchKernelGGL(k_panel_gemm<16>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl, units);
-    else if (mx <= 128) hipLaunchKernelGGL(k_panel_gemm<32>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl, units);
-    else hipLaunchKernelGGL(k_panel_gemm<64>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl, units);
+    if (mx <= 64) { panel_line("panel", "gemm16", mx, nl, nu); hipLaunchKernelGGL(k_panel_gemm<16>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl, units); }
+    else if (mx <= 128) { panel_line("panel", "gemm32", mx, nl, nu); hipLaunchKernelGGL(k_panel_gemm<32>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl, units); }
+    else { panel_line("panel", "gemm64", mx, nl, nu); hipLaunchKernelGGL(k_panel_gemm<64>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl, units); }
 }
 
 // ---- merged chain groups (sluamd_internal.h): gather of the group's block triangle, batched dense products ----------------------------------------------------------
@@ -3176,7 +3191,8 @@ void gemm_batched(hipStream_t s, const DevTables &T, const GemmDesc *d_descs, co
 }
 void full_inv(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, int mx)
 {
-    if (nwork > 0 && mx <= 64 && g_full_inv64) { hipLaunchKernelGGL(k_full_inv64, dim3((2 * nn + 3) / 4), dim3(256), 0, s, T, nodes, prefix, nn); return; }   // levels of narrow supernodes
+    if (nwork > 0 && mx <= 64 && g_full_inv64) { panel_line("full_inv", "inv64", mx); hipLaunchKernelGGL(k_full_inv64, dim3((2 * nn + 3) / 4), dim3(256), 0, s, T, nodes, prefix, nn); return; }   // levels of narrow supernodes
+    if (nwork > 0) panel_line("full_inv", "inv", mx);
     if (nwork > 0) hipLaunchKernelGGL(k_full_inv, dim3(nwork), dim3(FIS * 4), trsm_lds_bytes(FIS, (mx + 31) & ~31), s, T, nodes, prefix, nn);
 }
 
@@ -3421,21 +3437,21 @@ void zdiag_lu(hipStream_t s, const DevTables &T, const int *nodes, int nn, int m
 {
     if (nn <= 0) return;
     // levels of narrow supernodes (the leaves and the small separators: tens of thousands of blocks): one wave per block in registers
-    if (mx <= 8) hipLaunchKernelGGL(kz_diag_lu_wave_small<8>, dim3(nn), dim3(64), 0, s, T, nodes, nn, replace_tiny, thresh, info);
-    else if (mx <= 16) hipLaunchKernelGGL(kz_diag_lu_wave_small<16>, dim3(nn), dim3(64), 0, s, T, nodes, nn, replace_tiny, thresh, info);
-    else if (mx <= 32) hipLaunchKernelGGL(kz_diag_lu_wave_small<32>, dim3(nn), dim3(64), 0, s, T, nodes, nn, replace_tiny, thresh, info);
-    else if (mx <= 64 && nn <= g_zlu4_max_nodes) hipLaunchKernelGGL(kz_diag_lu_wave4, dim3(nn), dim3(256), 0, s, T, nodes, nn, replace_tiny, thresh, info);   // few blocks: four waves per block (the panel chain)
-    else if (mx <= 64) hipLaunchKernelGGL(kz_diag_lu_wave, dim3((nn + 3) / 4), dim3(256), 0, s, T, nodes, nn, replace_tiny, thresh, info);
-    else hipLaunchKernelGGL(kz_diag_lu, dim3(nn), dim3(256), zdiag_lds_bytes(mx), s, T, nodes, replace_tiny, thresh, info, mx | 1);
+    if (mx <= 8) { panel_line("diag_lu", "zwave_small8", mx); hipLaunchKernelGGL(kz_diag_lu_wave_small<8>, dim3(nn), dim3(64), 0, s, T, nodes, nn, replace_tiny, thresh, info); }
+    else if (mx <= 16) { panel_line("diag_lu", "zwave_small16", mx); hipLaunchKernelGGL(kz_diag_lu_wave_small<16>, dim3(nn), dim3(64), 0, s, T, nodes, nn, replace_tiny, thresh, info); }
+    else if (mx <= 32) { panel_line("diag_lu", "zwave_small32", mx); hipLaunchKernelGGL(kz_diag_lu_wave_small<32>, dim3(nn), dim3(64), 0, s, T, nodes, nn, replace_tiny, thresh, info); }
+    else if (mx <= 64 && nn <= g_zlu4_max_nodes) { panel_line("diag_lu", "zwave4", mx); hipLaunchKernelGGL(kz_diag_lu_wave4, dim3(nn), dim3(256), 0, s, T, nodes, nn, replace_tiny, thresh, info); }   // few blocks: four waves per block (the panel chain)
+    else if (mx <= 64) { panel_line("diag_lu", "zwave", mx); hipLaunchKernelGGL(kz_diag_lu_wave, dim3((nn + 3) / 4), dim3(256), 0, s, T, nodes, nn, replace_tiny, thresh, info); }
+    else { panel_line("diag_lu", "zlu", mx); hipLaunchKernelGGL(kz_diag_lu, dim3(nn), dim3(256), zdiag_lds_bytes(mx), s, T, nodes, replace_tiny, thresh, info, mx | 1); }
 }
 static const bool g_ztrsm_quad = getenv("SLUAMD_NO_ZTRSM_QUAD") == nullptr;
 void zpanel_trsm(hipStream_t s, const DevTables &T, const int *nodes, const int *lprefix, const int *uprefix, int nn, int nl, int nu, int mx)
 {
     if (nl + nu <= 0) return;
-    if (mx <= 16 && g_ztrsm_quad) hipLaunchKernelGGL(kz_panel_trsm_quad<4>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl);       // four lanes per row / column, 16 x 17 triangle
-    else if (mx <= 32 && g_ztrsm_quad) hipLaunchKernelGGL(kz_panel_trsm_quad<8>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl);  // 32 x 33
-    else if (mx <= 64 && g_ztrsm_quad) hipLaunchKernelGGL(kz_panel_trsm_quad<16>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl); // 64 x 65
-    else hipLaunchKernelGGL(kz_panel_trsm, dim3(nl + nu), dim3(64), 0, s, T, nodes, lprefix, uprefix, nn, nl);
+    if (mx <= 16 && g_ztrsm_quad) { panel_line("panel", "zquad4", mx, nl, nu); hipLaunchKernelGGL(kz_panel_trsm_quad<4>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl); }       // four lanes per row / column, 16 x 17 triangle
+    else if (mx <= 32 && g_ztrsm_quad) { panel_line("panel", "zquad8", mx, nl, nu); hipLaunchKernelGGL(kz_panel_trsm_quad<8>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl); }  // 32 x 33
+    else if (mx <= 64 && g_ztrsm_quad) { panel_line("panel", "zquad16", mx, nl, nu); hipLaunchKernelGGL(kz_panel_trsm_quad<16>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl); } // 64 x 65
+    else { panel_line("panel", "ztrsm", mx, nl, nu); hipLaunchKernelGGL(kz_panel_trsm, dim3(nl + nu), dim3(64), 0, s, T, nodes, lprefix, uprefix, nn, nl); }
 }
 void zschur(hipStream_t s, int cfg, const DevTables &T, const int *nodes, const int *prefix, int nn, int id_base, int ntiles, int *info,
             const int4 *ulist, int prio, const int *tmaps, int mmode, const int *xoff, int xmax)
