@@ -15,6 +15,10 @@
  * (sluamd_dCreateLUHandleFromSymb) -> sluamd_pdgstrf3d -> sluamd_pdgstrs3d -> sluamd_pdgsrfs3d (IterRefine = SLU_DOUBLE),
  * with xtrue_i = +-1 and b = A xtrue like dGenXtrue_dist / dFillRHS_dist (dutil_dist.c:598).  Prints what pddrive3d
  * prints at the end: ||X - Xtrue||_inf / ||X||_inf, plus the residual and the timings.  Exit code 0 iff residual < 1e-10.
+ *
+ *   --steps K   after the first solve, K more systems on the SAME pattern (Fact = SamePattern_SameRowPerm): the values are perturbed
+ *               deterministically, sluamd_dUpdateValues hands them to the handle (an equilibrated handle reuses R and C), then factor and
+ *               solve as before; one "STEP k" line with the residual against the perturbed matrix each, all of them < 1e-10 for exit code 0.
  */
 #include <math.h>
 #include <stdio.h>
@@ -131,7 +135,7 @@ static int read_matrix_market(const char *path, int64_t *n_out, int **rp_out, in
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s N [-nd] [--equil] | file.dat [--equil] | file.mtx [--equil]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s N [-nd] [--equil] [--steps K] | file.dat [--equil] [--steps K] | file.mtx [--equil] [--steps K]\n", argv[0]); return 2; }
     if (sluamd_device_count() < 1) { fprintf(stderr, "no HIP device: this library has no CPU fallback\n"); return 3; }
     int64_t n; int *rp, *ci; double *v;
     char *end;
@@ -139,6 +143,8 @@ int main(int argc, char **argv)
     int use_nd = argc > 2 && !strcmp(argv[2], "-nd");
     int equil = 0;                                            /* --equil: Equil = YES (pdgsequ + pdlaqgs on the device, scaled solve) */
     for (int a = 2; a < argc; ++a) if (!strcmp(argv[a], "--equil")) equil = 1;
+    long nsteps = 0;                                          /* --steps K: K same-pattern value updates after the first solve */
+    for (int a = 2; a + 1 < argc; ++a) if (!strcmp(argv[a], "--steps")) nsteps = strtol(argv[a + 1], NULL, 10);
     const size_t len = strlen(argv[1]);
     if (*end == '\0' && N > 0) { if (poisson3d((int) N, &n, &rp, &ci, &v)) return 2; }
     else if (len > 4 && !strcmp(argv[1] + len - 4, ".mtx")) {
@@ -212,7 +218,40 @@ int main(int argc, char **argv)
     printf("FACTOR time %.3f ms  (%.1f GFLOP/s)   SOLVE time %.3f ms   refinement steps %d  berr %.2e\n", st.t_factor_ms,
            flops / (st.t_factor_ms * 1e-3) / 1e9, st.t_solve_ms, steps, berr);
     printf("||X-Xtrue||/||X|| = %e   ||b-Ax||_2/||b||_2 = %e\n", err / xn, sqrt(rn / bn));
+    int bad_steps = 0;
+    double *v2 = nsteps > 0 ? (double *) malloc(sizeof(double) * (size_t) (rp[n] ? rp[n] : 1)) : NULL;
+    for (long s = 1; s <= nsteps; ++s) {
+        /* same pattern, new values: the diagonal grows by up to 1/2, the rest shrinks by up to 3/8 (a diagonally dominant A stays so) */
+        for (int64_t i = 0; i < n; ++i)
+            for (int e = rp[i]; e < rp[i + 1]; ++e)
+                v2[e] = ci[e] == i ? v[e] * (1.0 + 0.125 * (double) ((i + s) % 5)) : v[e] * (1.0 - 0.0625 * (double) ((e + 3 * s) % 7));
+        for (int64_t i = 0; i < n; ++i) {
+            double t = 0.0;
+            for (int e = rp[i]; e < rp[i + 1]; ++e) t += v2[e] * xt[ci[e]];
+            b[i] = t;
+        }
+        sluamd_update_t up;                                   /* a matrix is attached by now (sluamd_dEquilibrate / sluamd_dAttachMatrix): it takes the new values, and anorm comes back */
+        CHECK(sluamd_dUpdateValues(h, v2, &up));
+        CHECK(sluamd_pdgstrf3d(h, 1.1920928955078125e-07 * up.anorm, &info));
+        if (info) { printf("STEP %ld: INFO = %d returned from pdgstrf3d (zero pivot)\n", s, info); return 1; }
+        if (equil) {
+            CHECK(sluamd_pdgssvx3d_solve(h, SLUAMD_NOTRANS, b, n, x, n, 1, 1, &berr, &steps));
+        } else {
+            memcpy(x, b, sizeof(double) * n);
+            CHECK(sluamd_pdgstrs3d_dist(h, x, n, 1, n, 0, perm_c, perm_c));
+            CHECK(sluamd_pdgsrfs3d(h, b, n, x, n, 1, &berr, &steps));
+        }
+        double r2 = 0.0, b2 = 0.0;
+        for (int64_t i = 0; i < n; ++i) {
+            double t = b[i];
+            for (int e = rp[i]; e < rp[i + 1]; ++e) t -= v2[e] * x[ci[e]];
+            r2 += t * t; b2 += b[i] * b[i];
+        }
+        printf("STEP %ld: equed = %c  anorm %.6e  refinement steps %d  berr %.2e  ||b-Ax||_2/||b||_2 = %e\n", s, "NRCB"[up.equed], up.anorm, steps, berr, sqrt(r2 / b2));
+        if (!(sqrt(r2 / b2) < 1e-10)) bad_steps++;
+    }
+    free(v2);
     sluamd_dDestroyLUHandle(h);
     sluamd_symb_free(symb);
-    return sqrt(rn / bn) < 1e-10 ? 0 : 1;
+    return sqrt(rn / bn) < 1e-10 && !bad_steps ? 0 : 1;
 }

@@ -366,6 +366,43 @@ int sluamd_pzgssvx3d_solve(sluamd_handle_t h, int trans, const sluamd_doublecomp
 int sluamd_pzgssvx3d_solve_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
                                int64_t ldx, int32_t nrhs, int refine, double *berr, int32_t *steps);
 
+/* ---- Fact = SamePattern_SameRowPerm: new numeric values for the pattern the handle was planned for (superlu_defs.h:545-566; Newton steps, time
+ * stepping, parameter sweeps).  For handles made by sluamd_[dz]CreateLUHandleFromSymb[Grid]; a view-created handle takes new values in store form through
+ * sluamd_[dz]SetValues.  nzval: the values of the SAME CSR (rowptr / colind, rowptr[n] entries, the caller's order) the handle was created from.
+ *  1. Pattern and permutations are reused: nothing of the plan, the tables, the tile records, the exchange plans or perm_c is rebuilt.  After the call the
+ *     handle is UNFACTORED and holds the new matrix (sluamd_dGetDiagInv refuses until the next factorisation), and a later sluamd_dResetValues restores the
+ *     NEW values.
+ *  2. An equilibrated handle reuses R, C and equed, as the reference does for this value of Fact (pdgssvx3d.c:672-697: DiagScale, R and C are inputs and A is
+ *     scaled with them): the values are stored as (a r[i]) c[j], in exactly the order sluamd_[dz]Equilibrate documents, so the result can be reproduced bit
+ *     for bit on the host.  R and C are not recomputed, and sluamd_[dz]Equilibrate keeps refusing a second call; a caller whose new values have drifted far
+ *     from the old scalings creates a new handle.  out->equed returns the handle's equed (SLUAMD_EQUED_N on a handle that was never equilibrated).
+ *  3. out->anorm: the 1-norm of the matrix the handle now holds (scaled if equilibrated), for thresh = eps_single * anorm of the next sluamd_p[dz]gstrf3d; the
+ *     definition and the summation caveat of sluamd_equil_t::anorm (fp64 atomics: relative error <= k 2^-52 for a longest column of k entries; complex16: the
+ *     true modulus).  Computed only when out != NULL, and only with an attached matrix: a handle created from the symbolic structure keeps rowptr / colind on
+ *     the device only with one, and no second copy of the structure is kept for the norm -- out != NULL without an attached matrix: SLUAMD_EINVAL.
+ *  4. A matrix attached by sluamd_[dz]AttachMatrix or sluamd_[dz]Equilibrate receives the new (scaled) values too, in CSR order: sluamd_p[dz]gsrfs3d and
+ *     sluamd_p[dz]gssvx3d_solve(..., refine = 1) then refine the NEW system.  It must be the matrix the handle was created from (same number of entries,
+ *     else SLUAMD_EINVAL).  If nothing is attached, nothing is attached by this call.
+ *  5. Grid handles: every rank passes the complete value array, as at creation, and updates its own entries.  No communication: the call is not collective
+ *     and may run on the ranks in any order, but EVERY rank must have made it before the next (collective) factorisation.
+ *  6. Ordering: the host-pointer form stages the values through a device buffer the handle keeps (it grows once) and returns when the stream work is queued
+ *     and the staging copy is complete (nzval may be reused at once).  The _dev form only queues work on the handle's stream and reads d_nzval in stream
+ *     order: the caller keeps it alive and unchanged until the next synchronising call on the handle (a factorisation, a solve, a call with out != NULL);
+ *     what produced d_nzval on another stream must be complete before the call.  With out != NULL both forms synchronise once, to return anorm.
+ *  7. Errors, all SLUAMD_EINVAL with a message in sluamd_last_error() and the handle untouched: null handle or null values; a handle not created from the
+ *     symbolic structure (the message names sluamd_dSetValues); a handle of the other precision; the two cases of 3. and 4.
+ * The first update of a handle whose values are scaled also builds, on the device, the (row, column) of every owned entry (8 bytes each) from the attached
+ * structure; it is not built at creation, which every handle pays. */
+typedef struct sluamd_update {
+    double anorm;             /* 1-norm of the matrix the handle now holds (scaled if equilibrated) */
+    int32_t equed;            /* the handle's SLUAMD_EQUED_* (unchanged by the call) */
+    int32_t reserved;
+} sluamd_update_t;
+int sluamd_dUpdateValues(sluamd_handle_t h, const double *nzval, sluamd_update_t *out);                   /* host pointer   */
+int sluamd_dUpdateValues_dev(sluamd_handle_t h, const double *d_nzval, sluamd_update_t *out);             /* device pointer */
+int sluamd_zUpdateValues(sluamd_handle_t h, const sluamd_doublecomplex *nzval, sluamd_update_t *out);
+int sluamd_zUpdateValues_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_nzval, sluamd_update_t *out);
+
 /* ------------------------------------------------------------------------------------------------
  * Process grids: nprow x npcol x npdep ranks, one rank per GPU (gridinfo3d_t, superlu_defs.h:385-420).
  *

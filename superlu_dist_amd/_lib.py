@@ -47,6 +47,11 @@ class Equil(C.Structure):
                 ("anorm", C.c_double)]
 
 
+class Update(C.Structure):
+    """sluamd_update_t"""
+    _fields_ = [("anorm", C.c_double), ("equed", C.c_int32), ("reserved", C.c_int32)]
+
+
 EXPORTS = [
     "sluamd_default_options", "sluamd_dCreateLUHandle", "sluamd_dSetValues", "sluamd_pdgstrf3d",
     "sluamd_dCopyLU2Host", "sluamd_pdgstrs3d", "sluamd_pdgstrs3d_dev", "sluamd_pdgstrs3d_dist", "sluamd_pzgstrs3d_dist", "sluamd_dDestroyLUHandle",
@@ -58,6 +63,7 @@ EXPORTS = [
     "sluamd_pdgstrs3d_trans", "sluamd_pdgstrs3d_trans_dev", "sluamd_pzgstrs3d_trans", "sluamd_pzgstrs3d_trans_dev",
     "sluamd_dEquilibrate", "sluamd_zEquilibrate", "sluamd_GetScalings",
     "sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev",
+    "sluamd_dUpdateValues", "sluamd_dUpdateValues_dev", "sluamd_zUpdateValues", "sluamd_zUpdateValues_dev",
     "sluamd_comm_rccl_unique_id", "sluamd_comm_create_rccl", "sluamd_comm_create_callbacks", "sluamd_comm_create_local",
     "sluamd_comm_selftest", "sluamd_comm_rank", "sluamd_comm_size", "sluamd_comm_destroy", "sluamd_dCreateLUHandleGrid",
     "sluamd_dCreateLUHandleFromSymbGrid", "sluamd_zCreateLUHandleGrid", "sluamd_zCreateLUHandleFromSymbGrid",
@@ -150,6 +156,10 @@ def bind(L):
     for name in ("sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int, P_dbl, P_int]
+    # same-pattern value updates: only in the product library (the CPU test build has no update kernels)
+    for name in ("sluamd_dUpdateValues", "sluamd_dUpdateValues_dev", "sluamd_zUpdateValues", "sluamd_zUpdateValues_dev"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Update)]
     L.sluamd_comm_rccl_unique_id.argtypes = [C.c_void_p]
     L.sluamd_comm_create_rccl.argtypes = [C.POINTER(C.c_void_p), C.c_void_p] + [C.c_int] * 7
     L.sluamd_comm_create_callbacks.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CommCallbacks)] + [C.c_int] * 6

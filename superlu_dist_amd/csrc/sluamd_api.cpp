@@ -512,6 +512,17 @@ int sluamd_pdgstrs3d(sluamd_handle_t h, double *x, int64_t ldx, int32_t nrhs)
 
 // ---- iterative refinement: pdgsrfs3d (SRC/double/pdgsrfs.c:345-510); the driver: sluamd_refine.h ----
 namespace sluamd {
+int reset_store(Handle *H, bool scatter)
+{
+    HIPCHK(hipSetDevice(H->device));
+    H->dinv_ready = false; H->inv_ready = false; H->factored = false;
+    HIPCHK(hipMemsetAsync(H->d_val, 0, (H->z ? 16 : 8) * (size_t) H->own_len, H->stream));
+    if (scatter && H->a_nnz && !H->z) eng::scatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, H->a_nnz);
+    if (scatter && H->a_nnz && H->z) eng::zscatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, H->a_nnz);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 void free_rfs(Handle *H)
 {
     void **ps[] = {(void **) &H->d_rfs_rp, (void **) &H->d_rfs_ci, (void **) &H->d_rfs_pc, (void **) &H->d_rfs_av, (void **) &H->d_rfs_work, (void **) &H->d_rfs_s};
@@ -599,6 +610,9 @@ void sluamd_dDestroyLUHandle(sluamd_handle_t h)
     if (H->d_eq_r) hipFree(H->d_eq_r);
     if (H->d_eq_c) hipFree(H->d_eq_c);
     if (H->d_eq_work) hipFree(H->d_eq_work);
+    if (H->d_upd_stage) hipFree(H->d_upd_stage);
+    if (H->d_upd_ij) hipFree(H->d_upd_ij);
+    if (H->ev_upd) hipEventDestroy(H->ev_upd);
     if (H->h_pinned) hipHostFree(H->h_pinned);
     if (H->d_bloc) hipFree(H->d_bloc);
     for (void *q : H->dist.bufs) hipFree(q);
@@ -728,14 +742,7 @@ int sluamd_zCreateLUHandleFromSymbGrid(sluamd_handle_t *out, sluamd_symb_t s, co
 int sluamd_dResetValues(sluamd_handle_t h)
 {
     if (!h || !h->H.d_apos) { set_error("handle has no device-side copy of A"); return SLUAMD_EINVAL; }
-    Handle *H = &h->H;
-    HIPCHK(hipSetDevice(H->device));
-    H->dinv_ready = false; H->inv_ready = false; H->factored = false;
-    HIPCHK(hipMemsetAsync(H->d_val, 0, (H->z ? 16 : 8) * (size_t) H->own_len, H->stream));
-    if (H->a_nnz && !H->z) eng::scatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, H->a_nnz);
-    if (H->a_nnz && H->z) eng::zscatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, H->a_nnz);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return reset_store(&h->H, true);
 }
 
 int sluamd_device_synchronize(void)

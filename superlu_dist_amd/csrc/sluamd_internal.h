@@ -370,6 +370,10 @@ struct Handle {
     // equilibration (sluamd_[dz]Equilibrate, sluamd_equil.cpp): R and C on the device, what was applied, and the work block of the expert solve
     double *d_eq_r = nullptr, *d_eq_c = nullptr; bool eq_done = false, eq_row = false, eq_col = false;
     double *d_eq_work = nullptr; int64_t eq_work_cap = 0;     // [xp | B | X] of sluamd_p[dz]gssvx3d_solve (doubles)
+    // same-pattern value updates (sluamd_[dz]UpdateValues, sluamd_update.cpp): the staging buffer of the host-pointer form (grows once), the event that marks
+    // its copy complete, and (row, column) in the caller's CSR of every owned entry -- built on the first update of a handle whose values are scaled
+    double *d_upd_stage = nullptr; int64_t upd_stage_cap = 0; hipEvent_t ev_upd = nullptr;
+    int2 *d_upd_ij = nullptr;
     // iterative refinement (sluamd_dAttachMatrix / sluamd_zAttachMatrix): the ORIGINAL matrix in CSR + perm_c, and work vectors
     // (values and vectors in doubles: 2 per value when rfs_z)
     int *d_rfs_rp = nullptr, *d_rfs_ci = nullptr, *d_rfs_pc = nullptr; double *d_rfs_av = nullptr;
@@ -531,7 +535,20 @@ void eq_scale_norm(hipStream_t s, bool z, int n, int64_t nnz, const int *rp, con
 void eq_gather(hipStream_t s, bool z, int64_t cnt, const int *ent, const void *av, void *out);
 // gather = false: dst[perm[i], j] = scale[i] * src[i, j]; true: dst[i, j] = scale[i] * src[perm[i], j]; scale / perm may be null (ones / identity); ld in values
 void eq_permscale(hipStream_t s, bool z, bool gather, int n, int nrhs, const int *perm, const double *scale, const void *src, int64_t lds, void *dst, int64_t ldd);
+// same-pattern value updates (sluamd_ukernels.inc; z: doublecomplex values).  Referenced only by sluamd_update.cpp (the CPU test build of the host sources has
+// no restatement of them).  update_rowcol: ij[e] = (row, column) of CSR entry ent[e].  update_values: v = nz[ent[e]], scaled (v r[i]) c[j] where r / c are given
+// (ij may be null when both are), stored to aval[e] and val[pos[e]].  update_attached: av[e] = (nz[e] r[i]) c[j] over the CSR by rows; colsum (zero-filled, may
+// be null) += the moduli by column
+void update_rowcol(hipStream_t s, int64_t cnt, int n, const int *rp, const int *ci, const int *ent, int2 *ij);
+void update_values(hipStream_t s, bool z, int64_t cnt, const int *ent, const int2 *ij, const void *nz, const double *r, const double *c, void *aval,
+                   const int64_t *pos, void *val);
+void update_attached(hipStream_t s, bool z, int n, int64_t nnz, const int *rp, const int *ci, const void *nz, const double *r, const double *c, void *av,
+                     double *colsum);
 }  // namespace eng
+
+// the flags, the zero-fill of the arena and (scatter) the re-distribution of d_aval that sluamd_dResetValues queues on the handle's stream (sluamd_api.cpp);
+// sluamd_[dz]UpdateValues passes scatter = false and queues its own kernel behind the zero-fill
+int reset_store(Handle *H, bool scatter);
 
 }  // namespace sluamd
 

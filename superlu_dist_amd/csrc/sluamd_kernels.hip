@@ -2884,6 +2884,7 @@ __global__ void k_mfma_selftest(const double *A, const double *B, double *D)
 #include "sluamd_zkernels.inc"
 #include "sluamd_tkernels.inc"   // transposed / conjugate-transposed sweeps (sluamd_tsolve.cpp)
 #include "sluamd_ekernels.inc"   // equilibration, 1-norm, permute-and-scale of right-hand sides (sluamd_equil.cpp)
+#include "sluamd_ukernels.inc"   // same-pattern value updates (sluamd_update.cpp)
 
 // ---- exchange helpers (XY block-cyclic layers, Z ancestor reduction, distributed solve) ---------------------------
 // y += a x : the daxpy of dzRecvLPanel / dzRecvUPanel (pd3dcomm.c:189-331) on a whole forest slice; HBM-bound, 24 B/element

@@ -181,6 +181,8 @@ class LUHandle:
         self.store = store
         self.z = False
         self.n = None if store is None else store.n       # order of the matrix (from_symbolic sets it)
+        self.nnz = None                                   # entries of the CSR the handle was created from (from_symbolic sets it)
+        self.device = -1                                  # HIP device ordinal given at creation (-1: the device that was current)
 
     @staticmethod
     def _opts(replace_tiny=False, deterministic=False, device=-1, info_rule=0):
@@ -217,12 +219,12 @@ class LUHandle:
             _lib.check(L.sluamd_zCreateLUHandleFromSymb(C.byref(h), symb._h, _pi(symb.rowptr), _pi(symb.colind),
                                                         nz.ctypes.data_as(C.c_void_p), _pi(symb.perm_c), C.byref(o)),
                        "sluamd_zCreateLUHandleFromSymb")
-            obj = cls(h, None); obj.z = True; obj.n = symb.n
+            obj = cls(h, None); obj.z = True; obj.n = symb.n; obj.nnz = len(symb.colind); obj.device = int(o.device)
             return obj
         nz = np.ascontiguousarray(nzval, dtype=np.float64)
         _lib.check(L.sluamd_dCreateLUHandleFromSymb(C.byref(h), symb._h, _pi(symb.rowptr), _pi(symb.colind), _pd(nz),
                                                     _pi(symb.perm_c), C.byref(o)), "sluamd_dCreateLUHandleFromSymb")
-        obj = cls(h, None); obj.n = symb.n
+        obj = cls(h, None); obj.n = symb.n; obj.nnz = len(symb.colind); obj.device = int(o.device)
         return obj
 
     def set_values(self, store):
@@ -285,6 +287,15 @@ class LUHandle:
 
     def reset_values(self):
         _lib.check(_lib.load().sluamd_dResetValues(self._h), "sluamd_dResetValues")
+
+    def update_values(self, nzval, want_norm=False):
+        """New values for the SAME CSR the handle was created from (from_symbolic), Fact = SamePattern_SameRowPerm: sluamd_[dz]UpdateValues for a numpy
+        array (or a torch tensor on the CPU), sluamd_[dz]UpdateValues_dev with data_ptr() for a torch tensor on the handle's device -- values assembled
+        on the GPU never visit the host; the tensor must stay alive and unchanged until the next synchronising call on the handle (a factorisation).
+        The handle is then unfactored; an equilibrated handle scales the new values with its R and C; an attached matrix takes them too.
+        Returns None, or dict(anorm, equed) when want_norm (needs an attached matrix).  ValueError, before any library call: wrong dtype, wrong
+        length, non-contiguous data, a tensor on another device."""
+        return _update_values(self._h, self.z, self.nnz, self.device, nzval, want_norm)
 
     def attach_matrix(self, n, rowptr, colind, nzval, perm_c):
         """Device copy of the ORIGINAL matrix (CSR) + perm_c for pdgsrfs3d (sluamd_dAttachMatrix, or sluamd_zAttachMatrix on a complex16 handle)."""
@@ -409,6 +420,44 @@ def _gsrfs3d_dev(h, z, d_b, ldb, d_x, ldx, nrhs):
 
 
 EQUED = "NRCB"      # SLUAMD_EQUED_N / _R / _C / _B
+
+
+def _update_values(h, z, nnz, device, nzval, want_norm):
+    """argument checks (ValueError, before any library call) and the call of LUHandle.update_values / GridHandle.update_values"""
+    want = "complex128" if z else "float64"
+    ptr, dev = None, False
+    if type(nzval).__module__.split(".")[0] == "torch" and hasattr(nzval, "data_ptr"):
+        t = nzval
+        if str(t.dtype) != "torch." + want:
+            raise ValueError(f"update_values: the handle holds {want} values, the tensor is {t.dtype}")
+        if t.dim() != 1 or (nnz is not None and t.numel() != nnz):
+            raise ValueError(f"update_values: {nnz} values expected (the CSR the handle was created from), got a tensor of shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError("update_values: the tensor is not contiguous")
+        if t.device.type == "cpu":
+            nzval = t.numpy()
+        else:
+            if t.device.type != "cuda":
+                raise ValueError(f"update_values: the tensor is on {t.device}, the handle on a HIP device")
+            import torch
+            mine = device if device >= 0 else torch.cuda.current_device()      # device = -1 at creation: the device that is current
+            if t.device.index != mine:
+                raise ValueError(f"update_values: the tensor is on {t.device}, the handle on device {mine}")
+            ptr, dev, keep = t.data_ptr(), True, t
+    if not dev:
+        a = np.asarray(nzval)
+        if a.dtype != np.dtype(want):
+            raise ValueError(f"update_values: the handle holds {want} values, the array is {a.dtype}")
+        if a.ndim != 1 or (nnz is not None and a.shape[0] != nnz):
+            raise ValueError(f"update_values: {nnz} values expected (the CSR the handle was created from), got an array of shape {a.shape}")
+        if not a.flags.c_contiguous:
+            raise ValueError("update_values: the array is not contiguous")
+        ptr, keep = a.ctypes.data, a
+    name = ("sluamd_zUpdateValues" if z else "sluamd_dUpdateValues") + ("_dev" if dev else "")
+    out = _lib.Update() if want_norm else None
+    _lib.check(_lib.entry(name)(h, C.c_void_p(ptr), None if out is None else C.byref(out)), name)
+    del keep
+    return dict(anorm=float(out.anorm), equed=EQUED[out.equed]) if want_norm else None
 
 
 def _equilibrate(h, z, n, rowptr, colind, nzval, perm_c):

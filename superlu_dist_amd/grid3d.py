@@ -125,6 +125,7 @@ class GridHandle:
 
     def __init__(self, h, comm, n, z=False):
         self._h, self.comm, self.n, self.z = h, comm, n, z
+        self.nnz, self.device = None, -1      # from_symbolic sets them: entries of the CSR, device ordinal given at creation
 
     def plan_table(self):
         from .driver import plan_table
@@ -155,12 +156,14 @@ class GridHandle:
             _lib.check(L.sluamd_zCreateLUHandleFromSymbGrid(C.byref(h), symb._h, _pi(symb.rowptr), _pi(symb.colind), nz.ctypes.data_as(C.c_void_p),
                                                             _pi(symb.perm_c), C.byref(o), None if t is None else t.ctypes.data_as(_lib.P_int), comm),
                        "sluamd_zCreateLUHandleFromSymbGrid")
-            return cls(h, comm, symb.n, True)
+            obj = cls(h, comm, symb.n, True); obj.nnz = len(symb.colind); obj.device = int(o.device)
+            return obj
         nz = np.ascontiguousarray(nzval, dtype=np.float64)
         _lib.check(L.sluamd_dCreateLUHandleFromSymbGrid(C.byref(h), symb._h, _pi(symb.rowptr), _pi(symb.colind), _pd(nz), _pi(symb.perm_c),
                                                         C.byref(o), None if t is None else t.ctypes.data_as(_lib.P_int), comm),
                    "sluamd_dCreateLUHandleFromSymbGrid")
-        return cls(h, comm, symb.n)
+        obj = cls(h, comm, symb.n); obj.nnz = len(symb.colind); obj.device = int(o.device)
+        return obj
 
     def pdgstrf3d(self, thresh=0.0):
         info = C.c_int32(0)
@@ -238,6 +241,12 @@ class GridHandle:
 
     def reset_values(self):
         _lib.check(_lib.load().sluamd_dResetValues(self._h), "sluamd_dResetValues")
+
+    def update_values(self, nzval, want_norm=False):
+        """LUHandle.update_values on this rank: the COMPLETE value array of the CSR the handle was created from; the rank updates its own entries.
+        No communication and not collective, but every rank must have made the call before the next (collective) factorisation."""
+        from .driver import _update_values
+        return _update_values(self._h, self.z, self.nnz, self.device, nzval, want_norm)
 
     def set_profile(self, on=True):
         """per-phase HIP-event timing (serial schedule): Schur / panel kernels, XY exchange phases, Z ancestor reduction"""
