@@ -928,8 +928,10 @@ __global__ __launch_bounds__(RSv * 4) void k_panel_trsm(DevTables T, const int *
 // hazard, there is no LDS strip (many waves per SIMD instead of one workgroup per CU) and no barrier.  Operand roles as in
 // k_schur: D = Tinv^T-fragment x strip-fragment, so that the 16 fast lanes of every accumulator register run along panel rows
 // (128-byte runs of an L column / contiguous pieces of a skyline segment).
-constexpr int PGK = 64;                        // K chunk of the inverse staged in LDS
-constexpr int PG_LDS = PGK * 48;               // doubles: [64][48] (c-fastest, MODE 1) or [32][66] (k-fastest, MODE 0)
+constexpr int PGK = 32;                        // K chunk of the inverse staged in LDS: one 32 x 32 block of Tinv, so the chunks of block jb are exactly the non-zero ones
+constexpr int PG_LD0 = PGK + 2, PG_LD1 = 48;   // stage row lengths: [32 n][34] (k-fastest, MODE 0) or [32 k][48] (n-fastest, MODE 1)
+constexpr int PG_BUF = PGK * PG_LD1;           // doubles per stage buffer (the larger of the two forms)
+constexpr int PG_LDS = 2 * PG_BUF;             // two stage buffers: chunk i + 1 is loaded and stored while chunk i is multiplied
 template <int MODE, int NQ>   // NQ = fragment registers per lane = 64 (supernodes up to 256 columns), 32 (<= 128) or 16 (<= 64: the leaf levels,
                               // where the register budget decides how many of the tens of thousands of small panels are in flight)
 __device__ __forceinline__ void panel_gemm_wg(const DevTables &T, int k, int unit64, double *Ts)
@@ -966,37 +968,63 @@ __device__ __forceinline__ void panel_gemm_wg(const DevTables &T, int k, int uni
     }
     // Tinv(kk, n): MODE 0 -> Uinv(kk, n) at Ui[kk + n ns] (kk fastest); MODE 1 -> (Linv^T)(kk, n) = Linv(n, kk) at Li[n + kk ns] (n fastest)
     const double *Ti = T.inv + T.sn_inv[k] + (MODE == 0 ? (size_t) ns * ns : 0);
+    // Stage of chunk (jb, kb) = Tinv(32 kb .. +32, 32 jb .. +32), kb <= jb (Tinv is upper triangular: the blocks below are zero and are never staged or
+    // multiplied).  A thread moves two pairs of the memory-fastest index f (kk in MODE 0, n in MODE 1) at the slow index s: 16 lanes cover one 256-byte run.
+    // Chunks whose 32 columns lie inside ns (all of block jb, or none: kb <= jb) take unpredicated 16-byte loads when the supernode's inverse is 16-byte
+    // aligned in both directions (ns even); the ragged last block, and every block of an odd-width supernode, takes the predicated 8-byte loads.
+    constexpr int LD = MODE == 0 ? PG_LD0 : PG_LD1;
+    const bool wide = ((ns & 1) == 0) && ((reinterpret_cast<size_t>(Ti) & 15) == 0);
+    const int f2 = (tid & 15) * 2, s0 = tid >> 4;
+    auto fetch = [&](double (&r)[4], int jb, int kb) {
+        const int F0 = (MODE == 0 ? kb : jb) * DB + f2, S0 = (MODE == 0 ? jb : kb) * DB + s0;
+        if (wide && jb * DB + DB <= ns) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const double2 v = *reinterpret_cast<const double2 *>(Ti + F0 + (size_t) (S0 + 16 * e) * ns);
+                r[2 * e] = v.x; r[2 * e + 1] = v.y;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int S = S0 + 16 * e;
+                const double *p = Ti + F0 + (size_t) S * ns;
+                r[2 * e] = (F0 < ns && S < ns) ? p[0] : 0.0;
+                r[2 * e + 1] = (F0 + 1 < ns && S < ns) ? p[1] : 0.0;
+            }
+        }
+    };
+    auto stash = [&](const double (&r)[4], int buf) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            *reinterpret_cast<double2 *>(Ts + buf * PG_BUF + (s0 + 16 * e) * LD + f2) = make_double2(r[2 * e], r[2 * e + 1]);
+    };
+    // One flat chunk sequence (0,0) (1,0) (1,1) (2,0) ... for the whole workgroup: the loads of the next chunk are issued before the MFMAs of this one,
+    // stored into the other buffer after them, one barrier per chunk; the pipeline runs across the block boundaries.
+    double r[4];
+    fetch(r, 0, 0);
+    stash(r, 0);
+    __syncthreads();
+    int buf = 0;
     for (int jb = 0; jb < nblk; ++jb) {
         d4 acc0 = (d4){0.0, 0.0, 0.0, 0.0}, acc1 = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int kc = 0; kc < NQ / 16; ++kc) {    // K chunks of 64 strip columns: [0, 32 (jb + 1)) in all (Tinv is upper triangular)
-            if (kc * 2 <= jb) {
-                __syncthreads();                   // the previous chunk's fragment reads are done
-                const int k0 = kc * PGK;
-                if (MODE == 0) {
+        for (int kb = 0; kb < NQ / 8; ++kb) {    // K chunks of 32 strip columns: [0, 32 (jb + 1)) in all
+            if (kb <= jb) {
+                const int njb = kb == jb ? jb + 1 : jb, nkb = kb == jb ? 0 : kb + 1;
+                const bool more = njb < nblk;
+                if (more) fetch(r, njb, nkb);
+                const double *Tc = Ts + buf * PG_BUF;
 #pragma unroll
-                    for (int e = 0; e < PGK * DB / 256; ++e) {
-                        const int idx = tid + 256 * e, kk = idx & (PGK - 1), np = idx >> 6;
-                        const int kg = k0 + kk, n = jb * DB + np;
-                        Ts[np * (PGK + 2) + kk] = (kg < ns && n < ns) ? Ti[kg + (size_t) n * ns] : 0.0;
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < PGK * DB / 256; ++e) {
-                        const int idx = tid + 256 * e, np = idx & 31, kk = idx >> 5;
-                        const int kg = k0 + kk, n = jb * DB + np;
-                        Ts[kk * 48 + np] = (kg < ns && n < ns) ? Ti[n + (size_t) kg * ns] : 0.0;
-                    }
-                }
-                __syncthreads();
-#pragma unroll
-                for (int qq = 0; qq < 16; ++qq) {
+                for (int qq = 0; qq < 8; ++qq) {
                     const int kl = 4 * qq + lk;
-                    const double t0 = MODE == 0 ? Ts[li * (PGK + 2) + kl] : Ts[kl * 48 + li];
-                    const double t1 = MODE == 0 ? Ts[(16 + li) * (PGK + 2) + kl] : Ts[kl * 48 + 16 + li];
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(t0, a[16 * kc + qq], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(t1, a[16 * kc + qq], acc1, 0, 0, 0);
+                    const double t0 = MODE == 0 ? Tc[li * LD + kl] : Tc[kl * LD + li];
+                    const double t1 = MODE == 0 ? Tc[(16 + li) * LD + kl] : Tc[kl * LD + 16 + li];
+                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(t0, a[8 * kb + qq], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(t1, a[8 * kb + qq], acc1, 0, 0, 0);
                 }
+                if (more) stash(r, buf ^ 1);      // its last readers passed the barrier that ended the previous chunk
+                __syncthreads();
+                buf ^= 1;
             }
         }
         // D[(lk + 4 r)][li] = X_new(row li, column jb*32 + 16 h + lk + 4 r)
@@ -1021,7 +1049,7 @@ __global__ __launch_bounds__(256) void k_panel_gemm(DevTables T, const int *__re
                                                     const int *__restrict__ uprefix, int nn, int nl, const int2 *__restrict__ units)
 {
     __builtin_amdgcn_s_setprio(3);   // panel chain: its waves go first when they share a SIMD with Schur tiles
-    __shared__ double Ts[PG_LDS];
+    __shared__ __attribute__((aligned(16))) double Ts[PG_LDS];   // 16-byte stage stores
     if (units) {   // explicit (supernode, 64-row / 64-column unit) list [L units | U units]: one part of a split panel solve
         const int2 u = units[blockIdx.x];
         if ((int) blockIdx.x < nl) panel_gemm_wg<0, NQ>(T, u.x, u.y, Ts);
