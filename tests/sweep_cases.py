@@ -58,7 +58,7 @@ def _absint(M):
     else:
         assert np.all(M.data == np.rint(M.data))
         d = np.abs(M.data).astype(np.int64)
-    return sp.csr_matrix((d, M.indices, M.indptr), shape=M.shape)
+    return sp.csr_matrix((d, M.indices.copy(), M.indptr.copy()), shape=M.shape)                # copies: sorting |M| in place must not permute M's own index array under its data
 
 
 def _rowsum_max(A):
@@ -155,6 +155,7 @@ class SweepCase(sc.Case):
         for prod in ((aB, aUi), (aLi, aB), (aLi, aL, aLi), (aUi, aU, aUi)):
             assert _prod_bound(*prod) < LIMIT, _prod_bound(*prod)
         self.aL, self.aU, self.aLi, self.aUi = aL, aU, aLi, aUi
+        assert (B16 != L4 @ U4).nnz == 0                                                    # nothing above sorted an index array that B16 shares
         self.gL = self.gU = None
         if self.group:                                                                      # |inverse of the group's block triangle|, by its recurrence, int64
             a, e = int(self.xsup[self.group[0]]), int(self.xsup[self.group[0] + self.group[1]])

@@ -8,7 +8,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = ["test_gpu_parity.py", "test_gpu_edge_cases.py", "test_gpu_refine.py", "test_gpu_grid.py", "test_gpu_fuzz.py", "test_gpu_pivots.py",
-         "test_gpu_schur_shapes.py", "test_gpu_sweep_shapes.py", "test_gpu_panel_forms.py"]
+         "test_gpu_schur_shapes.py", "test_gpu_sweep_shapes.py", "test_gpu_panel_forms.py", "test_gpu_refine_exact.py"]
 
 
 def _mpirun(cmd, env, cwd):
