@@ -78,6 +78,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
     // substitutions on the 32 x 32 inverses the diagonal kernel leaves behind (k_panel_trsm), so that the full inverses (which the
     // triangular solves still want) leave the chain: they are computed beside it on the bulk stream
     const int trsm_tail = (gemm_panels && !xy) ? H->env.trsm_tail : 0;
+    eng::trsm_lds_strip = H->env.trsm_lds_strip;   // (thread-local, like panel_site: read by eng::panel_trsm on this thread)
     auto tail_level = [&](int l) { return trsm_tail > 0 && l >= S.nlevels - trsm_tail && S.lvl_off[l + 1] - S.lvl_off[l] == 1; };
     auto deferred_inv = [&](hipStream_t st, int l) {
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];

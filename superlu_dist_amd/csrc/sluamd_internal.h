@@ -304,6 +304,7 @@ struct Handle {
         int fuse_tail_guard = 0;    // SLUAMD_FUSE_TAIL_GUARD: groups of more than two K-fused supernodes (fuse_max_prev > 1) only below the last N levels
         int diag_tail = 64;          // SLUAMD_DIAG_TAIL: last N single-supernode levels factor their diagonal block with the whole-register-file build of k_diag_lu2
         int trsm_tail = 64;          // SLUAMD_TRSM_TAIL: last N single-supernode levels of a 1 x 1 layer solve their panels by blocked substitution, full inverses off the chain
+        bool trsm_lds_strip = false; // SLUAMD_TRSM_LDS_STRIP: the 64-high blocked substitution keeps its strip in LDS (k_panel_trsm<64>: a whole CU's LDS) instead of registers (k_panel_tsub)
         int level_split_min = 2048;  // SLUAMD_LEVEL_SPLIT_MIN: sub-levels never get smaller than this, forests whose largest level has fewer than 4 x this are not cut (tests lower it)
         int level_split_wdiv = 0;    // SLUAMD_LEVEL_SPLIT_WDIV (opt-in, e.g. 128): levels heavier (panel values, upper bound from the block graph) than 1 / this of the forest's total are cut too;
                                      // <= 1: off.  Off by default: cut levels break K-fused pairs (150^3 on 2x2x2 with 128: allocated / values 1.27-1.29 -> 1.17-1.24, tile executions + 20 %)
@@ -433,6 +434,9 @@ int setup();   // one-time function attributes (dynamic LDS limits)
 // wrappers (sluamd_kernels.hip) and only when the variable is set; thread-local: the ranks of a thread grid run their drivers side by side
 struct PanelSite { int level, nn, part, bulk; };
 inline thread_local PanelSite panel_site = {-1, 0, -1, 0};
+// SLUAMD_TRSM_LDS_STRIP of the handle whose driver runs on this thread (Handle::Env::trsm_lds_strip, written by run_factor_sched): panel_trsm with rs = 64
+// launches the kernel that keeps the strip in LDS instead of the one that keeps it in registers.  Same results; the switch exists for comparisons
+inline thread_local bool trsm_lds_strip = false;
 // flags: bit 0 = ReplaceTinyPivot, bit 1 = round-1 right-looking kernel, bit 2 = k_diag_lu2 built for the whole register file (tail levels).  Also leaves the inverted 32 x 32 diagonal sub-blocks of the
 // owned blocks in T.dinv (what diag_inv computes for blocks received from another rank)
 void diag_lu(hipStream_t s, const DevTables &T, const int *nodes, int nn, int max_nsupc, int flags, double thresh, int *info);

@@ -1066,6 +1066,183 @@ __global__ __launch_bounds__(256) void k_panel_gemm(DevTables T, const int *__re
     }
 }
 
+// ---- blocked substitution with the strip in registers (tail levels) ---------------------------------------------------------
+// The computation of panel_trsm_body<0 / 1, 64> -- per block column jb: acc = sum_{t < jb} X_t T(t, jb) (t ascending, k ascending), rhs = X_jb - acc,
+// X_jb = rhs inv(T_jj) with the 32 x 32 inverses of T.dinv, no Linv / Uinv -- in the data layout of panel_gemm_wg: a wave keeps its 16 panel rows (MODE 0) or
+// 16 skyline columns (MODE 1) as MFMA operand fragments a[NQ] for the whole solve, and only the operand chunks -- T(t, jb) out of the diagonal block, then
+// the dinv block -- go through LDS, 32 x 32 at a time through the two stage buffers of PG_LDS (24 KB static: the workgroup starts in the slot ONE retiring
+// Schur workgroup frees, where the 152 KB strip of k_panel_trsm<64> waits for a CU without any).
+// No layout conversion between a result and its re-use as an operand: with D = T^T-fragment x strip-fragment, lane (li, lk) of acc_h[r] holds
+// X(row li, column 32 jb + 16 h + 4 r + lk), and the operand fragment of K step q wants X(row li, column 4 q + lk): the same element for q = 8 jb + 4 h + r.
+// jb is a run-time loop: the fragments of block jb are read and written through compile-time indices under `j == jb` (a dynamic index would send a[] to scratch).
+template <int MODE, int NQ>
+__device__ __forceinline__ void panel_tsub_wg(const DevTables &T, int k, int unit64, double *Ts)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int unit = unit64 * 4 + wave;
+    const int klst = T.xsup[k + 1], ns = klst - T.xsup[k];
+    const int nblk = (ns + DB - 1) / DB;
+    const int li = lane & 15, lk = lane >> 4;
+    double a[NQ];
+    // ---- load the wave's 16 rows: a[q] = X(row li, column 4 q + lk), zero past ns and above a skyline segment ----
+    const int lda = T.sn_nsupr[k];
+    const int ldd = T.sn_dlda[k];
+    double *A = T.val + T.sn_lval[k];
+    double *Uv = T.val + T.sn_uval[k];
+    const double *Dg = T.val + T.sn_dptr[k];
+    const double *dinv = T.dinv + T.sn_dinv[k] + (MODE == 0 ? 0 : (size_t) nblk * DB * DB);
+    int row = 0, cp = 0, ld = ns;
+    bool valid;
+    if (MODE == 0) {
+        row = T.sn_ldiag[k] + unit * 16 + li;
+        valid = row < lda;
+    } else {
+        const int cr = unit * 16 + li;
+        valid = cr < T.sn_ncolu[k];
+        if (valid) { ld = T.ucol_ld[T.sn_ucol[k] + cr]; cp = T.ucol_cp[T.sn_ucol[k] + cr]; }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int c = 4 * q + lk;
+        double v = 0.0;
+        if (q < nblk * 8) {
+            if (MODE == 0) { if (valid && c < ns) v = A[row + (size_t) c * lda]; }
+            else { if (valid && c >= ld && c < ns) v = Uv[cp + (c - ld)]; }
+        }
+        a[q] = v;
+    }
+    // Chunk (jb, t): t < jb -> T(32 t .. +32, 32 jb .. +32), MODE 0: T(kk, c) = U_kk(kk, c) at Dg[kk + c ldd] (kk fastest), MODE 1: T(kk, c) = L_kk(c, kk) at
+    // Dg[c + kk ldd] (c fastest); t == jb -> the inverse D(kk, c) at dblk[c 32 + kk] (kk fastest, identity-padded: never predicated).  Stage forms as in
+    // panel_gemm_wg: [32 c][34] for kk-fastest chunks, [32 kk][48] for c-fastest ones.  A thread moves two pairs of the memory-fastest index f at the slow index
+    // s; 16-byte loads where the whole chunk lies inside ns and the block is 16-byte aligned in both directions, else the predicated 8-byte loads (zero padding).
+    const bool wide = ((ldd & 1) == 0) && ((reinterpret_cast<size_t>(Dg) & 15) == 0);
+    const int f2 = (tid & 15) * 2, s0 = tid >> 4;
+    auto fetch = [&](double (&r)[4], int jb, int t) {
+        if (t < jb) {
+            const int F0 = (MODE == 0 ? t : jb) * DB + f2, S0 = (MODE == 0 ? jb : t) * DB + s0;
+            if (wide && jb * DB + DB <= ns) {
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const double2 v = *reinterpret_cast<const double2 *>(Dg + F0 + (size_t) (S0 + 16 * e) * ldd);
+                    r[2 * e] = v.x; r[2 * e + 1] = v.y;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int S = S0 + 16 * e;
+                    const double *p = Dg + F0 + (size_t) S * ldd;
+                    r[2 * e] = (F0 < ns && S < ns) ? p[0] : 0.0;
+                    r[2 * e + 1] = (F0 + 1 < ns && S < ns) ? p[1] : 0.0;
+                }
+            }
+        } else {
+            const double *dblk = dinv + (size_t) jb * DB * DB;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const double *p = dblk + (s0 + 16 * e) * DB + f2;
+                r[2 * e] = p[0]; r[2 * e + 1] = p[1];
+            }
+        }
+    };
+    auto stash = [&](const double (&r)[4], int jb, int t, int buf) {
+        const int LD = (MODE == 1 && t < jb) ? PG_LD1 : PG_LD0;
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            *reinterpret_cast<double2 *>(Ts + buf * PG_BUF + (s0 + 16 * e) * LD + f2) = make_double2(r[2 * e], r[2 * e + 1]);
+    };
+    // One flat chunk sequence (0,0) | (1,0) (1,1) | (2,0) (2,1) (2,2) | ... for the whole workgroup: the loads of the next chunk are issued before the MFMAs of
+    // this one and stored into the other buffer after them, one barrier per chunk.
+    double r[4];
+    fetch(r, 0, 0);
+    stash(r, 0, 0, 0);
+    __syncthreads();
+    int buf = 0;
+    for (int jb = 0; jb < nblk; ++jb) {
+        d4 acc0 = (d4){0.0, 0.0, 0.0, 0.0}, acc1 = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int t = 0; t < NQ / 8 - 1; ++t) {     // acc += X_t T(t, jb)
+            if (t < jb) {
+                fetch(r, jb, t + 1);               // (jb, jb) is the inverse: there is always a next chunk
+                const double *Tc = Ts + buf * PG_BUF;
+#pragma unroll
+                for (int qq = 0; qq < 8; ++qq) {
+                    const int kl = 4 * qq + lk;
+                    const double t0 = MODE == 0 ? Tc[li * PG_LD0 + kl] : Tc[kl * PG_LD1 + li];
+                    const double t1 = MODE == 0 ? Tc[(16 + li) * PG_LD0 + kl] : Tc[kl * PG_LD1 + 16 + li];
+                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(t0, a[8 * t + qq], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(t1, a[8 * t + qq], acc1, 0, 0, 0);
+                }
+                stash(r, jb, t + 1, buf ^ 1);      // its last readers passed the barrier that ended the previous chunk
+                __syncthreads();
+                buf ^= 1;
+            }
+        }
+        // rhs = X_jb - acc in operand layout (q = 4 h + r), X_jb = rhs inv(T_jj)
+        const bool more = jb + 1 < nblk;
+        if (more) fetch(r, jb + 1, 0);
+        double rhs[8];
+#pragma unroll
+        for (int j = 0; j < NQ / 8; ++j)
+            if (j == jb) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { rhs[i] = a[8 * j + i] - acc0[i]; rhs[4 + i] = a[8 * j + 4 + i] - acc1[i]; }
+            }
+        acc0 = (d4){0.0, 0.0, 0.0, 0.0}; acc1 = (d4){0.0, 0.0, 0.0, 0.0};
+        const double *Tc = Ts + buf * PG_BUF;
+#pragma unroll
+        for (int qq = 0; qq < 8; ++qq) {
+            const int kl = 4 * qq + lk;
+            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(Tc[li * PG_LD0 + kl], rhs[qq], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(Tc[(16 + li) * PG_LD0 + kl], rhs[qq], acc1, 0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < NQ / 8; ++j)
+            if (j == jb) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { a[8 * j + i] = acc0[i]; a[8 * j + 4 + i] = acc1[i]; }
+            }
+        // D[(lk + 4 i)][li] = X_new(row li, column 32 jb + 16 h + lk + 4 i): final, stored under the chunks of the next block
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c0 = jb * DB + lk + 4 * i, c1 = c0 + 16;
+            if (MODE == 0) {
+                if (valid && c0 < ns) A[row + (size_t) c0 * lda] = acc0[i];
+                if (valid && c1 < ns) A[row + (size_t) c1 * lda] = acc1[i];
+            } else {
+                if (valid && c0 >= ld && c0 < ns) Uv[cp + (c0 - ld)] = acc0[i];
+                if (valid && c1 >= ld && c1 < ns) Uv[cp + (c1 - ld)] = acc1[i];
+            }
+        }
+        if (more) stash(r, jb + 1, 0, buf ^ 1);
+        __syncthreads();
+        buf ^= 1;
+    }
+}
+
+// the launch shape of k_panel_gemm / k_panel_trsm<64>: L units (workgroups [0, nl)) and U units ([nl, nl + nu)), explicit list or prefix form.  Two workgroups
+// per CU's worth of registers at the most (256 per wave, VGPR + AGPR): one fits in what a retiring k_schur<128,128,8> workgroup leaves
+template <int NQ>
+__global__ __launch_bounds__(256, 2) void k_panel_tsub(DevTables T, const int *__restrict__ nodes, const int *__restrict__ lprefix,
+                                                       const int *__restrict__ uprefix, int nn, int nl, const int2 *__restrict__ units)
+{
+    __builtin_amdgcn_s_setprio(3);   // panel chain: its waves go first when they share a SIMD with Schur tiles
+    __shared__ __attribute__((aligned(16))) double Ts[PG_LDS];   // 16-byte stage stores
+    if (units) {
+        const int2 u = units[blockIdx.x];
+        if ((int) blockIdx.x < nl) panel_tsub_wg<0, NQ>(T, u.x, u.y, Ts);
+        else panel_tsub_wg<1, NQ>(T, u.x, u.y, Ts);
+        return;
+    }
+    if ((int) blockIdx.x < nl) {
+        const int ni = find_node_wave(lprefix, nn, blockIdx.x);
+        panel_tsub_wg<0, NQ>(T, nodes[ni], blockIdx.x - lprefix[ni], Ts);
+    } else {
+        const int id = blockIdx.x - nl;
+        const int ni = find_node_wave(uprefix, nn, id);
+        panel_tsub_wg<1, NQ>(T, nodes[ni], id - uprefix[ni], Ts);
+    }
+}
+
 // Linv / Uinv of the owned diagonal blocks of a node list: work unit = (supernode, typ, 16-row strip of the identity) = one
 // wave with 56 KB of LDS, so that the workgroups fit beside a resident Schur workgroup (a 64-row strip needs a whole CU and
 // would wait for the Schur kernel to drain)
@@ -3053,8 +3230,15 @@ void panel_trsm(hipStream_t s, const DevTables &T, const int *nodes, const int *
 {
     if (nl + nu <= 0) return;
     const size_t lds = trsm_lds_bytes(rs, (mx + 31) & ~31);
-    if (rs == 32) { panel_line("panel", "trsm32", mx, nl, nu); hipLaunchKernelGGL(k_panel_trsm<32>, dim3(nl + nu), dim3(128), lds, s, T, nodes, lprefix, uprefix, nn, nl, units); }
-    else { panel_line("panel", "trsm64", mx, nl, nu); hipLaunchKernelGGL(k_panel_trsm<64>, dim3(nl + nu), dim3(256), lds, s, T, nodes, lprefix, uprefix, nn, nl, units); }
+    if (rs == 32) { panel_line("panel", "trsm32", mx, nl, nu); hipLaunchKernelGGL(k_panel_trsm<32>, dim3(nl + nu), dim3(128), lds, s, T, nodes, lprefix, uprefix, nn, nl, units); return; }
+    // 64-high units: the strip in registers (k_panel_tsub), or in LDS under SLUAMD_TRSM_LDS_STRIP -- unit for unit the same launch, so the launch line is the same;
+    // which of the two ran is a line of its own
+    panel_line("panel", "trsm64", mx, nl, nu);
+    if (g_factor_debug) fprintf(stderr, "[sluamd trsm64] impl=%s level=%d mx=%d nl=%d nu=%d\n", trsm_lds_strip ? "lds" : "regs", panel_site.level, mx, nl, nu);
+    if (trsm_lds_strip) hipLaunchKernelGGL(k_panel_trsm<64>, dim3(nl + nu), dim3(256), lds, s, T, nodes, lprefix, uprefix, nn, nl, units);
+    else if (mx <= 64) hipLaunchKernelGGL(k_panel_tsub<16>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl, units);
+    else if (mx <= 128) hipLaunchKernelGGL(k_panel_tsub<32>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl, units);
+    else hipLaunchKernelGGL(k_panel_tsub<64>, dim3(nl + nu), dim3(256), 0, s, T, nodes, lprefix, uprefix, nn, nl, units);
 }
 
 #define SCHUR_LAUNCH(TM, TN, NWV, ZV, THREADS) \
