@@ -307,6 +307,30 @@ int sluamd_pzgsrfs3d(sluamd_handle_t h, const sluamd_doublecomplex *B, int64_t l
                      int32_t nrhs, double *berr, int32_t *steps);
 int sluamd_pzgsrfs3d_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
                          int64_t ldx, int32_t nrhs, double *berr, int32_t *steps);
+/* Refinement of the transposed and conjugate-transposed systems (xGERFS with trans): op(A) x = b for the ATTACHED matrix, op(A) = A^T
+ * (SLUAMD_TRANS) or A^H (SLUAMD_CONJ; the same as SLUAMD_TRANS on a double handle), with the contract of sluamd_p[dz]gsrfs3d[_dev]:
+ * B, X in the original ordering, X holds the initial solution (e.g. of sluamd_p[dz]gstrs3d_trans on Pc b) and is refined in place,
+ * berr[j] = max_i |r_i| / (|op(A)| |x| + |b|)_i with the SAFE1 / SAFE2 guards (complex16: abs1), the same stopping rule, the same limit
+ * of 20 steps, *steps = those of the last right-hand side.  The correction of a step is the transposed solve with the resident factors:
+ * with the factors of Pc A Pc^T, A^T d = r is (Pc A Pc^T)^T (Pc d) = Pc r, the same permutation on both sides.  The residual reads the
+ * attached values through a transposed index of the CSR pattern (column pointers, rows, positions -- no second copy of the values, so
+ * sluamd_[dz]UpdateValues and sluamd_[dz]Equilibrate need nothing new), built on the host at the first transposed call after a matrix
+ * was attached (its time appears in sluamd_setup_times as refine.transposed_index) and dropped with that matrix.
+ * SLUAMD_NOTRANS calls sluamd_p[dz]gsrfs3d[_dev] and nothing else.  nrhs == 0 returns 0 with *steps = 0.
+ * Errors, all SLUAMD_EINVAL with a message: trans outside {0, 1, 2}; a handle of the other precision; no attached matrix, or one of the
+ * other precision; SLUAMD_TRANS / SLUAMD_CONJ on a grid handle of more than one rank (transposed refinement needs a 1 x 1 x 1 handle, as
+ * the transposed solves do).
+ * After sluamd_[dz]Equilibrate the attached matrix is the scaled one, A' = R A C, and these calls refine op(A') x' = b': for
+ * op(A) x = b pass b' = C o b and the scaled solution x' (op(A') x' = b' with x = R o x'), then unscale x = R o x' -- the roles of R and C
+ * swapped against the untransposed system, see sluamd_p[dz]gssvx3d_solve. */
+int sluamd_pdgsrfs3d_trans(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs,
+                           double *berr, int32_t *steps);
+int sluamd_pdgsrfs3d_trans_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs,
+                               double *berr, int32_t *steps);
+int sluamd_pzgsrfs3d_trans(sluamd_handle_t h, int trans, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X,
+                           int64_t ldx, int32_t nrhs, double *berr, int32_t *steps);
+int sluamd_pzgsrfs3d_trans_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
+                               int64_t ldx, int32_t nrhs, double *berr, int32_t *steps);
 
 /* ---- Equil = YES: row / column equilibration on the device and the solve phase of the expert driver in the caller's ordering and
  * scaling (pdgsequ + pdlaqgs at the head of pdgssvx3d, SRC/double/pdgssvx3d.c:673-729; B scaled by R before the solve, :1450-1465;
@@ -354,8 +378,9 @@ int sluamd_GetScalings(sluamd_handle_t h, double *r, double *c);
  * refine != 0: the refinement loop of sluamd_p[dz]gsrfs3d runs on the scaled system between solve and unscaling, as in the reference
  * (this path makes five passes over the n x nrhs block instead of two: X' gathered unscaled, B' = s_in o B formed in the work block for
  * the residuals, X unscaled in place at the end; each entry point also synchronises its stream once beside the waits of the wrapped calls);
- * berr[nrhs] and *steps as there (both may be NULL when refine == 0).  refine with SLUAMD_TRANS / SLUAMD_CONJ: SLUAMD_EINVAL (no transposed
- * SpMV).  Grid handles: the replicated form (complete B in, complete X out, collective); SLUAMD_TRANS / SLUAMD_CONJ there:
+ * berr[nrhs] and *steps as there (both may be NULL when refine == 0).  refine with SLUAMD_TRANS / SLUAMD_CONJ: SLUAMD_EINVAL here -- solve
+ * with refine == 0, then refine the scaled system with sluamd_p[dz]gsrfs3d_trans[_dev] (b' = C o b, x' = x / R; the recipe is at their
+ * declaration).  Grid handles: the replicated form (complete B in, complete X out, collective); SLUAMD_TRANS / SLUAMD_CONJ there:
  * SLUAMD_EINVAL, as for sluamd_p[dz]gstrs3d_trans.  nrhs == 0 returns 0. */
 int sluamd_pdgssvx3d_solve(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs,
                            int refine, double *berr, int32_t *steps);

@@ -525,7 +525,8 @@ int reset_store(Handle *H, bool scatter)
 
 void free_rfs(Handle *H)
 {
-    void **ps[] = {(void **) &H->d_rfs_rp, (void **) &H->d_rfs_ci, (void **) &H->d_rfs_pc, (void **) &H->d_rfs_av, (void **) &H->d_rfs_work, (void **) &H->d_rfs_s};
+    void **ps[] = {(void **) &H->d_rfs_rp, (void **) &H->d_rfs_ci, (void **) &H->d_rfs_pc, (void **) &H->d_rfs_av, (void **) &H->d_rfs_work, (void **) &H->d_rfs_s,
+                   (void **) &H->d_rfs_tcp, (void **) &H->d_rfs_tri, (void **) &H->d_rfs_tpos};      // (the transposed index belongs to the pattern that goes)
     for (void **p : ps) { if (*p) hipFree(*p); *p = nullptr; }
     H->rfs_nnz = 0;
     H->rfs_z = false;
@@ -573,6 +574,7 @@ struct DRfs {   // the double kernels of the refinement driver (sluamd_refine.h)
         eng::rfs_residual(s, (int) H->hs.n, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, x, b, H->d_rfs_pc, r_perm, H->d_rfs_s, safe1, safe2);
     }
     static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x) { eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc, dx_perm, x); }
+    static int solve(Handle *H, double *r_perm, int n) { return run_solve_dev(H, r_perm, n, 1); }
 };
 }  // namespace
 

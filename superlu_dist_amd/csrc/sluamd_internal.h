@@ -380,6 +380,9 @@ struct Handle {
     int *d_rfs_rp = nullptr, *d_rfs_ci = nullptr, *d_rfs_pc = nullptr; double *d_rfs_av = nullptr;
     double *d_rfs_work = nullptr; unsigned long long *d_rfs_s = nullptr; int64_t rfs_nnz = 0;
     bool rfs_z = false;                                     // the attached matrix is complex16
+    // transposed index of the attached matrix (sluamd_trefine.cpp), built on the first transposed refinement: column pointers, and per entry in
+    // column order (rows ascending inside a column) its row and its position in d_rfs_av.  No values: the kernels read d_rfs_av[d_rfs_tpos[e]]
+    int *d_rfs_tcp = nullptr, *d_rfs_tri = nullptr, *d_rfs_tpos = nullptr;
     void *h_pinned = nullptr; size_t pinned_bytes = 0;      // bounded pinned staging buffer (value upload / download)
     bool z = false;                                         // complex16 (doublecomplex) values: 16-byte elements
     bool dinv_ready = false;                                // T.dinv holds the inverses for the current factors
@@ -528,6 +531,13 @@ void bwd_update_t(hipStream_t s, const DevTables &T, const int *nodes, const int
 void zsolve_diag_t(hipStream_t s, bool upper, bool conj, const DevTables &T, const int *nodes, int nn, void *x, int64_t ldx, int nrhs, int max_nsupc);
 void zfwd_update_t(hipStream_t s, bool conj, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, int64_t ldx, int nrhs, int max_nsupc);
 void zbwd_update_t(hipStream_t s, bool conj, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, int64_t ldx, int nrhs);
+// residual + backward error of the transposed (conj: conjugate-transposed) refinement over the transposed index of the attached matrix (sluamd_rkernels.inc):
+// r_perm[pc[j]] = b_j - sum over column j of op(av[tpos[e]]) x[tri[e]].  Referenced only by sluamd_trefine.cpp (the CPU test build of the host sources has no
+// restatement of them).  The updates are rfs_update / zrfs_update
+void rfs_residual_t(hipStream_t s, int n, const int *tcp, const int *tri, const int *tpos, const double *av, const double *x, const double *b, const int *pc,
+                    double *r_perm, unsigned long long *s_out, double safe1, double safe2);
+void zrfs_residual_t(hipStream_t s, bool conj, int n, const int *tcp, const int *tri, const int *tpos, const void *av, const void *x, const void *b, const int *pc,
+                     void *r_perm, unsigned long long *s_out, double safe1, double safe2);
 // equilibration on the attached CSR copy of A (sluamd_ekernels.inc; z: doublecomplex values).  Referenced only by sluamd_equil.cpp (the CPU test build of the
 // host sources has no restatement of them).  red: three 64-bit words {min bits, max bits, first index whose value is exactly 0}, set to {~0, 0, ~0} before
 // eq_rowmax / eq_reduce; eq_colmax needs c zero-filled, eq_scale_norm colsum zero-filled; mode bit 0: scale by r[i], bit 1: by c[j] (in that order)

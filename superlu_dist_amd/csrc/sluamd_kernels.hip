@@ -3090,6 +3090,7 @@ __global__ void k_mfma_selftest(const double *A, const double *B, double *D)
 #include "sluamd_tkernels.inc"   // transposed / conjugate-transposed sweeps (sluamd_tsolve.cpp)
 #include "sluamd_ekernels.inc"   // equilibration, 1-norm, permute-and-scale of right-hand sides (sluamd_equil.cpp)
 #include "sluamd_ukernels.inc"   // same-pattern value updates (sluamd_update.cpp)
+#include "sluamd_rkernels.inc"   // residual / backward error of the transposed refinement (sluamd_trefine.cpp)
 
 // ---- exchange helpers (XY block-cyclic layers, Z ancestor reduction, distributed solve) ---------------------------
 // y += a x : the daxpy of dzRecvLPanel / dzRecvUPanel (pd3dcomm.c:189-331) on a whole forest slice; HBM-bound, 24 B/element
@@ -3716,6 +3717,22 @@ void zrfs_residual(hipStream_t s, int n, const int *rp, const int *ci, const voi
 void zrfs_update(hipStream_t s, int n, const int *pc, const void *dx_perm, void *x)
 {
     if (n > 0) hipLaunchKernelGGL(k_zrfs_update, dim3((n + 255) / 256), dim3(256), 0, s, n, pc, reinterpret_cast<const zc *>(dx_perm), reinterpret_cast<zc *>(x));
+}
+void rfs_residual_t(hipStream_t s, int n, const int *tcp, const int *tri, const int *tpos, const double *av, const double *x, const double *b, const int *pc,
+                    double *r_perm, unsigned long long *s_out, double safe1, double safe2)
+{
+    if (n > 0) hipLaunchKernelGGL(k_rfs_residual_t, dim3((n + 255) / 256), dim3(256), 0, s, n, tcp, tri, tpos, av, x, b, pc, r_perm, s_out, safe1, safe2);
+}
+void zrfs_residual_t(hipStream_t s, bool conj, int n, const int *tcp, const int *tri, const int *tpos, const void *av, const void *x, const void *b, const int *pc,
+                     void *r_perm, unsigned long long *s_out, double safe1, double safe2)
+{
+    if (n <= 0) return;
+    if (conj)
+        hipLaunchKernelGGL(kz_rfs_residual_t<true>, dim3((n + 255) / 256), dim3(256), 0, s, n, tcp, tri, tpos, reinterpret_cast<const zc *>(av),
+                           reinterpret_cast<const zc *>(x), reinterpret_cast<const zc *>(b), pc, reinterpret_cast<zc *>(r_perm), s_out, safe1, safe2);
+    else
+        hipLaunchKernelGGL(kz_rfs_residual_t<false>, dim3((n + 255) / 256), dim3(256), 0, s, n, tcp, tri, tpos, reinterpret_cast<const zc *>(av),
+                           reinterpret_cast<const zc *>(x), reinterpret_cast<const zc *>(b), pc, reinterpret_cast<zc *>(r_perm), s_out, safe1, safe2);
 }
 
 }  // namespace eng

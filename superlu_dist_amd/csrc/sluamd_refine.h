@@ -6,8 +6,12 @@
 //   K::attach, K::other  names for the error messages: this precision's attach call, the other precision's refinement call
 //   K::residual(s, H, x, b, r_perm, safe1, safe2)   r_perm = Pc (b - A x), *H->d_rfs_s = max(*H->d_rfs_s, berr bits)
 //   K::update(s, H, dx_perm, x)                     x += Pc^T dx_perm
-// sluamd_api.cpp instantiates it for double (eng::rfs_*), sluamd_zrefine.cpp for complex16 (eng::zrfs_*).  Keep the complex
-// instantiation out of sluamd_api.cpp: the CPU test build links the host sources without the complex kernels.
+//   K::solve(H, r_perm, n)                          the correction, in place in r_perm: run_solve_dev for A x = b; the transposed policies run the
+//                                                   transposed sweeps (A^T d = r is A1^T (Pc d) = Pc r for the factors of A1 = Pc A Pc^T: the same
+//                                                   permutation on both sides, so r_perm and K::update are used exactly alike)
+// sluamd_api.cpp instantiates it for double (eng::rfs_*), sluamd_zrefine.cpp for complex16 (eng::zrfs_*), sluamd_trefine.cpp for the transposed and
+// conjugate-transposed systems of both (eng::rfs_residual_t / eng::zrfs_residual_t).  Keep those instantiations out of sluamd_api.cpp: the CPU test build
+// links the host sources without the complex and the transposed kernels.
 #pragma once
 #include "sluamd_comm.h"
 #include "sluamd_plan.h"
@@ -62,7 +66,7 @@ template <class K> int rfs_dev(sluamd_handle_t h, const double *d_B, int64_t ldb
             // ranks can never split into unmatched solves
             if (grid) { if (int rc = H->comm->allreduce_min(&go, 1, s)) return rc; }
             if (!go) break;
-            if (int rc = run_solve_dev(H, r_perm, n, 1)) return rc;
+            if (int rc = K::solve(H, r_perm, n)) return rc;
             K::update(s, H, r_perm, Xc);
             lstres = sv;
             ++count;

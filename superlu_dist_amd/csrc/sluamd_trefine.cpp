@@ -1,0 +1,140 @@
+// sluamd_trefine.cpp -- iterative refinement of the TRANSPOSED and CONJUGATE-TRANSPOSED systems A^T x = b / A^H x = b of the attached matrix
+// (xGERFS with trans; the reference's pdgsrfs3d / pzgsrfs3d know A x = b only): sluamd_p[dz]gsrfs3d_trans[_dev].  The driver is sluamd_refine.h's, with
+//   residual   eng::rfs_residual_t / eng::zrfs_residual_t over the transposed index of the attached CSR matrix (below),
+//   solve      the transposed sweeps of sluamd_tsolve.cpp on r_perm: with the factors of A1 = Pc A Pc^T, A^T d = r is A1^T (Pc d) = Pc r -- the same
+//              permutation on both sides, so r_perm and the update kernels are used exactly as in the untransposed loop,
+//   update     eng::rfs_update / eng::zrfs_update, unchanged.
+// A file of its own: the CPU test build (oracle/Makefile) links a fixed list of the host sources against a CPU restatement of the untransposed double
+// kernels only, so no file of that list may reference the transposed kernels or sweeps.
+//
+// The transposed index (Handle::d_rfs_tcp / d_rfs_tri / d_rfs_tpos).  Column pointers, and per entry in column order its row and its POSITION in the CSR
+// value array -- no second copy of the values: sluamd_[dz]UpdateValues and sluamd_[dz]Equilibrate rewrite / scale d_rfs_av in place and nothing can go
+// stale.  Built on the first transposed refinement of a handle (a handle that never asks pays nothing) and on the HOST: the pattern is copied back and
+// sorted by column with one stable counting sort, O(nnz), rows ascending inside a column, so every sum has a fixed order.  A device build would need a
+// stable segmented sort to save tens of milliseconds once per attached matrix.  free_rfs drops it with the pattern it indexes (re-attaching, equilibrating).
+#include <vector>
+#include "sluamd_refine.h"
+
+using namespace sluamd;
+
+namespace {
+
+bool malloc_retry(Handle *H, void **q, size_t bytes)      // (once more after the arena pool gave its unused chunks back to the driver)
+{
+    if (hipMalloc(q, bytes) == hipSuccess) return true;
+    (void) hipGetLastError();
+    devpool_trim(H->device);
+    return hipMalloc(q, bytes) == hipSuccess;
+}
+
+int ensure_tindex(Handle *H, const char *who)
+{
+    if (H->d_rfs_tcp) return 0;
+    HIPCHK(hipSetDevice(H->device));
+    H->setup.start();
+    const int64_t n = H->hs.n, nnz = H->rfs_nnz;
+    std::vector<int> rp((size_t) n + 1), ci((size_t) std::max<int64_t>(nnz, 1));
+    HIPCHK(hipMemcpy(rp.data(), H->d_rfs_rp, sizeof(int) * (n + 1), hipMemcpyDeviceToHost));
+    if (nnz) HIPCHK(hipMemcpy(ci.data(), H->d_rfs_ci, sizeof(int) * nnz, hipMemcpyDeviceToHost));
+    // stable counting sort by column: the rows are visited in ascending order, so they ascend inside every column
+    std::vector<int> tcp((size_t) n + 1, 0), tri((size_t) std::max<int64_t>(nnz, 1)), tpos((size_t) std::max<int64_t>(nnz, 1));
+    for (int64_t e = 0; e < nnz; ++e) {
+        if (ci[e] < 0 || ci[e] >= n) { set_error(std::string(who) + ": the attached matrix has a column index outside [0, n)"); return SLUAMD_EINVAL; }
+        ++tcp[ci[e] + 1];
+    }
+    for (int64_t j = 0; j < n; ++j) tcp[j + 1] += tcp[j];
+    {
+        std::vector<int> next(tcp.begin(), tcp.end() - 1);
+        for (int64_t i = 0; i < n; ++i) {
+            if (rp[i] < 0 || rp[i + 1] < rp[i] || rp[i + 1] > nnz) { set_error(std::string(who) + ": the attached matrix has row pointers that do not ascend to nnz"); return SLUAMD_EINVAL; }
+            for (int e = rp[i]; e < rp[i + 1]; ++e) { const int p = next[ci[e]]++; tri[p] = (int) i; tpos[p] = e; }
+        }
+    }
+    int *d[3] = {nullptr, nullptr, nullptr};
+    const size_t bytes[3] = {sizeof(int) * ((size_t) n + 1), sizeof(int) * tri.size(), sizeof(int) * tpos.size()};
+    const int *src[3] = {tcp.data(), tri.data(), tpos.data()};
+    for (int k = 0; k < 3; ++k)
+        if (!malloc_retry(H, (void **) &d[k], bytes[k]) || hipMemcpy(d[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess) {
+            (void) hipGetLastError();
+            for (int q = 0; q <= k; ++q) if (d[q]) hipFree(d[q]);
+            set_error(std::string(who) + ": the transposed index of the attached matrix could not be allocated / uploaded");
+            return SLUAMD_ENOMEM;
+        }
+    H->d_rfs_tcp = d[0]; H->d_rfs_tri = d[1]; H->d_rfs_tpos = d[2];
+    H->setup.lap("refine.transposed_index");
+    return 0;
+}
+
+template <bool Z, bool CONJ> struct TRfs {
+    static constexpr bool z = Z;
+    static constexpr const char *attach = Z ? "sluamd_zAttachMatrix" : "sluamd_dAttachMatrix", *other = Z ? "sluamd_pdgsrfs3d_trans" : "sluamd_pzgsrfs3d_trans";
+    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
+    {
+        if (Z) eng::zrfs_residual_t(s, CONJ, (int) H->hs.n, H->d_rfs_tcp, H->d_rfs_tri, H->d_rfs_tpos, H->d_rfs_av, x, b, H->d_rfs_pc, r_perm, H->d_rfs_s, safe1, safe2);
+        else eng::rfs_residual_t(s, (int) H->hs.n, H->d_rfs_tcp, H->d_rfs_tri, H->d_rfs_tpos, H->d_rfs_av, x, b, H->d_rfs_pc, r_perm, H->d_rfs_s, safe1, safe2);
+    }
+    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x)
+    {
+        if (Z) eng::zrfs_update(s, (int) H->hs.n, H->d_rfs_pc, dx_perm, x);
+        else eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc, dx_perm, x);
+    }
+    static int solve(Handle *H, double *r_perm, int n) { return run_tsolve(H, Z && CONJ, r_perm, n, 1); }
+};
+
+// trans != SLUAMD_NOTRANS.  The checks in the order of the transposed solves, then the index, then the shared driver
+template <bool Z> int trefine(sluamd_handle_t h, int trans, bool dev, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps,
+                              const char *name)
+{
+    Handle *H = &h->H;
+    if (int rc = rfs_checks<TRfs<Z, false>>(H)) return rc;
+    if (H->grid.size() > 1) { set_error(std::string(name) + ": transposed refinement needs a 1 x 1 x 1 handle (the transposed sweeps of a grid need exchange plans of their own)"); return SLUAMD_EINVAL; }
+    if (nrhs == 0) { if (steps) *steps = 0; return 0; }
+    if (int rc = ensure_tindex(H, name)) return rc;
+    if (Z && trans == SLUAMD_CONJ) return dev ? rfs_dev<TRfs<Z, true>>(h, B, ldb, X, ldx, nrhs, berr, steps) : rfs_host<TRfs<Z, true>>(h, B, ldb, X, ldx, nrhs, berr, steps);
+    return dev ? rfs_dev<TRfs<Z, false>>(h, B, ldb, X, ldx, nrhs, berr, steps) : rfs_host<TRfs<Z, false>>(h, B, ldb, X, ldx, nrhs, berr, steps);
+}
+
+// 0: go on; the arguments every entry point checks before it looks at the matrix
+int check_args(sluamd_handle_t h, int trans, const void *B, int64_t ldb, const void *X, int64_t ldx, int32_t nrhs, const double *berr, bool z, const char *name)
+{
+    if (!h || !B || !X || !berr || nrhs < 0 || ldb < h->H.hs.n || ldx < h->H.hs.n) { set_error(std::string(name) + ": bad refinement arguments"); return SLUAMD_EINVAL; }
+    if (trans != SLUAMD_NOTRANS && trans != SLUAMD_TRANS && trans != SLUAMD_CONJ) { set_error(std::string(name) + ": trans must be SLUAMD_NOTRANS, SLUAMD_TRANS or SLUAMD_CONJ"); return SLUAMD_EINVAL; }
+    if (h->H.z != z) { set_error(std::string(name) + (z ? ": double handle: call sluamd_pdgsrfs3d_trans" : ": complex16 handle: call sluamd_pzgsrfs3d_trans")); return SLUAMD_EINVAL; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sluamd_pdgsrfs3d_trans(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
+{
+    if (int rc = check_args(h, trans, B, ldb, X, ldx, nrhs, berr, false, "sluamd_pdgsrfs3d_trans")) return rc;
+    if (trans == SLUAMD_NOTRANS) return sluamd_pdgsrfs3d(h, B, ldb, X, ldx, nrhs, berr, steps);
+    return trefine<false>(h, trans, false, B, ldb, X, ldx, nrhs, berr, steps, "sluamd_pdgsrfs3d_trans");
+}
+
+int sluamd_pdgsrfs3d_trans_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
+{
+    if (int rc = check_args(h, trans, d_B, ldb, d_X, ldx, nrhs, berr, false, "sluamd_pdgsrfs3d_trans_dev")) return rc;
+    if (trans == SLUAMD_NOTRANS) return sluamd_pdgsrfs3d_dev(h, d_B, ldb, d_X, ldx, nrhs, berr, steps);
+    return trefine<false>(h, trans, true, d_B, ldb, d_X, ldx, nrhs, berr, steps, "sluamd_pdgsrfs3d_trans_dev");
+}
+
+int sluamd_pzgsrfs3d_trans(sluamd_handle_t h, int trans, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X, int64_t ldx, int32_t nrhs, double *berr,
+                           int32_t *steps)
+{
+    if (int rc = check_args(h, trans, B, ldb, X, ldx, nrhs, berr, true, "sluamd_pzgsrfs3d_trans")) return rc;
+    if (trans == SLUAMD_NOTRANS) return sluamd_pzgsrfs3d(h, B, ldb, X, ldx, nrhs, berr, steps);
+    return trefine<true>(h, trans, false, reinterpret_cast<const double *>(B), ldb, reinterpret_cast<double *>(X), ldx, nrhs, berr, steps, "sluamd_pzgsrfs3d_trans");
+}
+
+int sluamd_pzgsrfs3d_trans_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X, int64_t ldx, int32_t nrhs,
+                               double *berr, int32_t *steps)
+{
+    if (int rc = check_args(h, trans, d_B, ldb, d_X, ldx, nrhs, berr, true, "sluamd_pzgsrfs3d_trans_dev")) return rc;
+    if (trans == SLUAMD_NOTRANS) return sluamd_pzgsrfs3d_dev(h, d_B, ldb, d_X, ldx, nrhs, berr, steps);
+    return trefine<true>(h, trans, true, reinterpret_cast<const double *>(d_B), ldb, reinterpret_cast<double *>(d_X), ldx, nrhs, berr, steps, "sluamd_pzgsrfs3d_trans_dev");
+}
+
+}  // extern "C"

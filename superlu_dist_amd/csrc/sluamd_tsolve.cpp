@@ -14,9 +14,8 @@
 
 using namespace sluamd;
 
-namespace {
-
-int run_tsolve(Handle *H, bool conj, double *d_x, int64_t ldx, int nrhs)
+// (also the correction step of the transposed refinement: sluamd_trefine.cpp)
+int sluamd::run_tsolve(Handle *H, bool conj, double *d_x, int64_t ldx, int nrhs)
 {
     int rc = eng::tsolve_setup();
     if (!rc && !H->z) rc = ensure_inv(H);
@@ -59,6 +58,8 @@ int run_tsolve(Handle *H, bool conj, double *d_x, int64_t ldx, int nrhs)
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+namespace {
 
 // the checks every entry point shares; 1: nothing to do (nrhs == 0)
 int check_args(sluamd_handle_t h, int trans, const void *x, int64_t ldx, int32_t nrhs, bool z, const char *name)

@@ -301,16 +301,19 @@ class LUHandle:
         """Device copy of the ORIGINAL matrix (CSR) + perm_c for pdgsrfs3d (sluamd_dAttachMatrix, or sluamd_zAttachMatrix on a complex16 handle)."""
         _attach_matrix(self._h, self.z, n, rowptr, colind, nzval, perm_c)
 
-    def pdgsrfs3d(self, b, x):
+    def pdgsrfs3d(self, b, x, trans="N"):
         """Iterative refinement of x (original ordering) for the attached matrix; returns (x, berr[nrhs], steps).
-        pzgsrfs3d on a complex16 handle (complex b and x)."""
-        return _gsrfs3d(self._h, self.z, b, x)
+        pzgsrfs3d on a complex16 handle (complex b and x).  trans = "T" / "C": the transposed / conjugate-transposed system A^T x = b, A^H x = b of
+        the attached matrix (sluamd_p[dz]gsrfs3d_trans; 1 x 1 x 1 handles), x e.g. from pdgstrs3d(trans=...).  ValueError, before any library call:
+        a trans other than "N", "T", "C"; b or x of another dtype than the handle's; shapes that differ or are not (n,) / (n, nrhs)."""
+        return _gsrfs3d(self._h, self.z, b, x, trans, self.n)
 
     pzgsrfs3d = pdgsrfs3d
 
-    def pdgsrfs3d_dev(self, d_b, ldb, d_x, ldx, nrhs):
-        """sluamd_p[dz]gsrfs3d_dev: b, x device pointers (column-major, ld in values); x refined in place.  Returns (berr[nrhs], steps)."""
-        return _gsrfs3d_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs)
+    def pdgsrfs3d_dev(self, d_b, ldb, d_x, ldx, nrhs, trans="N"):
+        """sluamd_p[dz]gsrfs3d_dev: b, x device pointers (column-major, ld in values); x refined in place.  Returns (berr[nrhs], steps).
+        trans = "T" / "C": sluamd_p[dz]gsrfs3d_trans_dev."""
+        return _gsrfs3d_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans)
 
     pzgsrfs3d_dev = pdgsrfs3d_dev
 
@@ -400,20 +403,37 @@ def _attach_matrix(h, z, n, rowptr, colind, nzval, perm_c):
         _lib.check(_lib.load().sluamd_dAttachMatrix(h, int(n), _pi(rp), _pi(ci), _pd(v), _pi(pc)), "sluamd_dAttachMatrix")
 
 
-def _gsrfs3d(h, z, b, x):
+def _gsrfs3d(h, z, b, x, trans="N", n=None):
+    t = _trans_code(trans)
     dt = np.complex128 if z else np.float64
+    if t:                                                   # the transposed forms refuse what the untransposed call converts (ValueError, before any library call)
+        for what, a in (("b", b), ("x", x)):
+            if np.asarray(a).dtype != np.dtype(dt):
+                raise ValueError(f"pdgsrfs3d(trans={trans!r}): the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
+        if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
+            raise ValueError(f"pdgsrfs3d(trans={trans!r}): b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
     b = np.asfortranarray(np.array(b, dtype=dt)); x = np.asfortranarray(np.array(x, dtype=dt))
     if b.ndim == 1:
         b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
     berr = np.zeros(b.shape[1]); steps = C.c_int32(0)
+    if t:
+        name = "sluamd_pzgsrfs3d_trans" if z else "sluamd_pdgsrfs3d_trans"
+        _lib.check(_lib.entry(name)(h, t, b.ctypes.data_as(C.c_void_p), b.shape[0], x.ctypes.data_as(C.c_void_p), x.shape[0], b.shape[1], _pd(berr),
+                                    C.byref(steps)), name)
+        return x, berr, steps.value
     name = "sluamd_pzgsrfs3d" if z else "sluamd_pdgsrfs3d"
     _lib.check(_lib.entry(name)(h, b.ctypes.data_as(C.c_void_p) if z else _pd(b), b.shape[0], x.ctypes.data_as(C.c_void_p) if z else _pd(x),
                                 x.shape[0], b.shape[1], _pd(berr), C.byref(steps)), name)
     return x, berr, steps.value
 
 
-def _gsrfs3d_dev(h, z, d_b, ldb, d_x, ldx, nrhs):
+def _gsrfs3d_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans="N"):
+    t = _trans_code(trans)
     berr = np.zeros(max(int(nrhs), 1)); steps = C.c_int32(0)
+    if t:
+        name = "sluamd_pzgsrfs3d_trans_dev" if z else "sluamd_pdgsrfs3d_trans_dev"
+        _lib.check(_lib.entry(name)(h, t, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), _pd(berr), C.byref(steps)), name)
+        return berr[:int(nrhs)], steps.value
     name = "sluamd_pzgsrfs3d_dev" if z else "sluamd_pdgsrfs3d_dev"
     _lib.check(_lib.entry(name)(h, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), _pd(berr), C.byref(steps)), name)
     return berr[:int(nrhs)], steps.value
@@ -532,7 +552,8 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
     LUHandle.gssvx_solve in the caller's ordering and scaling; `equed`, `rowcnd`, `colcnd`, `amax` and a positive `equil_info` go into the
     stats; `anorm` is not used then.  Returns (x, info, stats[, handle, symb])."""
     if refine and _trans_code(trans):
-        raise ValueError("refine=True with trans != 'N': refining a transposed system needs a transposed SpMV (not built)")
+        raise ValueError("refine=True with trans != 'N': not in this driver -- solve with refine=False and keep=True, then refine with "
+                         "LUHandle.pdgsrfs3d(b, x, trans=...) on the attached matrix")
     symb = Symbolic(n, rowptr, colind, perm_c, relax, maxsup)
     h = LUHandle.from_symbolic(symb, nzval, replace_tiny=replace_tiny)
     if equil:
