@@ -135,7 +135,7 @@ static int read_matrix_market(const char *path, int64_t *n_out, int **rp_out, in
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s N [-nd] [--equil] [--steps K] | file.dat [--equil] [--steps K] | file.mtx [--equil] [--steps K]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s N [-nd] [--equil] [--rowperm] [--steps K] | file.dat [--equil] [--rowperm] [--steps K] | file.mtx [--equil] [--rowperm] [--steps K]\n", argv[0]); return 2; }
     if (sluamd_device_count() < 1) { fprintf(stderr, "no HIP device: this library has no CPU fallback\n"); return 3; }
     int64_t n; int *rp, *ci; double *v;
     char *end;
@@ -143,6 +143,8 @@ int main(int argc, char **argv)
     int use_nd = argc > 2 && !strcmp(argv[2], "-nd");
     int equil = 0;                                            /* --equil: Equil = YES (pdgsequ + pdlaqgs on the device, scaled solve) */
     for (int a = 2; a < argc; ++a) if (!strcmp(argv[a], "--equil")) equil = 1;
+    int rowperm = 0;                                          /* --rowperm: RowPerm = LargeDiag_MC64 (matching on the device + host, its scalings, solve in A's ordering) */
+    for (int a = 2; a < argc; ++a) if (!strcmp(argv[a], "--rowperm")) rowperm = 1;
     long nsteps = 0;                                          /* --steps K: K same-pattern value updates after the first solve */
     for (int a = 2; a + 1 < argc; ++a) if (!strcmp(argv[a], "--steps")) nsteps = strtol(argv[a + 1], NULL, 10);
     const size_t len = strlen(argv[1]);
@@ -164,23 +166,49 @@ int main(int argc, char **argv)
         b[i] = s; if (rs > anorm) anorm = rs;
     }
 
+    /* RowPerm = LargeDiag_MC64: perm_r[i] = row of Pr A that row i of A becomes; the handle is built from A1 = Pr A (rpF / ciF / vF, vF[e] = v[pos[e]]) */
+    int *rpF = rp, *ciF = ci, *perm_r = NULL, *pos = NULL; double *vF = v, *rs = NULL, *cs = NULL;
+    if (rowperm) {
+        sluamd_rowperm_t m;
+        perm_r = (int *) malloc(sizeof(int) * n); rs = (double *) malloc(sizeof(double) * n); cs = (double *) malloc(sizeof(double) * n);
+        CHECK(sluamd_dLargeDiag(-1, n, rp, ci, v, perm_r, rs, cs, &m));
+        printf("ROWPERM: rounds %d  matched on the device %lld of %lld  augmenting paths on the host %lld  info %d\n", m.rounds, (long long) m.matched_device,
+               (long long) n, (long long) m.augmentations, m.info);
+        if (m.info) { printf("structurally singular: %d rows cannot be matched\n", m.info); return 1; }
+        const size_t nz = (size_t) (rp[n] ? rp[n] : 1);
+        rpF = (int *) calloc((size_t) n + 1, sizeof(int)); ciF = (int *) malloc(sizeof(int) * nz); vF = (double *) malloc(sizeof(double) * nz);
+        pos = (int *) malloc(sizeof(int) * nz);
+        double *r1 = (double *) malloc(sizeof(double) * n);                        /* R by the rows of Pr A */
+        for (int64_t i = 0; i < n; ++i) { rpF[perm_r[i] + 1] = rp[i + 1] - rp[i]; r1[perm_r[i]] = rs[i]; }
+        for (int64_t i = 0; i < n; ++i) rpF[i + 1] += rpF[i];
+        for (int64_t i = 0; i < n; ++i)
+            for (int e = rp[i], q = rpF[perm_r[i]]; e < rp[i + 1]; ++e, ++q) { pos[q] = e; ciF[q] = ci[e]; vF[q] = v[e]; }
+        free(rs); rs = r1;
+        use_nd = use_nd || N <= 0;
+    }
+
     /* ColPerm: NATURAL (generated grid) or our nested dissection (files), MY_PERMC in the reference's terms; the etree postorder of
      * the symbolic factorisation is composed into perm_c */
     int *perm_c = (int *) malloc(sizeof(int) * n), *perm_c_in = (int *) malloc(sizeof(int) * n);
-    if (use_nd) CHECK(sluamd_order_nd(n, rp, ci, 64, perm_c_in));
+    if (use_nd) CHECK(sluamd_order_nd(n, rpF, ciF, 64, perm_c_in));
     else for (int64_t i = 0; i < n; ++i) perm_c_in[i] = (int) i;
     sluamd_symb_t symb;
-    CHECK(sluamd_dsymbfact(&symb, n, rp, ci, perm_c_in, 32, 256, perm_c));
+    CHECK(sluamd_dsymbfact(&symb, n, rpF, ciF, perm_c_in, 32, 256, perm_c));
     int32_t nsupers; int64_t nnzL, nnzU; double flops;
     CHECK(sluamd_symb_info(symb, &nsupers, &nnzL, &nnzU, NULL, NULL, &flops));
 
     sluamd_options_t opt; sluamd_default_options(&opt);
     sluamd_handle_t h;
-    CHECK(sluamd_dCreateLUHandleFromSymb(&h, symb, rp, ci, v, perm_c, &opt));
+    CHECK(sluamd_dCreateLUHandleFromSymb(&h, symb, rpF, ciF, vF, perm_c, &opt));
 
     int info = 0;
     sluamd_equil_t eq;
-    if (equil) {   /* scales the handle's matrix; anorm of the scaled matrix comes back (pdgssvx3d.c:673-729) */
+    if (rowperm) {   /* the matching's scalings alone (with --equil; else none: the call attaches A1), then B and X in A's ordering */
+        CHECK(sluamd_dEquilibrateWith(h, (sluamd_int_t) n, rpF, ciF, vF, perm_c, equil ? rs : NULL, equil ? cs : NULL, &eq));
+        CHECK(sluamd_SetRowPerm(h, perm_r));
+        printf("EQUIL: equed = %c  rowcnd %.3e  colcnd %.3e  amax %.3e  info %d\n", "NRCB"[eq.equed], eq.rowcnd, eq.colcnd, eq.amax, eq.info);
+        anorm = eq.anorm;
+    } else if (equil) {   /* scales the handle's matrix; anorm of the scaled matrix comes back (pdgssvx3d.c:673-729) */
         CHECK(sluamd_dEquilibrate(h, (sluamd_int_t) n, rp, ci, v, perm_c, &eq));
         printf("EQUIL: equed = %c  rowcnd %.3e  colcnd %.3e  amax %.3e  info %d\n", "NRCB"[eq.equed], eq.rowcnd, eq.colcnd, eq.amax, eq.info);
         anorm = eq.anorm;
@@ -193,7 +221,7 @@ int main(int argc, char **argv)
      * perm_c run inside the library; a single rank holds all n rows) */
     double *x = (double *) malloc(sizeof(double) * n);
     double berr = 0.0; int32_t steps = 0;
-    if (equil) {   /* the expert driver's solve phase: B scaled by R, solve, refinement on the scaled system, X scaled by C */
+    if (equil || rowperm) {   /* the expert driver's solve phase: B scaled by R, solve, refinement on the scaled system, X scaled by C */
         CHECK(sluamd_pdgssvx3d_solve(h, SLUAMD_NOTRANS, b, n, x, n, 1, 1, &berr, &steps));
     } else {
         memcpy(x, b, sizeof(double) * n);
@@ -231,10 +259,11 @@ int main(int argc, char **argv)
             b[i] = t;
         }
         sluamd_update_t up;                                   /* a matrix is attached by now (sluamd_dEquilibrate / sluamd_dAttachMatrix): it takes the new values, and anorm comes back */
-        CHECK(sluamd_dUpdateValues(h, v2, &up));
+        if (rowperm) { for (int e = 0; e < rp[n]; ++e) vF[e] = v2[pos[e]]; }   /* the handle's CSR is that of Pr A */
+        CHECK(sluamd_dUpdateValues(h, rowperm ? vF : v2, &up));
         CHECK(sluamd_pdgstrf3d(h, 1.1920928955078125e-07 * up.anorm, &info));
         if (info) { printf("STEP %ld: INFO = %d returned from pdgstrf3d (zero pivot)\n", s, info); return 1; }
-        if (equil) {
+        if (equil || rowperm) {
             CHECK(sluamd_pdgssvx3d_solve(h, SLUAMD_NOTRANS, b, n, x, n, 1, 1, &berr, &steps));
         } else {
             memcpy(x, b, sizeof(double) * n);

@@ -84,8 +84,10 @@ typedef struct sluamd_forest_view {
 typedef struct sluamd_options {
     int32_t device;             /* HIP device ordinal (-1 = current device)                      */
     int32_t replace_tiny_pivot; /* options->ReplaceTinyPivot == YES (superlu_defs.h:697)         */
-    int32_t deterministic;      /* 1: one supernode per Schur launch -> fixed summation order of the factors (the solve
-                                 *    still accumulates lsum with fp64 atomics)                 */
+    int32_t deterministic;      /* 1: one supernode per Schur launch -> fixed summation order of the factors; the sweeps of
+                                 *    sluamd_pdgstrs3d on a one-rank double handle run one update unit per launch, so a solve
+                                 *    repeats bit for bit too (grids, complex16 and the transposed sweeps still accumulate
+                                 *    with fp64 atomics in arrival order)                          */
     int32_t verbose;
     int32_t info_rule;          /* which zero pivot `info` names on an exactly singular matrix (round 6; a former reserved slot -- the struct's size and the
                                  * offsets of the fields above are unchanged):
@@ -285,7 +287,7 @@ int sluamd_mfma_selftest(const double *A16x4, const double *B4x16, double *D16x1
 
 /* ---- iterative refinement: pdgsrfs3d (SRC/double/pdgsrfs.c:345-510) with its SpMV pdgsmv (SRC/double/pdgsmv.c) on the
  * device, SURVEY 8(f)-2.  The ORIGINAL matrix (CSR, 0-based) and perm_c are attached once; the factors in the handle are
- * those of Pc A Pc^T (Equil=NO, NOROWPERM -- the boundary's convention).  B, X: original ordering, column-major; X holds
+ * those of Pc A Pc^T (Equil=NO, NOROWPERM -- the boundary's convention; Equil = YES and RowPerm = LargeDiag_MC64 are the sections below).  B, X: original ordering, column-major; X holds
  * the initial solution and is refined in place; berr[nrhs] = componentwise backward errors; *steps = refinement steps of
  * the last right-hand side (stat->RefineSteps).  Stopping rule as the reference: berr > eps, berr*2 <= previous, < 20. */
 int sluamd_dAttachMatrix(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind,
@@ -368,6 +370,17 @@ int sluamd_dEquilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *r
                         const double *nzval, const sluamd_int_t *perm_c, sluamd_equil_t *out);
 int sluamd_zEquilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind,
                         const sluamd_doublecomplex *nzval, const sluamd_int_t *perm_c, sluamd_equil_t *out);
+/* The same with R and C as INPUTS (host arrays of n positive finite values; either may be NULL): for scalings that come from elsewhere, above all from
+ * sluamd_[dz]LargeDiag.  equed follows from which of them is non-NULL (both NULL: SLUAMD_EQUED_N, the call attaches the matrix and returns its norm).
+ * Everything else is the contract of sluamd_[dz]Equilibrate: the attached values are scaled in place as (a r[i]) c[j] in exactly that order and distributed
+ * into the store, the handle is UNFACTORED, anorm is that of the matrix the handle now holds, and a handle takes ONE equilibration of either kind.
+ * rowcnd / colcnd are what pdgsequ defines, formed from the given vectors: max(min r, smlnum) / min(max r, bignum), 1 for a NULL vector; amax is that of
+ * the unscaled matrix; info = 0.  Additional error (SLUAMD_EINVAL): a value of r or c that is not positive and finite. */
+int sluamd_dEquilibrateWith(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind,
+                            const double *nzval, const sluamd_int_t *perm_c, const double *r, const double *c, sluamd_equil_t *out);
+int sluamd_zEquilibrateWith(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind,
+                            const sluamd_doublecomplex *nzval, const sluamd_int_t *perm_c, const double *r, const double *c,
+                            sluamd_equil_t *out);
 /* R[n] and C[n] to the host (either may be NULL); both precisions; all ones where that side was not scaled (also before any
  * equilibration) */
 int sluamd_GetScalings(sluamd_handle_t h, double *r, double *c);
@@ -390,6 +403,51 @@ int sluamd_pzgssvx3d_solve(sluamd_handle_t h, int trans, const sluamd_doublecomp
                            int64_t ldx, int32_t nrhs, int refine, double *berr, int32_t *steps);
 int sluamd_pzgssvx3d_solve_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
                                int64_t ldx, int32_t nrhs, int refine, double *berr, int32_t *steps);
+
+/* ---- RowPerm = LargeDiag_MC64: the row permutation that maximises the product of the moduli on the diagonal, and the scalings that come with it (the
+ * reference's default, dldperm_dist at pdgssvx3d.c:779-870).  This library pivots statically: a matrix whose large entries lie off the diagonal (zeros on
+ * the diagonal: saddle-point and circuit matrices; rows that arrive in another order) needs this step before the symbolic factorisation.
+ *
+ * sluamd_[dz]LargeDiag takes no handle, like sluamd_order_nd.  A: n x n CSR, 0-based, n and rowptr[n] below 2^31 (else SLUAMD_EINVAL, as a column index
+ * outside [0, n) or a descending rowptr); stored entries equal to zero are not edges; device = -1: the current device.  complex16: the modulus by hypot.
+ *   perm_r[i] = j: row i of A is row j of Pr A (the reference's convention, pdgssvx3d.c:406) -- row i is matched to column j, a(i, j) lands on the diagonal.
+ *   r[n] by original row, c[n] by column (either may be NULL): |r[i] a(i,j) c[j]| <= 1 for every entry, = 1 where j = perm_r[i].
+ * Algorithm (Duff & Koster, SIAM J. Matrix Anal. Appl. 22, 2001: shortest augmenting paths on logarithmic costs), a hybrid:
+ *   cost(i,j) = lg(cmax_j) - lg|a(i,j)| >= 0, cmax_j the largest modulus of column j; lg(x) = e + log2(m) for x = m 2^e, 1/2 <= m < 1 (frexp), so the
+ *   logarithm of a power of two is an exact integer on the device and on any host.  Duals u, v: u_i + v_j <= cost(i,j), equality on the matched entries;
+ *   r[i] = 2^u_i, c[j] = 2^v_j / cmax_j.
+ *   Device: column maxima, costs, u_i = min_j cost(i,j), v_j = min_i (cost(i,j) - u_i); then proposal rounds on the tight entries ((cost - u_i) == v_j):
+ *   every unmatched row proposes to its free tight column of lowest index, a column accepts the proposing row of lowest index; the rounds stop after one
+ *   that matches nothing, when every row is matched, or after SLUAMD_ROWPERM_ROUNDS of them (environment, default 32).  All atomics are integer minima /
+ *   maxima / sums and a launch only reads what an earlier launch wrote: the outcome does not depend on scheduling, two calls on the same input return
+ *   bitwise equal perm_r, r, c and counters -- every rank of a grid may compute them on its own, as with sluamd_[dz]Equilibrate.
+ *   Host: for every row still unmatched, in ascending order, a shortest augmenting path (Dijkstra on the reduced costs, binary heap, ties to the lower
+ *   column), the dual update and the augmentation.  SLUAMD_ROWPERM_HOST=1 (environment) skips the proposal rounds, so the host matches every row: for A/B
+ *   timing and tests; the optimum's value is the same, perm_r too where the optimum is unique.
+ * out->info = k > 0: structurally singular, k rows cannot be matched; perm_r, r, c are not written; the call still returns 0.
+ * A matrix whose moduli span more than 2^1000 can overflow r or c.
+ * With the matching's scalings the scaled matrix has a unit diagonal (in modulus) and entries <= 1.  The reference composes them with pdgsequ's scalings;
+ * this library applies them alone (sluamd_[dz]EquilibrateWith): a second equilibration of such a matrix has nothing left to balance. */
+typedef struct sluamd_rowperm {
+    int32_t info;            /* 0; k > 0: structurally singular, k rows cannot be matched (perm_r, r, c not written) */
+    int32_t rounds;          /* proposal rounds run on the device */
+    int64_t matched_device;  /* rows matched by the device phase */
+    int64_t augmentations;   /* shortest augmenting paths found on the host */
+} sluamd_rowperm_t;
+int sluamd_dLargeDiag(int device, int64_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const double *nzval,
+                      sluamd_int_t *perm_r, double *r, double *c, sluamd_rowperm_t *out);
+int sluamd_zLargeDiag(int device, int64_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const sluamd_doublecomplex *nzval,
+                      sluamd_int_t *perm_r, double *r, double *c, sluamd_rowperm_t *out);
+/* The handle was created from A1 = Pr A (and equilibrated with R indexed by A1's rows, R1[perm_r[i]] = r[i]): perm_r[n] (host) tells
+ * sluamd_p[dz]gssvx3d_solve[_dev] that B and X are in A's ordering.  Either precision; with R, C, perm_c the handle's:
+ *   SLUAMD_NOTRANS:          xp[perm_c[perm_r[i]]] = R[perm_r[i]] B[i];   X[j] = C[j] y[perm_c[j]]
+ *   SLUAMD_TRANS / _CONJ:    xp[perm_c[j]] = C[j] B[j];                   X[i] = R[perm_r[i]] y[perm_c[perm_r[i]]]
+ * With refine = 1 the loop runs on the attached (permuted, scaled) system, as without a row permutation.  The composed index and scaling vectors are built
+ * once, on the device, by this call; they belong to the attached matrix: call it AFTER sluamd_[dz]EquilibrateWith / sluamd_[dz]AttachMatrix (a later
+ * attach or equilibration drops the permutation) and before the factorisation.  sluamd_[dz]UpdateValues is unchanged: its values are those of the CSR the
+ * handle was created from, that is A1.  Errors, all SLUAMD_EINVAL with a message: perm_r is not a permutation of 0 .. n-1; no matrix is attached; the
+ * handle holds factors. */
+int sluamd_SetRowPerm(sluamd_handle_t h, const sluamd_int_t *perm_r);
 
 /* ---- Fact = SamePattern_SameRowPerm: new numeric values for the pattern the handle was planned for (superlu_defs.h:545-566; Newton steps, time
  * stepping, parameter sweeps).  For handles made by sluamd_[dz]CreateLUHandleFromSymb[Grid]; a view-created handle takes new values in store form through

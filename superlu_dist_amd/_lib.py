@@ -52,6 +52,11 @@ class Update(C.Structure):
     _fields_ = [("anorm", C.c_double), ("equed", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RowPerm(C.Structure):
+    """sluamd_rowperm_t"""
+    _fields_ = [("info", C.c_int32), ("rounds", C.c_int32), ("matched_device", C.c_int64), ("augmentations", C.c_int64)]
+
+
 EXPORTS = [
     "sluamd_default_options", "sluamd_dCreateLUHandle", "sluamd_dSetValues", "sluamd_pdgstrf3d",
     "sluamd_dCopyLU2Host", "sluamd_pdgstrs3d", "sluamd_pdgstrs3d_dev", "sluamd_pdgstrs3d_dist", "sluamd_pzgstrs3d_dist", "sluamd_dDestroyLUHandle",
@@ -63,6 +68,7 @@ EXPORTS = [
     "sluamd_pdgstrs3d_trans", "sluamd_pdgstrs3d_trans_dev", "sluamd_pzgstrs3d_trans", "sluamd_pzgstrs3d_trans_dev",
     "sluamd_pdgsrfs3d_trans", "sluamd_pdgsrfs3d_trans_dev", "sluamd_pzgsrfs3d_trans", "sluamd_pzgsrfs3d_trans_dev",
     "sluamd_dEquilibrate", "sluamd_zEquilibrate", "sluamd_GetScalings",
+    "sluamd_dEquilibrateWith", "sluamd_zEquilibrateWith", "sluamd_dLargeDiag", "sluamd_zLargeDiag", "sluamd_SetRowPerm",
     "sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev",
     "sluamd_dUpdateValues", "sluamd_dUpdateValues_dev", "sluamd_zUpdateValues", "sluamd_zUpdateValues_dev",
     "sluamd_comm_rccl_unique_id", "sluamd_comm_create_rccl", "sluamd_comm_create_callbacks", "sluamd_comm_create_local",
@@ -161,6 +167,15 @@ def bind(L):
     for name in ("sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int, P_dbl, P_int]
+    # RowPerm = LargeDiag_MC64 and its handle integration: only in the product library (the CPU test build has no matching kernels)
+    for name in ("sluamd_dEquilibrateWith", "sluamd_zEquilibrateWith"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int32, P_int, P_int, C.c_void_p, P_int, P_dbl, P_dbl, C.POINTER(Equil)]
+    for name in ("sluamd_dLargeDiag", "sluamd_zLargeDiag"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_int, C.c_int64, P_int, P_int, C.c_void_p, P_int, P_dbl, P_dbl, C.POINTER(RowPerm)]
+    if hasattr(L, "sluamd_SetRowPerm"):
+        L.sluamd_SetRowPerm.argtypes = [C.c_void_p, P_int]
     # same-pattern value updates: only in the product library (the CPU test build has no update kernels)
     for name in ("sluamd_dUpdateValues", "sluamd_dUpdateValues_dev", "sluamd_zUpdateValues", "sluamd_zUpdateValues_dev"):
         if hasattr(L, name):

@@ -526,7 +526,8 @@ int reset_store(Handle *H, bool scatter)
 void free_rfs(Handle *H)
 {
     void **ps[] = {(void **) &H->d_rfs_rp, (void **) &H->d_rfs_ci, (void **) &H->d_rfs_pc, (void **) &H->d_rfs_av, (void **) &H->d_rfs_work, (void **) &H->d_rfs_s,
-                   (void **) &H->d_rfs_tcp, (void **) &H->d_rfs_tri, (void **) &H->d_rfs_tpos};      // (the transposed index belongs to the pattern that goes)
+                   (void **) &H->d_rfs_tcp, (void **) &H->d_rfs_tri, (void **) &H->d_rfs_tpos,       // (the transposed index belongs to the pattern that goes)
+                   (void **) &H->d_rp_pr, (void **) &H->d_rp_pcpr, (void **) &H->d_rp_rs};          // (and so does the row permutation of sluamd_SetRowPerm)
     for (void **p : ps) { if (*p) hipFree(*p); *p = nullptr; }
     H->rfs_nnz = 0;
     H->rfs_z = false;

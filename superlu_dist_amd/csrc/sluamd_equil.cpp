@@ -8,6 +8,8 @@
 // are a handful of scalar comparisons on the host between the launches.  The solve wraps the existing drivers: sluamd_p[dz]gstrs3d_trans_dev between two
 // fused permute-and-scale launches, sluamd_p[dz]gsrfs3d_dev for the refinement (three more passes over the block there, see solve_dev) -- the multi-right-hand-side block forms, the grids' replicated form and
 // their error codes come with them.
+// RowPerm = LargeDiag_MC64 meets the handle here: sluamd_[dz]EquilibrateWith is the same equilibration with R and C given (those of sluamd_[dz]LargeDiag),
+// sluamd_SetRowPerm makes the solve take B and X in the ordering of A for a handle created from Pr A (the matching itself: sluamd_rowperm.cpp).
 #include <cstring>
 #include "sluamd_refine.h"
 
@@ -18,8 +20,9 @@ namespace {
 typedef unsigned long long u64;
 double as_double(u64 b) { double d; memcpy(&d, &b, sizeof d); return d; }
 
+// with: sluamd_[dz]EquilibrateWith -- R = r_in and C = c_in (host, either may be null) are inputs, equed follows from which of them is given
 int equilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const void *nzval, const sluamd_int_t *perm_c,
-                sluamd_equil_t *out, bool z, const char *who)
+                sluamd_equil_t *out, bool z, const char *who, bool with = false, const double *r_in = nullptr, const double *c_in = nullptr)
 {
     const std::string me = std::string(who) + ": ";
     if (!h || !rowptr || !colind || !nzval || !perm_c || !out) { set_error(me + "null argument"); return SLUAMD_EINVAL; }
@@ -28,6 +31,21 @@ int equilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, c
     if (!H->d_aent || H->a_csr_nnz < 0) { set_error(me + "the handle was not created from the symbolic structure (sluamd_[dz]CreateLUHandleFromSymb[Grid]): the caller of a view-created handle scales its own values"); return SLUAMD_EINVAL; }
     if (n != H->hs.n || rowptr[n] != H->a_csr_nnz) { set_error(me + "n or the number of entries differs from the matrix the handle was created from"); return SLUAMD_EINVAL; }
     if (H->eq_done) { set_error(me + "the handle has been equilibrated already"); return SLUAMD_EINVAL; }
+    const double smlnum = 0x1p-1022, bignum = 1.0 / smlnum;          // dmach_dist("S")
+    double cnd[2] = {1.0, 1.0};                                      // rowcnd, colcnd of given scalings: smallest over largest, as pdgsequ.c:169, :213
+    if (with) {
+        const double *vec[2] = {r_in, c_in};
+        for (int k = 0; k < 2; ++k) {
+            if (!vec[k] || n == 0) continue;
+            double lo = HUGE_VAL, hi = 0.0;
+            for (sluamd_int_t i = 0; i < n; ++i) {
+                const double t = vec[k][i];
+                if (!(t > 0.0) || !(t < HUGE_VAL)) { set_error(me + (k ? "c" : "r") + " holds a value that is not positive and finite"); return SLUAMD_EINVAL; }
+                lo = std::min(lo, t); hi = std::max(hi, t);
+            }
+            cnd[k] = std::max(lo, smlnum) / std::min(hi, bignum);
+        }
+    }
     if (int rc = attach_rfs(h, n, rowptr, colind, nzval, perm_c, z, who)) return rc;
     *out = sluamd_equil_t{SLUAMD_EQUED_N, 0, 0.0, 0.0, 0.0, 0.0};
     if (n == 0) { out->rowcnd = out->colcnd = 1.0; H->eq_done = true; return 0; }      // pdgsequ.c:114-119
@@ -46,9 +64,17 @@ int equilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, c
     u64 red[3];
     auto reset = [&]() { const u64 init[3] = {~0ull, 0ull, ~0ull}; return hipMemcpyAsync(d_red, init, sizeof init, hipMemcpyHostToDevice, s) == hipSuccess ? hipStreamSynchronize(s) : hipErrorUnknown; };
     auto fetch = [&]() { return hipMemcpyAsync(red, d_red, sizeof red, hipMemcpyDeviceToHost, s) == hipSuccess ? hipStreamSynchronize(s) : hipErrorUnknown; };
-    const double smlnum = 0x1p-1022, bignum = 1.0 / smlnum;          // dmach_dist("S")
     int mode = 0;                                                   // bit 0: rows, bit 1: columns
-    do {
+    if (with) {   // amax of the unscaled matrix (the row maxima land in the work vector the column sums zero-fill below); R and C as given
+        HIPCHK(reset());
+        eng::eq_rowmax(s, z, n, nnz, H->d_rfs_rp, H->d_rfs_av, H->d_rfs_work, d_red);
+        HIPCHK(fetch());
+        out->amax = as_double(red[1]);
+        out->rowcnd = cnd[0]; out->colcnd = cnd[1];
+        if (r_in) HIPCHK(hipMemcpyAsync(H->d_eq_r, r_in, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        if (c_in) HIPCHK(hipMemcpyAsync(H->d_eq_c, c_in, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        mode = (r_in ? 1 : 0) | (c_in ? 2 : 0);
+    } else do {
         HIPCHK(reset());
         eng::eq_rowmax(s, z, n, nnz, H->d_rfs_rp, H->d_rfs_av, H->d_eq_r, d_red);
         HIPCHK(fetch());
@@ -128,15 +154,23 @@ int solve_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, doub
     hipStream_t s = H->stream;
     const double *R = H->eq_row ? H->d_eq_r : nullptr, *Cs = H->eq_col ? H->d_eq_c : nullptr;
     const double *s_in = trans == SLUAMD_NOTRANS ? R : Cs, *s_out = trans == SLUAMD_NOTRANS ? Cs : R;      // pdgssvx3d.c:1450-1465, :1806-1821
-    eng::eq_permscale(s, z, false, n, nrhs, H->d_rfs_pc, s_in, d_B, ldb, xp, n);
+    // sluamd_SetRowPerm: the handle holds Pr A, B and X are in A's ordering.  Row i of A is row perm_r[i] of the attached system, so whatever is indexed by
+    // the ROWS -- B and R of op = N, X and R of op = T / C -- goes through perm_r; the column side is untouched
+    const int *p_in = H->d_rfs_pc, *p_out = H->d_rfs_pc, *p_rows = nullptr;
+    if (H->d_rp_pr) {
+        p_rows = H->d_rp_pr;
+        if (trans == SLUAMD_NOTRANS) { p_in = H->d_rp_pcpr; if (R) s_in = H->d_rp_rs; }
+        else { p_out = H->d_rp_pcpr; if (R) s_out = H->d_rp_rs; }
+    }
+    eng::eq_permscale(s, z, false, n, nrhs, p_in, s_in, d_B, ldb, xp, n);
     HIPCHK(hipGetLastError());
     int rc = z ? sluamd_pzgstrs3d_trans_dev(h, trans, reinterpret_cast<sluamd_doublecomplex *>(xp), n, nrhs) : sluamd_pdgstrs3d_trans_dev(h, trans, xp, n, nrhs);
     if (rc) return rc;
     if (!refine) {
-        eng::eq_permscale(s, z, true, n, nrhs, H->d_rfs_pc, s_out, xp, n, d_X, ldx);
-    } else {   // the scaled system is refined, then X = s_out o X' (pdgssvx3d.c:1700-1821)
-        eng::eq_permscale(s, z, true, n, nrhs, H->d_rfs_pc, nullptr, xp, n, d_X, ldx);
-        eng::eq_permscale(s, z, false, n, nrhs, nullptr, s_in, d_B, ldb, xp, n);
+        eng::eq_permscale(s, z, true, n, nrhs, p_out, s_out, xp, n, d_X, ldx);
+    } else {   // the scaled system is refined, then X = s_out o X' (pdgssvx3d.c:1700-1821); op = N here (check_solve), so p_out is perm_c
+        eng::eq_permscale(s, z, true, n, nrhs, p_out, nullptr, xp, n, d_X, ldx);
+        eng::eq_permscale(s, z, false, n, nrhs, p_rows, s_in, d_B, ldb, xp, n);      // B' in the attached system's row order
         HIPCHK(hipGetLastError());
         rc = z ? sluamd_pzgsrfs3d_dev(h, reinterpret_cast<const sluamd_doublecomplex *>(xp), n, reinterpret_cast<sluamd_doublecomplex *>(d_X), ldx, nrhs, berr, steps)
                : sluamd_pdgsrfs3d_dev(h, xp, n, d_X, ldx, nrhs, berr, steps);
@@ -181,6 +215,50 @@ int sluamd_zEquilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *r
                         const sluamd_int_t *perm_c, sluamd_equil_t *out)
 {
     return equilibrate(h, n, rowptr, colind, nzval, perm_c, out, true, "sluamd_zEquilibrate");
+}
+
+int sluamd_dEquilibrateWith(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const double *nzval,
+                            const sluamd_int_t *perm_c, const double *r, const double *c, sluamd_equil_t *out)
+{
+    return equilibrate(h, n, rowptr, colind, nzval, perm_c, out, false, "sluamd_dEquilibrateWith", true, r, c);
+}
+
+int sluamd_zEquilibrateWith(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const sluamd_doublecomplex *nzval,
+                            const sluamd_int_t *perm_c, const double *r, const double *c, sluamd_equil_t *out)
+{
+    return equilibrate(h, n, rowptr, colind, nzval, perm_c, out, true, "sluamd_zEquilibrateWith", true, r, c);
+}
+
+int sluamd_SetRowPerm(sluamd_handle_t h, const sluamd_int_t *perm_r)
+{
+    const std::string me = "sluamd_SetRowPerm: ";
+    if (!h || !perm_r) { set_error(me + "null argument"); return SLUAMD_EINVAL; }
+    Handle *H = &h->H;
+    if (!H->d_rfs_pc) { set_error(me + "no matrix attached (perm_c): call sluamd_[dz]EquilibrateWith, sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix first"); return SLUAMD_EINVAL; }
+    if (H->factored) { set_error(me + "the handle holds factors: set the row permutation before the factorisation"); return SLUAMD_EINVAL; }
+    const int64_t n = H->hs.n;
+    std::vector<uint8_t> seen((size_t) n, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t j = perm_r[i];
+        if (j < 0 || j >= n || seen[j]) { set_error(me + "perm_r is not a permutation of 0 .. n-1"); return SLUAMD_EINVAL; }
+        seen[j] = 1;
+    }
+    HIPCHK(hipSetDevice(H->device));
+    void **ps[] = {(void **) &H->d_rp_pr, (void **) &H->d_rp_pcpr, (void **) &H->d_rp_rs};
+    auto drop = [&]() { for (void **p : ps) { if (*p) hipFree(*p); *p = nullptr; } };
+    drop();
+    if (n == 0) return 0;
+    hipError_t e = hipMalloc((void **) &H->d_rp_pr, sizeof(int) * (size_t) n);
+    if (e == hipSuccess) e = hipMalloc((void **) &H->d_rp_pcpr, sizeof(int) * (size_t) n);
+    if (e == hipSuccess && H->eq_row) e = hipMalloc((void **) &H->d_rp_rs, sizeof(double) * (size_t) n);
+    if (e == hipSuccess) e = hipMemcpyAsync(H->d_rp_pr, perm_r, sizeof(int) * (size_t) n, hipMemcpyHostToDevice, H->stream);
+    if (e == hipSuccess) {
+        eng::rp_compose(H->stream, (int) n, H->d_rp_pr, H->d_rfs_pc, H->eq_row ? H->d_eq_r : nullptr, H->d_rp_pcpr, H->d_rp_rs);
+        e = hipStreamSynchronize(H->stream);
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { drop(); set_error(me + hipGetErrorString(e)); return SLUAMD_EHIP; }
+    return 0;
 }
 
 int sluamd_GetScalings(sluamd_handle_t h, double *r, double *c)

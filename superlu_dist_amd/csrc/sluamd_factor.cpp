@@ -787,6 +787,46 @@ static int solve_bwd_links(Handle *H, LevelSched &S, double *d_x, int64_t ldx, i
     return 0;
 }
 
+// The links of a handle created with options.deterministic: the same units, records and vectors as solve_fwd_links / solve_bwd_links, but every update unit is a
+// launch of its own, in list order.  Units of one launch subtract from shared rows of x with fp64 atomics, in whatever order they arrive; one unit per launch
+// on one stream fixes that order, so a solve repeats bit for bit (the diagonal units write distinct blocks out of place and stay together).  As slow as the
+// deterministic factorisation is: one launch per unit.
+static int solve_fwd_links_serial(Handle *H, LevelSched &S, double *d_x, int64_t ldx, int nrhs)
+{
+    const DevTables &T = H->T;
+    hipStream_t s = H->stream;
+    const int nl = S.nlevels;
+    if (nl == 0) return 0;
+    double *w = H->d_w;
+    const int4 *fr = S.d_fwd_recs, *dr = S.d_diag_recs;
+    for (int l = 0; l < nl; ++l) {
+        const int nd = S.du_off[l + 1] - S.du_off[l];
+        eng::sweep_step(s, true, T, S.d_diag_units + S.du_off[l], nd, nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[l], dr ? dr + 2 * (size_t) S.du_off[l] : nullptr, nullptr);
+        for (int u = S.fu_off[2 * l]; u < S.fu_off[2 * l + 2]; ++u)
+            eng::fwd_update(s, T, nullptr, nullptr, 0, 1, w, d_x, ldx, nrhs, S.max_nsupc[l], S.d_fwd_units + u, fr ? fr + 2 * (size_t) u : nullptr);
+        H->st.solve_launches += 1 + S.fu_off[2 * l + 2] - S.fu_off[2 * l];
+    }
+    return 0;
+}
+
+static int solve_bwd_links_serial(Handle *H, LevelSched &S, double *d_x, int64_t ldx, int nrhs)
+{
+    const DevTables &T = H->T;
+    hipStream_t s = H->stream;
+    const int nl = S.nlevels;
+    if (nl == 0) return 0;
+    double *w = H->d_w;
+    const int4 *br = S.d_bwd_recs, *dr = S.d_diag_recs;
+    for (int l = nl - 1; l >= 0; --l) {     // every chunk of level l reads x of levels above l (or of other forests) only: all of them, then the level's diagonal units
+        for (int u = S.bu_off[2 * l]; u < S.bu_off[2 * l + 2]; ++u)
+            eng::bwd_update(s, T, nullptr, nullptr, 0, 1, d_x, w, ldx, nrhs, S.max_nsupc[l], S.d_bwd_units + u, br ? br + 2 * (size_t) u : nullptr);
+        const int nd = S.du_off[l + 1] - S.du_off[l];
+        eng::sweep_step(s, false, T, S.d_diag_units + S.du_off[l], nd, nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[l], dr ? dr + 2 * (size_t) S.du_off[l] : nullptr, nullptr);
+        H->st.solve_launches += 1 + S.bu_off[2 * l + 2] - S.bu_off[2 * l];
+    }
+    return 0;
+}
+
 // the strips of a merged group stage the group's right-hand sides in LDS (nG x nrhs doubles): wider blocks of right-hand sides take the ungrouped schedule
 static inline bool groups_fit(const Handle *H, int nrhs)
 {
@@ -802,6 +842,7 @@ static int solve_fwd_z(Handle *H, int z, double *d_x, int64_t ldx, int nrhs)
     const bool xy = H->grid.Pr * H->grid.Pc > 1;
     if (!xy && !H->z && !H->profile) {
         int rc = ensure_w(H, ldx * (int64_t) max_rhs_chunk(H));
+        if (!rc && H->opt.deterministic) return solve_fwd_links_serial(H, S, d_x, ldx, nrhs);
         if (!rc && !H->ssched.empty() && H->ssched[z].join && groups_fit(H, nrhs)) return solve_fwd_join(H, H->ssched[z], d_x, ldx, nrhs);     // merged chain groups: the contracted schedule
         if (!rc && S.join) return solve_fwd_join(H, S, d_x, ldx, nrhs);
         return rc ? rc : solve_fwd_links(H, S, d_x, ldx, nrhs);
@@ -831,6 +872,7 @@ static int solve_bwd_z(Handle *H, int z, double *d_x, int64_t ldx, int nrhs)
     const bool xy = H->grid.Pr * H->grid.Pc > 1;
     if (!xy && !H->z && !H->profile) {
         int rc = ensure_w(H, ldx * (int64_t) max_rhs_chunk(H));      // (already there: the forward sweep ran first)
+        if (!rc && H->opt.deterministic) return solve_bwd_links_serial(H, S, d_x, ldx, nrhs);
         if (!rc && !H->ssched.empty() && H->ssched[z].join && groups_fit(H, nrhs)) return solve_bwd_join(H, H->ssched[z], d_x, ldx, nrhs);
         if (!rc && S.join) return solve_bwd_join(H, S, d_x, ldx, nrhs);
         return rc ? rc : solve_bwd_links(H, S, d_x, ldx, nrhs);

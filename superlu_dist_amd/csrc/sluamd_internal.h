@@ -371,6 +371,9 @@ struct Handle {
     // equilibration (sluamd_[dz]Equilibrate, sluamd_equil.cpp): R and C on the device, what was applied, and the work block of the expert solve
     double *d_eq_r = nullptr, *d_eq_c = nullptr; bool eq_done = false, eq_row = false, eq_col = false;
     double *d_eq_work = nullptr; int64_t eq_work_cap = 0;     // [xp | B | X] of sluamd_p[dz]gssvx3d_solve (doubles)
+    // sluamd_SetRowPerm (sluamd_equil.cpp): the handle was made from Pr A; perm_r, perm_c o perm_r and (row-scaled handles) R o perm_r, composed once.  They
+    // belong to the attached matrix and go with it (free_rfs)
+    int *d_rp_pr = nullptr, *d_rp_pcpr = nullptr; double *d_rp_rs = nullptr;
     // same-pattern value updates (sluamd_[dz]UpdateValues, sluamd_update.cpp): the staging buffer of the host-pointer form (grows once), the event that marks
     // its copy complete, and (row, column) in the caller's CSR of every owned entry -- built on the first update of a handle whose values are scaled
     double *d_upd_stage = nullptr; int64_t upd_stage_cap = 0; hipEvent_t ev_upd = nullptr;
@@ -553,6 +556,18 @@ void eq_permscale(hipStream_t s, bool z, bool gather, int n, int nrhs, const int
 // no restatement of them).  update_rowcol: ij[e] = (row, column) of CSR entry ent[e].  update_values: v = nz[ent[e]], scaled (v r[i]) c[j] where r / c are given
 // (ij may be null when both are), stored to aval[e] and val[pos[e]].  update_attached: av[e] = (nz[e] r[i]) c[j] over the CSR by rows; colsum (zero-filled, may
 // be null) += the moduli by column
+// RowPerm = LargeDiag_MC64 (sluamd_pkernels.inc).  Referenced only by sluamd_rowperm.cpp and sluamd_equil.cpp (the CPU test build of the host sources has no
+// restatement of them).  rp_colmax: cmax zero-filled; rp_v: v filled by rp_fill_inf; rp_propose / rp_accept: one proposal round, prop filled with INT32_MAX
+// before the first, *count += the matches of the round; rp_compose: pcpr[i] = pc[pr[i]], rs[i] = r[pr[i]] (r and rs may be null)
+void rp_colmax(hipStream_t s, bool z, int n, int64_t nnz, const int *rp, const int *ci, const void *av, double *cmax);
+void rp_cost_u(hipStream_t s, bool z, int n, int64_t nnz, const int *rp, const int *ci, const void *av, const double *cmax, double *cost, double *u);
+void rp_v(hipStream_t s, int n, int64_t nnz, const int *rp, const int *ci, const double *cost, const double *u, double *v);
+void rp_propose(hipStream_t s, int n, int64_t nnz, const int *rp, const int *ci, const double *cost, const double *u, const double *v, const int *rowmatch,
+                const int *colmatch, int *prop);
+void rp_accept(hipStream_t s, int n, int *prop, int *rowmatch, int *colmatch, int *count);
+void rp_fill(hipStream_t s, int64_t cnt, int *p, int value);
+void rp_fill_inf(hipStream_t s, int64_t cnt, double *p);
+void rp_compose(hipStream_t s, int n, const int *pr, const int *pc, const double *r, int *pcpr, double *rs);
 void update_rowcol(hipStream_t s, int64_t cnt, int n, const int *rp, const int *ci, const int *ent, int2 *ij);
 void update_values(hipStream_t s, bool z, int64_t cnt, const int *ent, const int2 *ij, const void *nz, const double *r, const double *c, void *aval,
                    const int64_t *pos, void *val);

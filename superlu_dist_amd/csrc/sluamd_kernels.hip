@@ -3089,6 +3089,7 @@ __global__ void k_mfma_selftest(const double *A, const double *B, double *D)
 #include "sluamd_zkernels.inc"
 #include "sluamd_tkernels.inc"   // transposed / conjugate-transposed sweeps (sluamd_tsolve.cpp)
 #include "sluamd_ekernels.inc"   // equilibration, 1-norm, permute-and-scale of right-hand sides (sluamd_equil.cpp)
+#include "sluamd_pkernels.inc"   // RowPerm = LargeDiag_MC64: costs, duals, proposal rounds (sluamd_rowperm.cpp)
 #include "sluamd_ukernels.inc"   // same-pattern value updates (sluamd_update.cpp)
 #include "sluamd_rkernels.inc"   // residual / backward error of the transposed refinement (sluamd_trefine.cpp)
 

@@ -84,6 +84,39 @@ def order_nd(n, rowptr, colind, leaf=64):
     return perm
 
 
+def large_diag(n, rowptr, colind, nzval, scale=True, device=-1):
+    """RowPerm = LargeDiag_MC64 (sluamd_[dz]LargeDiag; complex nzval takes the z form): the row permutation that maximises the product of the diagonal
+    moduli.  Returns (perm_r, r, c, info): perm_r[i] = j -- row i of A is row j of Pr A, a(i, j) lands on the diagonal; r by original row and c by column
+    with |r a c| <= 1 everywhere and = 1 on the matched entries (both None when scale=False); info = dict(info, rounds, matched_device, augmentations),
+    info["info"] = k > 0: structurally singular, k rows unmatched, and perm_r, r, c are None."""
+    rp = np.ascontiguousarray(rowptr, dtype=np.int32); ci = np.ascontiguousarray(colind, dtype=np.int32)
+    z = np.iscomplexobj(nzval)
+    v = np.ascontiguousarray(nzval, dtype=np.complex128 if z else np.float64)
+    n = int(n)
+    perm = np.full(n, -1, dtype=np.int32)
+    r = np.zeros(n) if scale else None; c = np.zeros(n) if scale else None
+    o = _lib.RowPerm()
+    name = "sluamd_zLargeDiag" if z else "sluamd_dLargeDiag"
+    _lib.check(_lib.entry(name)(int(device), n, _pi(rp), _pi(ci), v.ctypes.data_as(C.c_void_p), _pi(perm), None if r is None else _pd(r),
+                                None if c is None else _pd(c), C.byref(o)), name)
+    info = dict(info=int(o.info), rounds=int(o.rounds), matched_device=int(o.matched_device), augmentations=int(o.augmentations))
+    if o.info > 0:
+        return None, None, None, info
+    return perm, r, c, info
+
+
+def permute_rows_csr(n, rowptr, colind, nzval, perm_r):
+    """CSR of Pr A for perm_r[i] = j (row i of A is row j of Pr A) and the position map of its values: returns (rowptr1, colind1, nzval1, pos) with
+    nzval1 = nzval[pos] -- new values of the same pattern in A's order become those of Pr A by the same take."""
+    rp = np.asarray(rowptr, dtype=np.int64); pr = np.asarray(perm_r, dtype=np.int64)
+    n = int(n)
+    inv = np.empty(n, dtype=np.int64); inv[pr] = np.arange(n)              # row k of Pr A is row inv[k] of A
+    cnt = (rp[1:] - rp[:-1])[inv]
+    rp1 = np.zeros(n + 1, dtype=np.int64); np.cumsum(cnt, out=rp1[1:])
+    pos = np.repeat(rp[:-1][inv] - rp1[:-1], cnt) + np.arange(rp1[n])
+    return rp1.astype(np.int32), np.ascontiguousarray(np.asarray(colind)[pos], dtype=np.int32), np.ascontiguousarray(np.asarray(nzval)[pos]), pos
+
+
 class Symbolic:
     """sluamd_dsymbfact result (our symbfact_dist + pddistribute3d stand-in for a 1x1 layer)."""
 
@@ -183,6 +216,7 @@ class LUHandle:
         self.n = None if store is None else store.n       # order of the matrix (from_symbolic sets it)
         self.nnz = None                                   # entries of the CSR the handle was created from (from_symbolic sets it)
         self.device = -1                                  # HIP device ordinal given at creation (-1: the device that was current)
+        self.rowperm_pos = None                           # pdgssvx3d(rowperm=...): the handle was made from Pr A; values in A's order go through this map
 
     @staticmethod
     def _opts(replace_tiny=False, deterministic=False, device=-1, info_rule=0):
@@ -294,7 +328,11 @@ class LUHandle:
         on the GPU never visit the host; the tensor must stay alive and unchanged until the next synchronising call on the handle (a factorisation).
         The handle is then unfactored; an equilibrated handle scales the new values with its R and C; an attached matrix takes them too.
         Returns None, or dict(anorm, equed) when want_norm (needs an attached matrix).  ValueError, before any library call: wrong dtype, wrong
-        length, non-contiguous data, a tensor on another device."""
+        length, non-contiguous data, a tensor on another device.
+        A handle made by pdgssvx3d(rowperm=...) holds Pr A: nzval is in the order of A's CSR and is taken through the position map first (numpy take; torch
+        index_select on the tensor's device, so device values still never visit the host)."""
+        if self.rowperm_pos is not None:
+            nzval = self._taken = _take_values(nzval, self.rowperm_pos, self.nnz)      # kept: the _dev form reads it until the next synchronising call
         return _update_values(self._h, self.z, self.nnz, self.device, nzval, want_norm)
 
     def attach_matrix(self, n, rowptr, colind, nzval, perm_c):
@@ -321,6 +359,17 @@ class LUHandle:
         """Equil = YES on a handle made by from_symbolic (sluamd_[dz]Equilibrate): pass the arrays the handle was created from.  Returns
         dict(equed="N"|"R"|"C"|"B", info, rowcnd, colcnd, amax, anorm); the handle then holds the scaled matrix, unfactored."""
         return _equilibrate(self._h, self.z, n, rowptr, colind, nzval, perm_c)
+
+    def equilibrate_with(self, n, rowptr, colind, nzval, perm_c, r=None, c=None):
+        """sluamd_[dz]EquilibrateWith: equilibrate() with R and C given (either may be None), e.g. those of large_diag; same return value"""
+        return _equilibrate(self._h, self.z, n, rowptr, colind, nzval, perm_c, with_rc=(r, c))
+
+    def set_row_perm(self, perm_r):
+        """sluamd_SetRowPerm: the handle was made from Pr A; gssvx_solve then takes b and returns x in A's ordering.  After equilibrate_with / attach_matrix."""
+        pr = np.ascontiguousarray(perm_r, dtype=np.int32)
+        if pr.shape != (self.n,):
+            raise ValueError(f"set_row_perm: {self.n} entries expected, got shape {pr.shape}")
+        _lib.check(_lib.entry("sluamd_SetRowPerm")(self._h, _pi(pr)), "sluamd_SetRowPerm")
 
     def scalings(self):
         """(R, C) of the equilibration; all ones where that side was not scaled (sluamd_GetScalings)"""
@@ -480,11 +529,34 @@ def _update_values(h, z, nnz, device, nzval, want_norm):
     return dict(anorm=float(out.anorm), equed=EQUED[out.equed]) if want_norm else None
 
 
-def _equilibrate(h, z, n, rowptr, colind, nzval, perm_c):
+def _take_values(nzval, pos, nnz):
+    """nzval[pos] for the value arrays update_values accepts; anything else (or a wrong length) is passed on for _update_values to refuse"""
+    if type(nzval).__module__.split(".")[0] == "torch" and hasattr(nzval, "data_ptr"):
+        if nzval.dim() != 1 or nzval.numel() != nnz:
+            return nzval
+        import torch
+        out = torch.index_select(nzval, 0, torch.as_tensor(pos, dtype=torch.int64, device=nzval.device))
+        if out.device.type == "cuda":
+            torch.cuda.current_stream(out.device).synchronize()      # the library reads it on the handle's stream
+        return out
+    a = np.asarray(nzval)
+    return a.take(pos) if a.ndim == 1 and a.shape[0] == nnz else nzval
+
+
+def _equilibrate(h, z, n, rowptr, colind, nzval, perm_c, with_rc=None):
     rp = np.ascontiguousarray(rowptr, dtype=np.int32); ci = np.ascontiguousarray(colind, dtype=np.int32)
     pc = np.ascontiguousarray(perm_c, dtype=np.int32)
     v = np.ascontiguousarray(nzval, dtype=np.complex128 if z else np.float64)
     e = _lib.Equil()
+    if with_rc is not None:
+        r, c = (None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in with_rc)
+        for what, a in (("r", r), ("c", c)):
+            if a is not None and a.shape != (int(n),):
+                raise ValueError(f"equilibrate_with: {what} must have shape ({int(n)},), got {a.shape}")
+        name = "sluamd_zEquilibrateWith" if z else "sluamd_dEquilibrateWith"
+        _lib.check(_lib.entry(name)(h, int(n), _pi(rp), _pi(ci), v.ctypes.data_as(C.c_void_p), _pi(pc), None if r is None else _pd(r),
+                                    None if c is None else _pd(c), C.byref(e)), name)
+        return dict(equed=EQUED[e.equed], info=int(e.info), rowcnd=float(e.rowcnd), colcnd=float(e.colcnd), amax=float(e.amax), anorm=float(e.anorm))
     name = "sluamd_zEquilibrate" if z else "sluamd_dEquilibrate"
     _lib.check(_lib.entry(name)(h, int(n), _pi(rp), _pi(ci), v.ctypes.data_as(C.c_void_p), _pi(pc), C.byref(e)), name)
     return dict(equed=EQUED[e.equed], info=int(e.info), rowcnd=float(e.rowcnd), colcnd=float(e.colcnd), amax=float(e.amax), anorm=float(e.anorm))
@@ -543,19 +615,29 @@ def pivot_thresh(n, rowptr, colind, nzval):
 
 
 def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, replace_tiny=False, anorm=None,
-              keep=False, refine=False, trans="N", equil=False):
+              keep=False, refine=False, trans="N", equil=False, rowperm=None, deterministic=False):
     """Solve A x = b -- trans = "T": A^T x = b, "C": A^H x = b, with the same factorisation of A -- through the GPU hot path: symbolic (host) -> device-resident distribute -> pdgstrf3d ->
     pdgstrs3d, with Equil = NO, RowPerm = NOROWPERM, ColPerm = MY_PERMC/NATURAL, IterRefine = NOREFINE
     (the timing configuration of BASELINE.md section 4); refine=True adds IterRefine = SLU_DOUBLE (pdgsrfs3d on the device;
     pzgsrfs3d for complex nzval) and puts `berr` / `refine_steps` into the stats.  equil=True: Equil = YES -- the handle is equilibrated on
     the device (LUHandle.equilibrate), thresh comes from the 1-norm of the scaled matrix, and the solve (and the refinement) runs through
     LUHandle.gssvx_solve in the caller's ordering and scaling; `equed`, `rowcnd`, `colcnd`, `amax` and a positive `equil_info` go into the
-    stats; `anorm` is not used then.  Returns (x, info, stats[, handle, symb])."""
+    stats; `anorm` is not used then.
+    rowperm="LargeDiag_MC64": RowPerm = LargeDiag_MC64 -- large_diag, the CSR of Pr A (permute_rows_csr), perm_c = order_nd of it when none is
+    given, symbolic, handle, equilibrate_with(r, c) when equil (the matching's scalings ALONE; the reference composes them with pdgsequ's), else
+    attach_matrix; set_row_perm; factorisation and gssvx_solve with b and x in A's ordering.  `rowperm` = the matching's counters goes into the
+    stats; a structurally singular A raises RuntimeError.  With keep=True the handle's update_values takes values in A's order.
+    deterministic=True: the handle option of that name (bitwise reproducible factors).
+    Returns (x, info, stats[, handle, symb])."""
     if refine and _trans_code(trans):
         raise ValueError("refine=True with trans != 'N': not in this driver -- solve with refine=False and keep=True, then refine with "
                          "LUHandle.pdgsrfs3d(b, x, trans=...) on the attached matrix")
+    if rowperm is not None:
+        if rowperm != "LargeDiag_MC64":
+            raise ValueError(f"rowperm must be None or 'LargeDiag_MC64', not {rowperm!r}")
+        return _gssvx3d_rowperm(n, rowptr, colind, nzval, b, perm_c, relax, maxsup, replace_tiny, keep, refine, trans, equil, deterministic)
     symb = Symbolic(n, rowptr, colind, perm_c, relax, maxsup)
-    h = LUHandle.from_symbolic(symb, nzval, replace_tiny=replace_tiny)
+    h = LUHandle.from_symbolic(symb, nzval, replace_tiny=replace_tiny, deterministic=deterministic)
     if equil:
         return _gssvx3d_equil(h, symb, n, rowptr, colind, nzval, b, keep, refine, trans)
     thresh = pivot_thresh(n, rowptr, colind, nzval) if anorm is None else 0.5 * float(np.finfo(np.float32).eps) * anorm
@@ -572,6 +654,41 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
         h.attach_matrix(n, rowptr, colind, nzval, symb.perm_c)
         x, berr, steps = h.pdgsrfs3d(b, x)
         st["berr"] = berr; st["refine_steps"] = steps
+    if keep:
+        return x, info, st, h, symb
+    h.destroy(); symb.free()
+    return x, info, st
+
+
+def _gssvx3d_rowperm(n, rowptr, colind, nzval, b, perm_c, relax, maxsup, replace_tiny, keep, refine, trans, equil, deterministic):
+    """the RowPerm = LargeDiag_MC64 path of pdgssvx3d"""
+    perm_r, r, c, rinfo = large_diag(n, rowptr, colind, nzval, scale=equil)
+    if rinfo["info"] > 0:
+        raise RuntimeError(f"pdgssvx3d(rowperm='LargeDiag_MC64'): the matrix is structurally singular, {rinfo['info']} rows cannot be matched")
+    rp1, ci1, v1, pos = permute_rows_csr(n, rowptr, colind, nzval, perm_r)
+    if perm_c is None:
+        perm_c = order_nd(n, rp1, ci1)
+    symb = Symbolic(n, rp1, ci1, perm_c, relax, maxsup)
+    h = LUHandle.from_symbolic(symb, v1, replace_tiny=replace_tiny, deterministic=deterministic)
+    h.rowperm_pos = pos
+    eq = None
+    if equil:
+        r1 = np.empty(int(n)); r1[perm_r] = r                   # R by the rows of Pr A
+        eq = h.equilibrate_with(n, rp1, ci1, v1, symb.perm_c, r1, c)
+        thresh = 0.5 * float(np.finfo(np.float32).eps) * eq["anorm"]
+    else:
+        h.attach_matrix(n, rp1, ci1, v1, symb.perm_c)
+        thresh = pivot_thresh(n, rp1, ci1, v1)
+    h.set_row_perm(perm_r)
+    info = h.pdgstrf3d(thresh)
+    out = h.gssvx_solve(b, trans=trans, refine=refine)
+    st = h.stats()
+    st["rowperm"] = rinfo; st["perm_r"] = perm_r
+    if eq is not None:
+        st.update(equed=eq["equed"], rowcnd=eq["rowcnd"], colcnd=eq["colcnd"], amax=eq["amax"])
+    x = out
+    if refine:
+        x, st["berr"], st["refine_steps"] = out
     if keep:
         return x, info, st, h, symb
     h.destroy(); symb.free()
