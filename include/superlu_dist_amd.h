@@ -177,14 +177,25 @@ int sluamd_pzgstrs3d(sluamd_handle_t h, sluamd_doublecomplex *x, int64_t ldx, in
  * The reference's pdgstrs3d has no such solve (pdgssvx3d reads options->Trans for the equilibration only).
  * SLUAMD_NOTRANS calls sluamd_pdgstrs3d[_dev] / sluamd_pzgstrs3d and nothing else; it also gives complex16 handles a
  * device-pointer solve.  Errors: trans outside {0, 1, 2} or a handle of the other precision: SLUAMD_EINVAL.  GRID HANDLES of
- * more than one rank: SLUAMD_EINVAL for SLUAMD_TRANS / SLUAMD_CONJ (sluamd_last_error() says that transposed solves need a
- * 1 x 1 x 1 handle) -- the transposed sweeps broadcast along the other grid axis and need exchange plans of their own; not
- * built.  nrhs == 0 returns 0.  stats.t_solve_ms and stats.solve_launches are filled as by the untransposed solve: per chunk of
- * right-hand sides one diagonal and one update launch per DAG level and sweep (4 x levels). */
+ * more than one rank, after sluamd_PlanTransposedSweeps (below): the replicated form of sluamd_pdgstrs3d -- every rank passes the
+ * complete x, the call is collective, every rank returns the complete solution.  The transposed sweeps reduce the partial sums of
+ * x_k along process COLUMN k % Pc and broadcast x_k along process ROW k % Pr (the untransposed ones the other way round), through
+ * exchange lists of their own.  A grid handle whose lists were not planned returns SLUAMD_EINVAL for SLUAMD_TRANS / SLUAMD_CONJ, as
+ * every grid handle did before these lists existed (sluamd_last_error() names the call); that and the argument errors above are
+ * decided on state that is the same on all ranks, before the first exchange, so every rank returns them alike.
+ * sluamd_p[dz]gstrs3d_dist (B distributed by rows) stays untransposed.
+ * nrhs == 0 returns 0.  stats.t_solve_ms and stats.solve_launches are filled as by the untransposed solve: per chunk of
+ * right-hand sides one diagonal and one update launch per DAG level and sweep (4 x levels; on a grid: of the forests this rank sweeps). */
 #define SLUAMD_NOTRANS 0
 #define SLUAMD_TRANS   1
 #define SLUAMD_CONJ    2   /* conjugate transpose; identical to SLUAMD_TRANS on double handles */
 int sluamd_pdgstrs3d_trans(sluamd_handle_t h, int trans, double *x, int64_t ldx, int32_t nrhs);
+/* Plans the exchange lists of the transposed sweeps on a handle of more than one rank: from then on sluamd_p[dz]gstrs3d_trans,
+ * sluamd_p[dz]gsrfs3d_trans and sluamd_p[dz]gssvx3d_solve take SLUAMD_TRANS / SLUAMD_CONJ on it.  EVERY rank of the grid calls it,
+ * any time after the handle was created; it is local (the handle's own level lists and grid position, no communication, no device
+ * work), costs a few run lists per level, and may be repeated.  A handle that never asks plans nothing.  1 x 1 x 1 handles: returns 0,
+ * nothing to plan. */
+int sluamd_PlanTransposedSweeps(sluamd_handle_t h);
 int sluamd_pdgstrs3d_trans_dev(sluamd_handle_t h, int trans, double *d_x, int64_t ldx, int32_t nrhs);
 int sluamd_pzgstrs3d_trans(sluamd_handle_t h, int trans, sluamd_doublecomplex *x, int64_t ldx, int32_t nrhs);
 int sluamd_pzgstrs3d_trans_dev(sluamd_handle_t h, int trans, sluamd_doublecomplex *d_x, int64_t ldx, int32_t nrhs);
@@ -202,6 +213,10 @@ int sluamd_setup_times(sluamd_handle_t h, char *buf, int32_t cap);
  * SCT counters commVolFactor / commVolRed, sec_structs.c). */
 #define SLUAMD_PLAN_COLS 20
 int sluamd_plan_table(sluamd_handle_t h, double *buf, int64_t cap_rows, int64_t *rows);
+/* The x-segment exchange lists of the solve sweeps on this rank's plan, read-only (tests compare the two sides of every message).  which: 0 .. 3 = the
+ * untransposed sweeps' reduce-send, reduce-receive, broadcast-send, broadcast-receive lists, 4 .. 7 = the same of the transposed sweeps.  One row of 5 ints
+ * per run, in list order: Z level, DAG level, peer (world rank), first row, rows (in doubles: complex16 rows count twice).  buf may be NULL: *rows = rows needed. */
+int sluamd_plan_xlists(sluamd_handle_t h, int which, int32_t *buf, int64_t cap_rows, int64_t *rows);
 const char *sluamd_last_error(void);
 /* number of visible HIP devices (0 when none) -- lets callers fail loudly instead of falling back */
 int sluamd_device_count(void);
@@ -320,8 +335,9 @@ int sluamd_pzgsrfs3d_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_B, int
  * was attached (its time appears in sluamd_setup_times as refine.transposed_index) and dropped with that matrix.
  * SLUAMD_NOTRANS calls sluamd_p[dz]gsrfs3d[_dev] and nothing else.  nrhs == 0 returns 0 with *steps = 0.
  * Errors, all SLUAMD_EINVAL with a message: trans outside {0, 1, 2}; a handle of the other precision; no attached matrix, or one of the
- * other precision; SLUAMD_TRANS / SLUAMD_CONJ on a grid handle of more than one rank (transposed refinement needs a 1 x 1 x 1 handle, as
- * the transposed solves do).
+ * other precision; a grid handle without sluamd_PlanTransposedSweeps.  Grid handles: the replicated form of sluamd_p[dz]gsrfs3d (the complete attached matrix, B and X on every rank,
+ * collective); berr and the step count come from replicated data and are the same on every rank, the continue / stop decision is agreed
+ * by a min-all-reduce.
  * After sluamd_[dz]Equilibrate the attached matrix is the scaled one, A' = R A C, and these calls refine op(A') x' = b': for
  * op(A) x = b pass b' = C o b and the scaled solution x' (op(A') x' = b' with x = R o x'), then unscale x = R o x' -- the roles of R and C
  * swapped against the untransposed system, see sluamd_p[dz]gssvx3d_solve. */
@@ -393,8 +409,8 @@ int sluamd_GetScalings(sluamd_handle_t h, double *r, double *c);
  * the residuals, X unscaled in place at the end; each entry point also synchronises its stream once beside the waits of the wrapped calls);
  * berr[nrhs] and *steps as there (both may be NULL when refine == 0).  refine with SLUAMD_TRANS / SLUAMD_CONJ: SLUAMD_EINVAL here -- solve
  * with refine == 0, then refine the scaled system with sluamd_p[dz]gsrfs3d_trans[_dev] (b' = C o b, x' = x / R; the recipe is at their
- * declaration).  Grid handles: the replicated form (complete B in, complete X out, collective); SLUAMD_TRANS / SLUAMD_CONJ there:
- * SLUAMD_EINVAL, as for sluamd_p[dz]gstrs3d_trans.  nrhs == 0 returns 0. */
+ * declaration).  Grid handles: the replicated form (complete B in, complete X out, collective); SLUAMD_TRANS / SLUAMD_CONJ there after sluamd_PlanTransposedSweeps, else SLUAMD_EINVAL.
+ * nrhs == 0 returns 0. */
 int sluamd_pdgssvx3d_solve(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs,
                            int refine, double *berr, int32_t *steps);
 int sluamd_pdgssvx3d_solve_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs,

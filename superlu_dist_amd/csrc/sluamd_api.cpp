@@ -648,6 +648,36 @@ int sluamd_setup_times(sluamd_handle_t h, char *buf, int32_t cap)
     return 0;
 }
 
+// Plans the exchange lists of the transposed sweeps of a handle of more than one rank (header: sluamd_PlanTransposedSweeps)
+int sluamd_PlanTransposedSweeps(sluamd_handle_t h)
+{
+    if (!h) { set_error("sluamd_PlanTransposedSweeps: null handle"); return SLUAMD_EINVAL; }
+    return plan_trans_exchange(&h->H);
+}
+
+// The x-segment exchange lists of the solve sweeps on THIS rank's plan (read-only; tests compare both sides of every message).  which: 0 .. 3 =
+// LevelSched::xs_red_send, xs_red_recv, xs_bc_send, xs_bc_recv (untransposed sweeps), 4 .. 7 = xt_red_send, xt_red_recv, xt_bc_send, xt_bc_recv (transposed).
+// One row of 5 ints per run, in list order: Z level, DAG level, peer (world rank), first row, rows (in doubles of the right-hand side: complex16 rows count twice)
+int sluamd_plan_xlists(sluamd_handle_t h, int which, int32_t *buf, int64_t cap_rows, int64_t *rows)
+{
+    if (!h || !rows || which < 0 || which > 7) { set_error("sluamd_plan_xlists: null argument or which outside 0 .. 7"); return SLUAMD_EINVAL; }
+    const Handle *H = &h->H;
+    int64_t n = 0;
+    for (size_t zl = 0; zl < H->sched.size(); ++zl) {
+        const LevelSched &S = H->sched[zl];
+        const std::vector<std::vector<LevelSched::XSeg>> *lists[8] = {&S.xs_red_send, &S.xs_red_recv, &S.xs_bc_send, &S.xs_bc_recv, &S.xt_red_send, &S.xt_red_recv, &S.xt_bc_send, &S.xt_bc_recv};
+        const auto &v = *lists[which];
+        for (size_t l = 0; l < v.size(); ++l)
+            for (const LevelSched::XSeg &m : v[l])
+                for (const auto &r : m.runs) {
+                    if (buf && n < cap_rows) { int32_t *o = buf + 5 * n; o[0] = (int32_t) zl; o[1] = (int32_t) l; o[2] = m.peer; o[3] = r.first; o[4] = r.second; }
+                    ++n;
+                }
+    }
+    *rows = n;
+    return 0;
+}
+
 // One row of SLUAMD_PLAN_COLS doubles per (Z level, DAG level) of THIS rank's schedule -- what the level costs this rank, from the plan alone:
 //   0 Z level, 1 DAG level, 2 supernodes, 3 widest supernode, 4 exact-segment Schur flops of this rank's tiles, 5 its planned Schur tile executions,
 //   6 diagonal LU + panel-solve flops it owns, 7/8 bytes / messages it SENDS in exchange phase 1 (factored diagonal blocks), 9/10 bytes / messages it receives there,

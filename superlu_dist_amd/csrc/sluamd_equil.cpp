@@ -138,7 +138,7 @@ int check_solve(sluamd_handle_t h, int trans, const void *B, int64_t ldb, const 
     if (H->z != z) { set_error(me + (z ? "double handle: call sluamd_pdgssvx3d_solve" : "complex16 handle: call sluamd_pzgssvx3d_solve")); return SLUAMD_EINVAL; }
     if (!H->d_rfs_pc || H->rfs_z != z) { set_error(me + "no matrix attached (perm_c): call sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix first"); return SLUAMD_EINVAL; }
     if (refine && trans != SLUAMD_NOTRANS) { set_error(me + "refine with a transposed system is not part of this call: solve with refine = 0, then refine the attached (scaled) system with sluamd_p[dz]gsrfs3d_trans"); return SLUAMD_EINVAL; }
-    if (trans != SLUAMD_NOTRANS && H->grid.size() > 1) { set_error(me + "transposed solves need a 1 x 1 x 1 handle"); return SLUAMD_EINVAL; }
+    if (trans != SLUAMD_NOTRANS && H->grid.size() > 1 && !H->xt_ready) { set_error(me + "transposed solves need a 1 x 1 x 1 handle, or a grid handle after sluamd_PlanTransposedSweeps"); return SLUAMD_EINVAL; }
     if (steps) *steps = 0;
     return nrhs == 0 ? 1 : 0;
 }

@@ -594,8 +594,8 @@ static int runs_on_device(Handle *H, const LevelSched::XSeg &m, const int **d)
 
 // exchange of x segments with a set of peers: send = pack (mode 0, or 3 = pack and clear) -> grouped send/recv -> unpack
 // (mode 1 = overwrite, 2 = accumulate)
-static int xseg_exchange(Handle *H, double *d_x, int64_t ldx, int nrhs, const std::vector<LevelSched::XSeg> &snd, int pack_mode,
-                         const std::vector<LevelSched::XSeg> &rcv, int unpack_mode, hipStream_t s)
+int xseg_exchange(Handle *H, double *d_x, int64_t ldx, int nrhs, const std::vector<LevelSched::XSeg> &snd, int pack_mode,
+                  const std::vector<LevelSched::XSeg> &rcv, int unpack_mode, hipStream_t s)
 {
     if (snd.empty() && rcv.empty()) return 0;
     int64_t need = 0;
@@ -1101,8 +1101,12 @@ static int allgather_solution(Handle *H, double *x, int64_t ldxd, int nr, hipStr
 // forward and backward sweeps of one right-hand-side chunk on the grid.  On entry x holds b at the rows this rank consumes (diagonal
 // owner on the factoring layer) and zeros elsewhere; on return x_k is final at those rows.  Z sweeps as pdgsTrForwardSolve3d /
 // pdgsTrBackSolve3d (pdgstrs3d.c:7312, :7564): forward reduction of the ancestor rows to the partner layer (dfsolveReduceLsum3d
-// :1646), backward hand-down of the solved ancestors (dp2pSolvedX3d :1596).
-static int grid_sweeps(Handle *H, double *x, int64_t ldx, int nr)
+// :1646), backward hand-down of the solved ancestors (dp2pSolvedX3d :1596).  `ops` supplies the two per-forest bodies and the forest_runs roles of the
+// rows that hold partial sums / solved entries (untransposed: process row / process column; the transposed sweeps of sluamd_tsolve.cpp: the other way round).
+static int fwd_z_op(Handle *H, int z, double *x, int64_t ldx, int nr, void *) { return solve_fwd_z(H, z, x, ldx, nr); }
+static int bwd_z_op(Handle *H, int z, double *x, int64_t ldx, int nr, void *) { return solve_bwd_z(H, z, x, ldx, nr); }
+static const GridSweepOps plain_ops = {fwd_z_op, bwd_z_op, nullptr, 0, 1};
+static int grid_sweeps(Handle *H, double *x, int64_t ldx, int nr, const GridSweepOps &ops = plain_ops)
 {
     const Grid &g = H->grid;
     const int nzl = (int) H->sched.size();
@@ -1114,11 +1118,11 @@ static int grid_sweeps(Handle *H, double *x, int64_t ldx, int nr)
     for (int zl = 0; zl < nzl; ++zl) {
         const int step = 1 << zl;
         if (g.z % step) break;
-        if (H->z_active[zl] && (rc = solve_fwd_z(H, zl, x, ldx, nr))) return rc;
+        if (H->z_active[zl] && (rc = ops.fwd(H, zl, x, ldx, nr, ops.ctx))) return rc;
         if (zl + 1 < nzl) {
             const bool receiver = (g.z % (2 * step)) == 0;
             if (receiver && g.z + step >= g.Pz) continue;
-            LevelSched::XSeg seg = forest_runs(H, zl + 1, 0);        // (copy shares the cached device image)
+            LevelSched::XSeg seg = forest_runs(H, zl + 1, ops.acc_role);        // (copy shares the cached device image)
             seg.peer = g.rank_of(g.r, g.c, receiver ? g.z + step : g.z - step);
             std::vector<LevelSched::XSeg> one(1, seg), none;
             if (seg.total && (rc = receiver ? xseg_exchange(H, x, ldxd, nr, none, 0, one, 2, s) : xseg_exchange(H, x, ldxd, nr, one, 0, none, 0, s))) return rc;
@@ -1131,13 +1135,13 @@ static int grid_sweeps(Handle *H, double *x, int64_t ldx, int nr)
         if (zl + 1 < nzl) {
             const bool sender = (g.z % (2 * step)) == 0;
             if (!(sender && g.z + step >= g.Pz)) {
-                LevelSched::XSeg seg = forest_runs(H, zl + 1, 1);
+                LevelSched::XSeg seg = forest_runs(H, zl + 1, ops.x_role);
                 seg.peer = g.rank_of(g.r, g.c, sender ? g.z + step : g.z - step);
                 std::vector<LevelSched::XSeg> one(1, seg), none;
                 if (seg.total && (rc = sender ? xseg_exchange(H, x, ldxd, nr, one, 0, none, 0, s) : xseg_exchange(H, x, ldxd, nr, none, 0, one, 1, s))) return rc;
             }
         }
-        if (H->z_active[zl] && (rc = solve_bwd_z(H, zl, x, ldx, nr))) return rc;
+        if (H->z_active[zl] && (rc = ops.bwd(H, zl, x, ldx, nr, ops.ctx))) return rc;
     }
     return 0;
 }
@@ -1154,8 +1158,13 @@ static int grid_solve_checks(Handle *H)
 // complete solution on return.  (sluamd_pdgstrs3d_dist keeps B distributed like the reference.)
 int run_solve_dev(Handle *H, double *d_x, int64_t ldx, int nrhs)
 {
-    const Grid &g = H->grid;
-    if (g.size() == 1) return run_solve_local(H, d_x, ldx, nrhs);
+    if (H->grid.size() == 1) return run_solve_local(H, d_x, ldx, nrhs);
+    return run_grid_solve(H, d_x, ldx, nrhs, plain_ops);
+}
+
+// the replicated grid solve around a pair of per-forest sweeps: checks, per chunk keep b / Z loop / all-gather
+int run_grid_solve(Handle *H, double *d_x, int64_t ldx, int nrhs, const GridSweepOps &ops)
+{
     int rc = grid_solve_checks(H);
     if (rc) return rc;
     hipStream_t s = H->stream;
@@ -1180,7 +1189,7 @@ int run_solve_dev(Handle *H, double *d_x, int64_t ldx, int nrhs)
             eng::xseg_copy(s, x, ldxd, nr, dr, (int) keep.runs.size(), keep.total, H->d_xtmp, 1);
             if (!H->comm->stream_ordered()) HIPCHK(hipStreamSynchronize(s));
         }
-        if ((rc = grid_sweeps(H, x, ldx, nr))) return rc;
+        if ((rc = grid_sweeps(H, x, ldx, nr, ops))) return rc;
         // every x_k is final at its diagonal owner on the layer that factored its forest: all-gather
         if ((rc = allgather_solution(H, x, ldxd, nr, s))) return rc;
     }

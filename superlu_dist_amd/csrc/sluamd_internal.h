@@ -228,6 +228,9 @@ struct LevelSched {
     // solve exchange plan: per level, x segments (as [first row, rows) runs) reduced to / broadcast from the diagonal owners
     struct XSeg { int peer = -1; std::vector<std::pair<int, int>> runs; int64_t total = 0; mutable int *d_runs = nullptr; /* device image, uploaded on first use (owned by Handle::d_misc) */ };
     std::vector<std::vector<XSeg>> xs_red_send, xs_red_recv, xs_bc_send, xs_bc_recv;
+    // ... and of the TRANSPOSED sweeps (sluamd_tsolve.cpp), where the two directions swap: partial sums of x_k are reduced along process COLUMN k % Pc to the
+    // diagonal owner, x_k is broadcast along process ROW k % Pr.  Built on request, after the handle exists (sluamd_PlanTransposedSweeps -> plan_trans_exchange)
+    std::vector<std::vector<XSeg>> xt_red_send, xt_red_recv, xt_bc_send, xt_bc_recv;
     // device copies
     int *d_nodes = nullptr, *d_tile_prefix = nullptr, *d_ltr_prefix = nullptr, *d_utr_prefix = nullptr;
     int *d_fwd_prefix = nullptr, *d_bwd_prefix = nullptr, *d_inv_prefix = nullptr, *d_sn_level = nullptr, *d_zltr_prefix = nullptr;
@@ -411,6 +414,7 @@ struct Handle {
     int xy_scratch_copies = 0;     // XY layers: copies of the received-panel scratch (by level modulo this), 0 on a 1 x 1 layer
     int max_nsupc = 0;
     Comm *comm = nullptr;           // not owned; set by sluamd_dCreateLUHandleGrid / ...FromSymbGrid
+    bool xt_ready = false;          // LevelSched::xt_* are planned (sluamd_PlanTransposedSweeps): a handle of more than one rank takes transposed solves
     std::map<int, LevelSched::XSeg> xseg_cache;        // x-segment run lists of the grid solve (Z exchanges, owner rows), built once
     std::vector<LevelSched::XSeg> owner_runs; bool owner_ready = false;      // every rank's owner rows (where x is final after the sweeps), indexed by world rank; exchanged once
     // distributed right-hand side at the solve boundary (sluamd_pdgstrs3d_dist): routing of the caller's local rows of B to the ranks

@@ -1344,6 +1344,53 @@ static void add_runs(std::vector<std::pair<int, int>> &runs, int64_t &total, int
     total += nrows;
 }
 
+// sluamd_PlanTransposedSweeps: the x-segment exchange lists of the TRANSPOSED sweeps (LevelSched::xt_*, sluamd_tsolve.cpp) of a handle that exists already.
+// Purely local -- the level lists, the partition and the grid position of the handle, no communication -- so ranks cannot disagree about a message: both
+// sides walk the level's supernodes in ASCENDING order (LevelSched::nodes lists a level's big-tile supernodes first, which may differ between ranks) with
+// the same two ownership predicates, and the length of a send equals that of its receive by construction.  Against the lists of the untransposed sweeps
+// (plan_and_upload, step 4) the directions swap.  U^T forward: y_k goes along process ROW k % Pr (where U(k, :) lives) and the partial sums of a later x_j
+// sit on process COLUMN j % Pc; L^T backward: the strips of L(:, k) on process column k % Pc accumulate into x_k and read the solved x_i of process row i % Pr.
+// Run lists in DOUBLES of the right-hand side seen as a real array (complex16 rows count twice).
+int plan_trans_exchange(Handle *H)
+{
+    if (H->xt_ready) return 0;
+    const HostStruct &hs = H->hs;
+    const Grid &g = H->grid;
+    const int xvs = H->z ? 2 : 1;
+    if (g.Pr * g.Pc > 1)
+        for (LevelSched &S : H->sched) {
+            S.xt_red_send.assign(S.nlevels, {}); S.xt_red_recv.assign(S.nlevels, {}); S.xt_bc_send.assign(S.nlevels, {}); S.xt_bc_recv.assign(S.nlevels, {});
+            for (int l = 0; l < S.nlevels; ++l) {
+                std::vector<int> nodes(S.nodes.begin() + S.lvl_off[l], S.nodes.begin() + S.lvl_off[l + 1]);
+                std::sort(nodes.begin(), nodes.end());
+                for (int r2 = 0; r2 < g.Pr; ++r2) {       // partial sums: along my process column, to / at the diagonal owner
+                    if (r2 == g.r) continue;
+                    LevelSched::XSeg snd, rcv; snd.peer = rcv.peer = g.rank_of(r2, g.c, g.z);
+                    for (int k : nodes) {
+                        if (g.kcol(k) != g.c) continue;
+                        if (g.krow(k) == r2) add_runs(snd.runs, snd.total, hs.xsup[k] * xvs, nsupc_of(hs, k) * xvs);
+                        if (g.krow(k) == g.r) add_runs(rcv.runs, rcv.total, hs.xsup[k] * xvs, nsupc_of(hs, k) * xvs);
+                    }
+                    if (snd.total) S.xt_red_send[l].push_back(std::move(snd));
+                    if (rcv.total) S.xt_red_recv[l].push_back(std::move(rcv));
+                }
+                for (int c2 = 0; c2 < g.Pc; ++c2) {       // solved x_k: along my process row, from the diagonal owner
+                    if (c2 == g.c) continue;
+                    LevelSched::XSeg snd, rcv; snd.peer = rcv.peer = g.rank_of(g.r, c2, g.z);
+                    for (int k : nodes) {
+                        if (g.krow(k) != g.r) continue;
+                        if (g.kcol(k) == g.c) add_runs(snd.runs, snd.total, hs.xsup[k] * xvs, nsupc_of(hs, k) * xvs);
+                        if (g.kcol(k) == c2) add_runs(rcv.runs, rcv.total, hs.xsup[k] * xvs, nsupc_of(hs, k) * xvs);
+                    }
+                    if (snd.total) S.xt_bc_send[l].push_back(std::move(snd));
+                    if (rcv.total) S.xt_bc_recv[l].push_back(std::move(rcv));
+                }
+            }
+        }
+    H->xt_ready = true;
+    return 0;
+}
+
 int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
 {
     HostStruct &hs = H->hs;

@@ -88,12 +88,28 @@ int slots_from_symb(Handle &H, const Symb &sy, const Grid &g, const int32_t *sn_
 // Planner: H.hs / H.grid / in -> value-arena layout, device tables, schedules, exchange plans; allocates the arena
 // (zero-filled) and uploads everything but the values.  `t` is left filled for the value producers.
 int plan_and_upload(Handle *H, SlotInput &in, HostTables &t);
+// the exchange lists of the transposed sweeps of an existing handle (LevelSched::xt_*; sets Handle::xt_ready): local, no communication, idempotent
+int plan_trans_exchange(Handle *H);
 
 // drivers (sluamd_factor.cpp)
 int run_factor(Handle *H, double thresh, int *info);
 int run_solve_dev(Handle *H, double *d_x, int64_t ldx, int nrhs);
 int run_solve_dist(Handle *H, double *d_b, int64_t ldb, int nrhs, int64_t m_loc, int64_t fst_row, const int *perm_in, const int *perm_out);   // B distributed by rows (pdReDistribute3d_B_to_X / X_to_B inside)
-int run_tsolve(Handle *H, bool conj, double *d_x, int64_t ldx, int nrhs);   // sluamd_tsolve.cpp: (L U)^T y = x / (L U)^H y = x in place, 1 x 1 x 1 handles (not in the CPU test build)
+int run_tsolve(Handle *H, bool conj, double *d_x, int64_t ldx, int nrhs);   // sluamd_tsolve.cpp: (L U)^T y = x / (L U)^H y = x in place; grids: replicated form, collective (not in the CPU test build)
+// The replicated solve of a multi-rank handle around two per-forest sweeps (sluamd_factor.cpp; run_solve_dev and run_tsolve are its two callers): per chunk of
+// right-hand sides b is kept at the rows that consume it, fwd runs on the forests leaves to root with the ancestors' partial sums (forest_runs role acc_role:
+// 0 = rows of my process row, 1 = of my process column) added into the partner layer, bwd root to leaves after the solved ancestors (role x_role) came down,
+// then the all-gather.  The bodies get the chunk's vector (ldx in values of the handle's precision) and ctx.
+struct GridSweepOps {
+    int (*fwd)(Handle *H, int z, double *x, int64_t ldx, int nr, void *ctx);
+    int (*bwd)(Handle *H, int z, double *x, int64_t ldx, int nr, void *ctx);
+    void *ctx;
+    int acc_role, x_role;
+};
+int run_grid_solve(Handle *H, double *d_x, int64_t ldx, int nrhs, const GridSweepOps &ops);
+// exchange of x segments with a set of peers on stream s (run lists and ldx in doubles): pack_mode 0 = pack, 3 = pack and clear; unpack_mode 1 = overwrite, 2 = accumulate
+int xseg_exchange(Handle *H, double *d_x, int64_t ldx, int nrhs, const std::vector<LevelSched::XSeg> &snd, int pack_mode,
+                  const std::vector<LevelSched::XSeg> &rcv, int unpack_mode, hipStream_t s);
 int run_solve_local(Handle *H, double *d_x, int64_t ldx, int nrhs);   // single-rank sweep over every schedule (refinement)
 int ensure_dinv(Handle *H);
 int ensure_inv(Handle *H);

@@ -87,7 +87,7 @@ template <bool Z> int trefine(sluamd_handle_t h, int trans, bool dev, const doub
 {
     Handle *H = &h->H;
     if (int rc = rfs_checks<TRfs<Z, false>>(H)) return rc;
-    if (H->grid.size() > 1) { set_error(std::string(name) + ": transposed refinement needs a 1 x 1 x 1 handle (the transposed sweeps of a grid need exchange plans of their own)"); return SLUAMD_EINVAL; }
+    if (H->grid.size() > 1 && !H->xt_ready) { set_error(std::string(name) + ": transposed refinement needs a 1 x 1 x 1 handle, or a grid handle after sluamd_PlanTransposedSweeps (the transposed sweeps of a grid need exchange plans of their own)"); return SLUAMD_EINVAL; }
     if (nrhs == 0) { if (steps) *steps = 0; return 0; }
     if (int rc = ensure_tindex(H, name)) return rc;
     if (Z && trans == SLUAMD_CONJ) return dev ? rfs_dev<TRfs<Z, true>>(h, B, ldb, X, ldx, nrhs, berr, steps) : rfs_host<TRfs<Z, true>>(h, B, ldb, X, ldx, nrhs, berr, steps);

@@ -205,6 +205,21 @@ def plan_table(h):
     return out[:rows.value]
 
 
+XLISTS = ("xs_red_send", "xs_red_recv", "xs_bc_send", "xs_bc_recv", "xt_red_send", "xt_red_recv", "xt_bc_send", "xt_bc_recv")
+
+
+def plan_xlists(h, which):
+    """this rank's x-segment exchange list `which` (a name of XLISTS: xs_* = the untransposed sweeps, xt_* = the transposed ones) as an int array of
+    rows (Z level, DAG level, peer, first row, rows), one per run in list order (sluamd_plan_xlists)"""
+    L = _lib.load()
+    w = XLISTS.index(which)
+    rows = C.c_int64(0)
+    _lib.check(L.sluamd_plan_xlists(h, w, None, 0, C.byref(rows)), "sluamd_plan_xlists")
+    out = np.zeros((max(rows.value, 1), 5), dtype=np.int32)
+    _lib.check(L.sluamd_plan_xlists(h, w, _pi(out), rows.value, C.byref(rows)), "sluamd_plan_xlists")
+    return out[:rows.value]
+
+
 class LUHandle:
     """Device-resident L/U (sluamd_handle_t): dCreateLUgpuHandle / pdgstrf3d_LUv1 / dCopyLUGPU2Host /
     dDestroyLUgpuHandle replacement (SRC/CplusplusFactor/LUgpuCHandle_interface_impl.cu:11-73)."""
@@ -283,7 +298,7 @@ class LUHandle:
 
     def pdgstrs3d(self, x, trans="N"):
         """pdgstrs3d, or pzgstrs3d on a complex16 handle.  trans = "T" / "C": the transposed / conjugate-transposed solve (L U)^T y = x,
-        (L U)^H y = x with the same factors (sluamd_p[dz]gstrs3d_trans; 1 x 1 x 1 handles)."""
+        (L U)^H y = x with the same factors (sluamd_p[dz]gstrs3d_trans)."""
         t = _trans_code(trans)
         x = np.asfortranarray(np.array(x, dtype=np.complex128 if self.z else np.float64))
         if x.ndim == 1:
@@ -342,7 +357,7 @@ class LUHandle:
     def pdgsrfs3d(self, b, x, trans="N"):
         """Iterative refinement of x (original ordering) for the attached matrix; returns (x, berr[nrhs], steps).
         pzgsrfs3d on a complex16 handle (complex b and x).  trans = "T" / "C": the transposed / conjugate-transposed system A^T x = b, A^H x = b of
-        the attached matrix (sluamd_p[dz]gsrfs3d_trans; 1 x 1 x 1 handles), x e.g. from pdgstrs3d(trans=...).  ValueError, before any library call:
+        the attached matrix (sluamd_p[dz]gsrfs3d_trans), x e.g. from pdgstrs3d(trans=...).  ValueError, before any library call:
         a trans other than "N", "T", "C"; b or x of another dtype than the handle's; shapes that differ or are not (n,) / (n, nrhs)."""
         return _gsrfs3d(self._h, self.z, b, x, trans, self.n)
 
@@ -615,7 +630,7 @@ def pivot_thresh(n, rowptr, colind, nzval):
 
 
 def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, replace_tiny=False, anorm=None,
-              keep=False, refine=False, trans="N", equil=False, rowperm=None, deterministic=False):
+              keep=False, refine=False, trans="N", equil=False, rowperm=None, deterministic=False, grid=None):
     """Solve A x = b -- trans = "T": A^T x = b, "C": A^H x = b, with the same factorisation of A -- through the GPU hot path: symbolic (host) -> device-resident distribute -> pdgstrf3d ->
     pdgstrs3d, with Equil = NO, RowPerm = NOROWPERM, ColPerm = MY_PERMC/NATURAL, IterRefine = NOREFINE
     (the timing configuration of BASELINE.md section 4); refine=True adds IterRefine = SLU_DOUBLE (pdgsrfs3d on the device;
@@ -628,10 +643,17 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
     attach_matrix; set_row_perm; factorisation and gssvx_solve with b and x in A's ordering.  `rowperm` = the matching's counters goes into the
     stats; a structurally singular A raises RuntimeError.  With keep=True the handle's update_values takes values in A's order.
     deterministic=True: the handle option of that name (bitwise reproducible factors).
+    grid=(Pr, Pc, Pz): the same on a process grid whose ranks are threads of this process over the in-process transport (grid3d.local_comms) -- every
+    rank holds the complete matrix and b, the calls are collective (replicated forms), rank 0's x, info and stats are returned; trans, equil and refine
+    as above; keep and rowperm are not part of this form (ValueError).
     Returns (x, info, stats[, handle, symb])."""
     if refine and _trans_code(trans):
         raise ValueError("refine=True with trans != 'N': not in this driver -- solve with refine=False and keep=True, then refine with "
                          "LUHandle.pdgsrfs3d(b, x, trans=...) on the attached matrix")
+    if grid is not None and tuple(grid) != (1, 1, 1):
+        if keep or rowperm is not None:
+            raise ValueError("pdgssvx3d(grid=...): keep=True and rowperm are not part of the grid form -- use grid3d.GridHandle directly")
+        return _gssvx3d_grid(n, rowptr, colind, nzval, b, perm_c, relax, maxsup, replace_tiny, anorm, refine, trans, equil, deterministic, tuple(grid))
     if rowperm is not None:
         if rowperm != "LargeDiag_MC64":
             raise ValueError(f"rowperm must be None or 'LargeDiag_MC64', not {rowperm!r}")
@@ -658,6 +680,55 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
         return x, info, st, h, symb
     h.destroy(); symb.free()
     return x, info, st
+
+
+def _gssvx3d_grid(n, rowptr, colind, nzval, b, perm_c, relax, maxsup, replace_tiny, anorm, refine, trans, equil, deterministic, grid):
+    """the grid=(Pr, Pc, Pz) path of pdgssvx3d: one thread per rank, replicated right-hand sides, every step collective"""
+    from . import grid3d
+    Pr, Pc, Pz = grid
+    symb = Symbolic(n, rowptr, colind, perm_c, relax, maxsup)
+    sn_tree = symb.partition(Pz) if Pz > 1 else None
+    comms = grid3d.local_comms(Pr, Pc, Pz)
+    b = np.asfortranarray(np.array(b, dtype=np.complex128 if np.iscomplexobj(nzval) else np.float64))
+    if b.ndim == 1:
+        b = np.asfortranarray(b[:, None])
+
+    def body(rank):
+        h = grid3d.GridHandle.from_symbolic(symb, nzval, comms[rank], sn_tree, replace_tiny=replace_tiny, deterministic=deterministic)
+        try:
+            extra = {}
+            if _trans_code(trans):
+                h.plan_transposed()
+            if equil:
+                eq = h.equilibrate(n, rowptr, colind, nzval, symb.perm_c)
+                info = h.pdgstrf3d(0.5 * float(np.finfo(np.float32).eps) * eq["anorm"])
+                out = h.gssvx_solve(b, trans=trans, refine=refine)
+                extra.update(equed=eq["equed"], rowcnd=eq["rowcnd"], colcnd=eq["colcnd"], amax=eq["amax"])
+                if eq["info"] > 0:
+                    extra["equil_info"] = eq["info"]
+                x = out
+                if refine:
+                    x, extra["berr"], extra["refine_steps"] = out
+            else:
+                info = h.pdgstrf3d(pivot_thresh(n, rowptr, colind, nzval) if anorm is None else 0.5 * float(np.finfo(np.float32).eps) * anorm)
+                xp = np.zeros_like(b, order="F")
+                xp[symb.perm_c, :] = b
+                x = np.asfortranarray(h.pdgstrs3d(xp, trans=trans)[symb.perm_c, :])
+                if refine:
+                    h.attach_matrix(n, rowptr, colind, nzval, symb.perm_c)
+                    x, extra["berr"], extra["refine_steps"] = h.pdgsrfs3d(b, x)
+            st = h.stats()
+            st.update(extra)
+            return x, info, st
+        finally:
+            h.destroy()
+
+    try:
+        out = grid3d.run_ranks(Pr * Pc * Pz, body)
+    finally:
+        symb.free()
+    x, _, st = out[0]
+    return x, max(o[1] for o in out), st
 
 
 def _gssvx3d_rowperm(n, rowptr, colind, nzval, b, perm_c, relax, maxsup, replace_tiny, keep, refine, trans, equil, deterministic):

@@ -131,6 +131,15 @@ class GridHandle:
         from .driver import plan_table
         return plan_table(self._h)
 
+    def plan_transposed(self):
+        """sluamd_PlanTransposedSweeps: plan the exchange lists of the transposed sweeps on this rank (local, no communication, idempotent).  Every rank of the
+        grid calls it before the first pdgstrs3d / pdgsrfs3d / gssvx_solve with trans = "T" / "C"; a handle that never did refuses those with RuntimeError."""
+        _lib.check(_lib.load().sluamd_PlanTransposedSweeps(self._h), "sluamd_PlanTransposedSweeps")
+
+    def plan_xlists(self, which):
+        from .driver import plan_xlists
+        return plan_xlists(self._h, which)
+
     @classmethod
     def from_store(cls, store, forests, comm, **opts):
         from .driver import LUHandle, _forest_view
@@ -171,13 +180,20 @@ class GridHandle:
         _lib.check((L.sluamd_pzgstrf3d if self.z else L.sluamd_pdgstrf3d)(self._h, float(thresh), C.byref(info)), "sluamd_p[dz]gstrf3d")
         return info.value
 
-    def pdgstrs3d(self, xp):
-        """xp: complete permuted right-hand side (n x nrhs), replicated; returns the complete solution."""
+    def pdgstrs3d(self, xp, trans="N"):
+        """xp: complete permuted right-hand side (n x nrhs), replicated; returns the complete solution.  trans = "T" / "C": the transposed /
+        conjugate-transposed solve (L U)^T y = xp, (L U)^H y = xp with the same factors, collective like the untransposed one (sluamd_p[dz]gstrs3d_trans;
+        after plan_transposed() on every rank)."""
+        from .driver import _trans_code
+        t = _trans_code(trans)
         x = np.asfortranarray(np.array(xp, dtype=np.complex128 if self.z else np.float64))
         if x.ndim == 1:
             x = np.asfortranarray(x[:, None])
         L = _lib.load()
-        if self.z:
+        if t:
+            name = "sluamd_pzgstrs3d_trans" if self.z else "sluamd_pdgstrs3d_trans"
+            _lib.check(_lib.entry(name)(self._h, t, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1]), name)
+        elif self.z:
             _lib.check(L.sluamd_pzgstrs3d(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1]), "sluamd_pzgstrs3d")
         else:
             _lib.check(L.sluamd_pdgstrs3d(self._h, x.ctypes.data_as(_lib.P_dbl), x.shape[0], x.shape[1]), "sluamd_pdgstrs3d")
@@ -204,11 +220,12 @@ class GridHandle:
         from .driver import _attach_matrix
         _attach_matrix(self._h, self.z, n, rowptr, colind, nzval, perm_c)
 
-    def pdgsrfs3d(self, b, x):
+    def pdgsrfs3d(self, b, x, trans="N"):
         """Iterative refinement, replicated form (collective): the complete b and initial x (original ordering) on every rank;
-        returns (the complete refined x, berr[nrhs], steps) -- the same on every rank.  pzgsrfs3d on a complex16 handle."""
+        returns (the complete refined x, berr[nrhs], steps) -- the same on every rank.  pzgsrfs3d on a complex16 handle.
+        trans = "T" / "C": the system A^T x = b / A^H x = b of the attached matrix (sluamd_p[dz]gsrfs3d_trans; after plan_transposed()), with LUHandle.pdgsrfs3d's argument checks."""
         from .driver import _gsrfs3d
-        return _gsrfs3d(self._h, self.z, b, x)
+        return _gsrfs3d(self._h, self.z, b, x, trans, self.n)
 
     pzgsrfs3d = pdgsrfs3d
 
@@ -224,7 +241,7 @@ class GridHandle:
 
     def gssvx_solve(self, b, trans="N", refine=False):
         """The expert driver's solve phase, replicated form (collective): the complete b in the original ordering and scaling on every
-        rank -> the complete x (sluamd_p[dz]gssvx3d_solve); refine=True returns (x, berr, steps)."""
+        rank -> the complete x (sluamd_p[dz]gssvx3d_solve); trans = "T" / "C": A^T x = b / A^H x = b (after plan_transposed()); refine=True (trans = "N" only) returns (x, berr, steps)."""
         from .driver import _gssvx_solve
         return _gssvx_solve(self._h, self.z, b, trans, refine)
 
