@@ -510,7 +510,6 @@ int run_factor(Handle *H, double thresh, int *info)
     HIPCHK(hipStreamSynchronize(H->stream));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev0, H->ev1));
     H->st.t_factor_ms = ms;
-    if (getenv("SLUAMD_EXP_COUNT")) fprintf(stderr, "[sluamd] K chunks of the Schur tiles (instrumented kernel build only): 128 x 128 clean %d other %d; 64 x 64 clean %d other %d\n", res[4], res[5], res[6], res[7]);
     H->dinv_ready = true; H->inv_ready = !H->env.trsm_panels && !H->z; H->factored = true;
     if (H->profile && H->env.profile_dump && H->schur_rec.size() == H->ev_schur_used)
         for (size_t i = 0; i < H->ev_schur_used; ++i) {

@@ -34,12 +34,8 @@ __device__ __forceinline__ int find_node(const int *__restrict__ prefix, int nn,
 
 // The same search by a whole wave -- id wave-uniform, all 64 lanes active (kernel entry): 64 probes per round trip instead of one.  The kernels of a
 // latency-bound level start with this search; a binary search over a level of 16 supernodes is four dependent loads, over a leaf level of 9 000 fourteen.
-#ifndef SLUAMD_FIND_WAVE
-#define SLUAMD_FIND_WAVE 1
-#endif
 __device__ __forceinline__ int find_node_wave(const int *__restrict__ prefix, int nn, int id)
 {
-#if SLUAMD_FIND_WAVE
     const int lane = threadIdx.x & 63;
     int lo = 0, hi = nn;                             // prefix[lo] <= id < prefix[hi]
     while (hi - lo > 1) {
@@ -51,9 +47,6 @@ __device__ __forceinline__ int find_node_wave(const int *__restrict__ prefix, in
         hi = min(hi, lo + stride);
     }
     return __builtin_amdgcn_readfirstlane(lo);
-#else
-    return find_node(prefix, nn, id);
-#endif
 }
 
 __device__ __forceinline__ void atomic_sub_f64(double *p, double v)
@@ -1376,8 +1369,8 @@ __global__ __launch_bounds__(256) void k_rfs_update(int n, const int *__restrict
 // MFMAs of the current chunk run out of the other LDS buffer (one barrier per chunk).
 // the MFMAs of one K chunk for a wave that owns RA x CA 16 x 16 blocks
 typedef const volatile double __attribute__((address_space(3))) *lds_vdouble_t;
-// USW: the U stage in the swizzled column-major form (see k_schur): `pa` is the lane's index for k4 = 0, column block 0
-template <int RA, int CA, int LDL, int LDU, bool USW>
+// W16 (real arithmetic, see k_schur): the U stage in the swizzled column-major form, `pa` is the lane's index for k4 = 0, column block 0; otherwise (complex) k-major, leading dimension LDU
+template <int RA, int CA, int LDL, int LDU, bool W16>
 __device__ __forceinline__ void schur_chunk(const double *Lb, const double *Ub, int rm0, int cn0, int lane, d4 (&acc)[CA][RA], int pa)
 {
 #pragma unroll
@@ -1385,11 +1378,11 @@ __device__ __forceinline__ void schur_chunk(const double *Lb, const double *Ub, 
         const int kr = k4 + (lane >> 4);
         double a[CA], b[RA];
 #pragma unroll
-        for (int c = 0; c < CA; ++c) a[c] = USW ? ((lds_vdouble_t) Ub)[(pa ^ k4) + 256 * c] : Ub[kr * LDU + cn0 + 16 * c + (lane & 15)];
+        for (int c = 0; c < CA; ++c) a[c] = W16 ? ((lds_vdouble_t) Ub)[(pa ^ k4) + 256 * c] : Ub[kr * LDU + cn0 + 16 * c + (lane & 15)];
         // (volatile: single ds_read_b64 -- two lane groups of 32 over 64 banks, 2 LDS cycles -- instead of the merged ds_read2[st64]_b64, whose 16-lane groups over 32
         //  banks take 8 cycles and see the swizzled columns 2-way conflicted)
 #pragma unroll
-        for (int r = 0; r < RA; ++r) b[r] = USW ? ((lds_vdouble_t) Lb)[kr * LDL + rm0 + 16 * r + (lane & 15)] : Lb[kr * LDL + rm0 + 16 * r + (lane & 15)];
+        for (int r = 0; r < RA; ++r) b[r] = W16 ? ((lds_vdouble_t) Lb)[kr * LDL + rm0 + 16 * r + (lane & 15)] : Lb[kr * LDL + rm0 + 16 * r + (lane & 15)];
 #pragma unroll
         for (int c = 0; c < CA; ++c)
 #pragma unroll
@@ -1397,28 +1390,6 @@ __device__ __forceinline__ void schur_chunk(const double *Lb, const double *Ub, 
     }
 }
 
-// Instrumentation switches of the epilogue decomposition (scripts/ab_epilogue.sh builds the variants; the product build never sets them):
-//   SLUAMD_EXP_EPI    2 = the product's epilogue (one fp64 atomic per updated element), 1 = plain load-subtract-store (racy between concurrent
-//                     sources of one destination: timing only), 0 = no scatter at all (the accumulators are kept alive by an impossible branch)
-//   SLUAMD_EXP_NOLOAD 1 = the K loop's operands are constants: no global loads between the prologue and the epilogue (LDS stores, reads, barriers, MFMAs stay)
-#ifndef SLUAMD_EXP_EPI
-#define SLUAMD_EXP_EPI 2
-#endif
-#ifndef SLUAMD_EXP_NOLOAD
-#define SLUAMD_EXP_NOLOAD 0
-#endif
-//   SLUAMD_EXP_VALU   N > 0: N extra dependent-free integer VALU instructions per K chunk and wave beside the loader (is ordinary VALU work hidden behind the other
-//                     waves' fp64 MFMAs, or does it add to them?); SLUAMD_EXP_VALU_MID: the same instructions spread between the MFMA groups of the chunk
-#ifndef SLUAMD_EXP_VALU
-#define SLUAMD_EXP_VALU 0
-#endif
-#ifndef SLUAMD_SCHUR_FETCH2
-#define SLUAMD_SCHUR_FETCH2 1     // 0: the loader of rounds 1-5 (kept for the same-box A/B)
-#endif
-// a pointer every lane holds alike, moved to SGPRs so that loads take the (SGPR base + 32-bit VGPR offset) form
-#ifndef SLUAMD_SCHUR_FETCH3
-#define SLUAMD_SCHUR_FETCH3 1     // the loader in 16-byte loads (two tile rows of one panel column / two k of one U column per lane): half the load instructions,
-#endif                            // map reads and predicates of SLUAMD_SCHUR_FETCH2; 0: that loader
 // raw buffer loads: address = 48-bit base of a wave-uniform resource descriptor (4 SGPRs) + 32-bit per-lane byte offset (VGPR) + 32-bit wave-uniform byte offset
 // (SGPR): no 64-bit vector arithmetic in front of the load
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -1443,29 +1414,12 @@ __device__ __forceinline__ void lds_dma_16(i32x4 rsrc, uint32_t lds_byte, int vo
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voffset), "s"(rsrc), "s"(soffset), "s"(lds_byte) : "memory");
 }
-#ifdef SLUAMD_EXP_NODMAWAIT      // (instrumented build: nobody waits for the LDS-DMA loads -- wrong factors, timing only)
-__device__ __forceinline__ void lds_dma_wait() { asm volatile("" ::: "memory"); }
-#else
 __device__ __forceinline__ void lds_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-#endif
 __device__ __forceinline__ uint32_t lds_byte_addr(const void *p) { return (uint32_t) (uintptr_t) (__attribute__((address_space(3))) const void *) p; }
-#ifndef SLUAMD_SCHUR_TOUCH
-#define SLUAMD_SCHUR_TOUCH 0      // 1: one chunk before the last, a tile touches its destination lines (rounds 2-5; at the 128-VGPR cap of the round-6 kernel the two touched
-                                  // values are spilled, i.e. waited for at once: 265.6 ms); 2: the touch as loads into an LDS sink (262.2 ms); 0: none (259.6 ms, profiles/r06_ab_dma_loader.txt)
-#endif
-#ifndef SLUAMD_SCHUR_TIGHT
-#define SLUAMD_SCHUR_TIGHT 1      // the full chunks of a clean source of the LDS-DMA configurations run in a loop of their own (0: inside the general pipeline; same-box A/B)
-#endif
-#ifndef SLUAMD_SCHUR_DMA
-#define SLUAMD_SCHUR_DMA 1        // clean sources of the 128-row tile configurations load their chunks straight into the LDS stage; 0: through registers (same-box A/B)
-#endif
-#ifndef SLUAMD_SCHUR_CLEAN
-#define SLUAMD_SCHUR_CLEAN 1      // the predicate-free loader for clean sources (see `clean` in k_schur); 0: fetch3 / stash3 everywhere (same-box A/B)
-#endif
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef const d2 __attribute__((address_space(1), aligned(8))) *gd2_t;      // (the pairs are 8-byte aligned only: panel leading dimensions and segment offsets are arbitrary)
 typedef const char __attribute__((address_space(1))) *gbytes_t;     // (global address space kept through the integer round trip: global_load, not flat_load)
-typedef const double __attribute__((address_space(1))) *gdouble_t;
+// a pointer every lane holds alike, moved to SGPRs so that loads take the (SGPR base + 32-bit VGPR offset) form
 __device__ __forceinline__ gbytes_t uniform_ptr(const double *p)
 {
     const uint64_t v = (uint64_t) p;
@@ -1494,25 +1448,30 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
                                                                     const int *__restrict__ tmaps, const int *__restrict__ xoff)
 {
     constexpr int LDL = TMv + 16;   // == 16 mod 32 doubles: conflict-free ds_read_b64 fragment reads
-    constexpr int LDU = TNv + 17;   // odd: the k-major U stash (16 lanes x stride LDU) spreads over all banks too
+    constexpr int LDU = TNv + 17;   // complex loader only -- odd: the k-major U stash (16 lanes x stride LDU) spreads over all banks too
     constexpr int NT = NW * 64;                         // threads per workgroup
     constexpr int WR = (NW == 8) ? 4 : 2, WC = 2;       // wave grid (rows x cols): 4 waves = 2x2, 8 waves = 4x2
     constexpr int NBR = TMv / (16 * WR), NBC = TNv / (16 * WC);   // 16x16 MFMA blocks per wave (rows, cols)
-    constexpr int LQ = TMv * KC / NT, UQ = TNv * KC / NT;         // prefetch registers per thread
-    constexpr int LKS = NT / TMv;                       // k stride of the L loader
-    constexpr int UJS = NT / 16;                        // column stride of the U loader
+    constexpr int LQ = TMv * KC / NT, UQ = TNv * KC / NT;         // complex loader: prefetch registers per thread
+    constexpr int LKS = NT / TMv;                       //   k stride of the L loads
+    constexpr int UJS = NT / 16;                        //   column stride of the U loads
     constexpr int ZS = Z ? 2 : 1;                       // doubles per value: arena offsets and tile rows of the tables are in values
     static_assert(!Z || (LKS % 2 == 0 && KC % 2 == 0), "complex L loader: the parity of a thread's k must be constant");
     // 128 x 128 tiles: two LDS stages (one barrier per chunk).  64 x 64 tiles -- the bottom of the tree, short K loops, the tile's
     // life is dependent index loads -- trade the second stage for occupancy: 24 KB instead of 44 KB per workgroup
     constexpr int NBUF = (TMv == 64 && SCHUR64_WGS > 4) ? 1 : 2;
-    __shared__ double Ls[NBUF][KC * LDL];
-    // U stage.  USW (the 16-byte loader, real arithmetic): column-major in 16-byte slots -- column c, k pair kp at doubles c * 16 + 2 * (kp ^ ((c >> 1) & 7)) -- so that a
+    // (both stages take 16-byte stores and LDS-DMA writes: their bases and every row of them are 16-byte aligned by declaration, not by their place among the arrays)
+    __shared__ __attribute__((aligned(16))) double Ls[NBUF][KC * LDL];
+    static_assert((LDL * sizeof(double)) % 16 == 0, "L stage: every k row starts on a 16-byte boundary (d2 stores, LDS-DMA)");
+    // Two operand loaders, chosen by the arithmetic alone.  W16 (real): 16-byte loads -- fetch3 / stash3, and for clean sources fetch_clean / stash_clean (below).
+    // Complex: 8-byte loads with predicates, fetch_z / stash_z; only its L loads differ from a real loader's (the embedding above).
+    constexpr bool W16 = !Z;
+    // U stage.  W16: column-major in 16-byte slots -- column c, k pair kp at doubles c * 16 + 2 * (kp ^ ((c >> 1) & 7)) -- so that a
     // thread's loaded pair (two k of one column) is ONE 16-byte store, a wave's 64 pairs (8 columns x 8 pairs) are 1 KiB in lane order (what a load straight into
-    // LDS writes), and the MFMA fragment reads (16 lanes = 16 columns of one k) fall on 16 different slots of a 256-byte window (the XOR); otherwise k-major, padded
-    constexpr bool USW = SLUAMD_SCHUR_FETCH3 && !Z;
-    __shared__ __attribute__((aligned(16))) double Us[NBUF][USW ? KC * TNv : KC * LDU];
-    auto uidx = [](int k, int c) { return USW ? c * 16 + ((((k >> 1) ^ ((c >> 1) & 7)) << 1) | (k & 1)) : k * LDU + c; };
+    // LDS writes), and the MFMA fragment reads (16 lanes = 16 columns of one k) fall on 16 different slots of a 256-byte window (the XOR); complex: k-major, padded
+    __shared__ __attribute__((aligned(16))) double Us[NBUF][W16 ? KC * TNv : KC * LDU];
+    static_assert((KC * sizeof(double)) % 16 == 0, "U stage (W16): a column is KC = 16 doubles, every column starts on a 16-byte boundary (d2 stores, LDS-DMA)");
+    auto uidx = [](int k, int c) { return W16 ? c * 16 + ((((k >> 1) ^ ((c >> 1) & 7)) << 1) | (k & 1)) : k * LDU + c; };
     __shared__ int s_ind[256 + 8];
     __shared__ int s_rowmap[TMv];
     __shared__ int s_colmap[TNv];
@@ -1522,7 +1481,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
     __shared__ int s_lead2[TNv];
     __shared__ int s_jj[TNv];     // column id inside supernode jb
     __shared__ int s_dinfo[1];
-    __shared__ int s_sink[(SLUAMD_SCHUR_TOUCH == 2 && TMv == 128) ? NW * 64 : 1];     // destination of the touch loads of the LDS-DMA configurations
     constexpr int HDR = 64;                          // header ints of a tile record: [0,16) the tile itself, [16] number of K-fused predecessors, [17 + 11 j, 28 + 11 j) predecessor j (nearest first)
     __shared__ int s_hdr[HDR];
     constexpr int REC = HDR + TMv + 3 * TNv;         // ints per tile record (MM 1 / 2)
@@ -1689,7 +1647,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
             else { di0 = T.ub_iukp[dblk]; dbase = ZS * T.sn_uval[ib]; }
         }
         // ---- destination maps (tile row / column -> offset inside the destination panel / U row), before the K loop: the first
-        // source fetch is in flight behind these index loads, and the lines can be touched ahead of the scatter ----
+        // source fetch is in flight behind these index loads ----
         dst = T.val + dbase;
         if (has_dst && !merged) {
             if (ib >= jb) {
@@ -1754,7 +1712,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
     int nprev = 0;
     if (MM == 2) nprev = Z ? 0 : s_hdr[16];
     else if (!Z && T.fuse_prev) { while (nprev < 3 && T.fuse_prev[3 * k + nprev] >= 0) ++nprev; }
-    double touch0 = 0.0, touch1 = 0.0;
 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     // a wave whose 32 x 64 (32 x 32) part lies entirely outside a ragged tile skips its MFMAs: the MFMA pipe is the resource
@@ -1770,34 +1727,39 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
 #pragma unroll
         for (int b = 0; b < NBR; ++b) acc[a][b] = (d4){0.0, 0.0, 0.0, 0.0};
 
-    const int li = tid % TMv, lk = tid / TMv;           // L loader: row li, k = lk + LKS*q
-    const int uk = tid & 15, uj = tid >> 4;             // U loader: k = uk, col = uj + UJS*q
-    double pl[LQ], pu[UQ];
+    // per-source state of the K loop, both loaders (source 0 ... nprev - 1 = the K-fused predecessors, the last source = k itself); ns_s counts REAL k (2 per complex one)
     const int *cpS = s_cptr, *ldS = s_lead;   // column maps of the current source (LDS): re-read per chunk, registers are scarce
-    bool lrow_ok = li < nr;
-    // complex L loader: real row li = (panel row li / 2, part a), the thread's k all have parity b = lk & 1: it reads part a ^ b,
-    // negated for (a, b) = (0, 1)
-    const int zoff = Z ? ((li ^ lk) & 1) : 0;
-    const double zsgn = (Z && !(li & 1) && (lk & 1)) ? -1.0 : 1.0;
-    const int lrow0 = Z ? (li & ~1) + zoff : li;
-    // per-source state of the K loop (source 0 = fused predecessor ka, source 1 = k itself); ns_s counts REAL k (2 per complex one)
     int ns_s = ZS * ns, lda_s = lda;
-    const double *Lrow = Lp + lrow0, *Uvs = Uv;
-    const double *Lsrc = Lp;                              // SLUAMD_SCHUR_FETCH2: the source panel's base (uniform) and this thread's byte offset from it
-    uint32_t lvo = (uint32_t) (lrow0 + lk * lda) << 3;    //   (row of the tile + its k phase; a slot is far below 2^29 values)
-    // SLUAMD_SCHUR_FETCH3: thread = (pair of tile rows 2 li2, 2 li2 + 1; panel column lk3 + LKS3 q) and (pair of k 2 uk2, 2 uk2 + 1; tile column uj3 + UJS3 q)
-    constexpr bool F3 = SLUAMD_SCHUR_FETCH3 && !Z;
-    constexpr int LRP = TMv / 2, LKS3 = NT / LRP, LQ3 = KC / LKS3, UJS3 = NT / 8, UQ3 = TNv / UJS3;
-    const int li2 = tid % LRP, lk3 = tid / LRP, uk2 = tid & 7, uj3 = tid >> 3;
+    const double *Uvs = Uv;
+
+    // ---- complex loader's state (Z only; a complex tile has no K-fused predecessors: its only source is k) ----
+    // thread = (real row li; k = lk + LKS q) and (k = uk; tile column uj + UJS q), one 8-byte load each
+    const int li = tid % TMv, lk = tid / TMv;
+    const int uk = tid & 15, uj = tid >> 4;
+    double pl[LQ], pu[UQ];                    // the prefetched chunk
+    const bool lrow_ok = li < nr;
+    // real row li = (panel row li / 2, part a), the thread's k all have parity b = lk & 1: it reads part a ^ b, negated for (a, b) = (0, 1)
+    const int zoff = (li ^ lk) & 1;
+    const double zsgn = (!(li & 1) && (lk & 1)) ? -1.0 : 1.0;
+    const double *Lrow = Lp + (li & ~1) + zoff;
+
+    // ---- 16-byte loader's state (W16 only) ----
+    // thread = (pair of tile rows 2 li2, 2 li2 + 1; panel column lk3 + LKS3 q) and (pair of k 2 uk2, 2 uk2 + 1; tile column uj3 + UJS3 q): half the load instructions,
+    // map reads and predicates of one 8-byte load per element.  What the K loop pays for is the ISSUE cost of its loader, not the latency of its loads
+    // (profiles/r06_ab_schur_epilogue.txt: no loads at all -36 ms in the steady state, the same loads served by L1 / L2 / MALL -6 ... -4 ms).
     // (Measured and not kept, profiles/r06_ab_*.txt: a SECOND register set in flight -- 0 ms in the 4-wave configuration with 256 VGPRs, spills and +35 ms at this
     //  configuration's 128-VGPR cap; ONE software pipeline across the K-fused sources with all their maps staged in LDS up front -- 0 ms; s_setprio around the MFMA
-    //  phase -- 0 ms; the scatter's maps read in one batch -- 0 ms.  What the K loop paid for was the ISSUE cost of its loader.)
-    d2 wl[F3 ? LQ3 : 1], wu[F3 ? UQ3 : 1];        // the raw 16-byte loads; zeros / halves are selected at the stash, when they have arrived
-    bool un0[F3 ? UQ3 : 1], un1[F3 ? UQ3 : 1];    // per U load: element k / k + 1 is a stored one (at or below the column's leading zeros, inside the source)
-    // per source: which of the two rows exist there (own source: inside the tile; a K-fused predecessor: present in its panel), the byte offset of the first
-    // existing one, and -- rows that are not neighbours in a predecessor's panel (its blocks may come in another order) -- the second one's own offset
+    //  phase -- 0 ms; the scatter's maps read in one batch -- 0 ms; touching the destination lines one chunk ahead of the scatter -- +6.0 ms as plain loads at the
+    //  128-VGPR cap, +2.6 ms as loads into an LDS sink, profiles/r06_ab_dma_loader.txt.)
+    const double *Lsrc = Lp;                      // the source panel's base (uniform)
+    constexpr int LRP = TMv / 2, LKS3 = NT / LRP, LQ3 = KC / LKS3, UJS3 = NT / 8, UQ3 = TNv / UJS3;
+    const int li2 = tid % LRP, lk3 = tid / LRP, uk2 = tid & 7, uj3 = tid >> 3;
+    d2 wl[W16 ? LQ3 : 1], wu[W16 ? UQ3 : 1];      // the raw 16-byte loads; zeros / halves are selected at the stash, when they have arrived
+    bool un0[W16 ? UQ3 : 1], un1[W16 ? UQ3 : 1];  // per U load: element k / k + 1 is a stored one (at or below the column's leading zeros, inside the source)
+    // per source: which of the two rows exist there (own source: inside the tile; a K-fused predecessor: present in its panel) and the byte offset of the first
+    // existing one
     bool l_has0 = 2 * li2 < nr, l_has1 = 2 * li2 + 1 < nr;
-    bool lon[F3 ? LQ3 : 1];                       // per L load: its panel column lies inside the source
+    bool lon[W16 ? LQ3 : 1];                      // per L load: its panel column lies inside the source
     uint32_t lvo3 = (uint32_t) (2 * li2 + lk3 * lda) << 3;
     // (two rows that both exist in a predecessor's panel are neighbours there: the planner only fuses pairs whose row map is monotone, build_pair_maps)
     bool rows_ok3 = true;                         // this thread's pair of tile rows is one 16-byte run of the source panel (or lies outside the tile): see `clean`
@@ -1807,8 +1769,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
         const bool p0 = 2 * li2 < nr, p1 = 2 * li2 + 1 < nr;
         rows_ok3 = !p0 || (l_has0 && (!p1 || ra1 == ra0 + 1));
     };
-    // Every load is UNCONDITIONAL (a lane with nothing to fetch reads the first 16 bytes of the source instead): no exec-mask branches, no zero initialisation of
-    // the destination registers -- which the compiler guards with s_waitcnt vmcnt(0), i.e. with the arrival of the loads issued just before
+    // Every load is UNCONDITIONAL (a lane with nothing to fetch reads the first 16 bytes of the source instead; profiles/r06_ab_fetch3.txt): no exec-mask branches, no zero initialisation of
+    // the destination registers -- which the compiler guards with s_waitcnt vmcnt(0), i.e. with the arrival of the loads issued just before.  A pair of which only
+    // the first element exists is still one 16-byte load: it reads one double past what it uses (past the source's value slot when the pair is the slot's last);
+    // the stash drops it (exact test: the `last_slot` case of tests/schur_cases.py)
     auto fetch3 = [&](int k0) {
         const gbytes_t Lb0 = uniform_ptr(Lsrc), Ub0 = uniform_ptr(Uvs);
 #pragma unroll
@@ -1846,7 +1810,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
         }
     };
 
-    // ---- the CLEAN form of the loader (round 6, profiles/r06_ab_valu_additive.txt) ----
+    // ---- the CLEAN form of the 16-byte loader (profiles/r06_ab_valu_additive.txt) ----
     // On this device the fp64 MFMA runs at the vector ALU's rate and SHARES it: every ordinary VALU instruction of a wave adds its cycles to the MFMA time of its
     // SIMD instead of hiding behind the other waves' MFMAs (32 / 96 extra v_add_u32 per chunk and wave: +7.4 / +20.5 ms on the 247 ms of all Schur launches = 0.22 ms
     // per instruction).  The loader above is ~80 VALU instructions per chunk (predicates, selects, 64-bit address arithmetic).  A source is CLEAN for a tile when no
@@ -1855,7 +1819,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
     // offsets fixed per source, the chunk's advance in the wave-uniform (SGPR) base, plain stores into the stage.  Rows >= nr / columns >= nc of a ragged tile hold
     // whatever their (valid) addresses hold: they only reach accumulators that are never scattered.  Partial chunks and unclean sources take fetch3 / stash3.
     bool clean = false;
-    uint32_t uvoc[F3 ? UQ3 : 1];                 // per U load: byte offset of (column, first k of this thread's pair) from the source's U base at k = kbeg0
+    uint32_t uvoc[W16 ? UQ3 : 1];                // per U load: byte offset of (column, first k of this thread's pair) from the source's U base at k = kbeg0
     int kbeg0 = 0;
     bool cur_fast = false;                       // the chunk in the registers was fetched by fetch_clean
     i32x4 rsL = {0, 0, 0, 0}, rsU = {0, 0, 0, 0};     // resource descriptors of the current source's panel / U row block (SGPRs; set by source_clean)
@@ -1875,15 +1839,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
         // (32-bit offsets: a panel / a U row block is far below 4 GB -- 300^3: 9e4 rows x 256 columns x 8 bytes)
         if (clean) { rsL = buffer_rsrc(Lsrc); rsU = buffer_rsrc(Uvs); }
     };
-    constexpr bool DMA = F3 && TMv == 128 && NBUF == 2 && SLUAMD_SCHUR_DMA && SLUAMD_SCHUR_CLEAN;
+    // DMA: the 128-row tile configurations load a clean source's chunks straight into the LDS stage (lds_dma_16); the 64 x 64 one stages them through registers
+    constexpr bool DMA = W16 && TMv == 128 && NBUF == 2;
     static_assert(!DMA || (LRP == 64 && UJS3 * UQ3 == TNv), "LDS-DMA loader: one panel column / eight tile columns per wave and load");
     auto fetch_clean = [&](int k0, int tb) {
-#ifdef SLUAMD_EXP_NOWAIT      // (instrumented build: the loads are issued, their data is never waited for at the stash -- it is "used" here, a whole chunk later; the stage gets constants)
-#pragma unroll
-        for (int q = 0; q < LQ3; ++q) asm volatile("" :: "v"(wl[q]));
-#pragma unroll
-        for (int q = 0; q < UQ3; ++q) asm volatile("" :: "v"(wu[q]));
-#endif
         if (DMA) {
             // the stage `tb` is free: every wave is past the MFMAs that read it (the barrier that closed the previous chunk / the previous source)
 #pragma unroll
@@ -1902,19 +1861,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
     };
     auto stash_clean = [&](int buf) {
         if (DMA) { lds_dma_wait(); return; }          // (the loads wrote the stage themselves)
-#ifdef SLUAMD_EXP_NOSTASH     // (instrumented build, with SLUAMD_EXP_NOWAIT: no stores into the stage either -- what the five LDS writes per chunk cost)
-        return;
-#endif
-#ifdef SLUAMD_EXP_NOWAIT
-        const d2 cst = {1.0 + 1e-9 * tid, 1.0 - 1e-9 * tid};
-#pragma unroll
-        for (int q = 0; q < LQ3; ++q) *(d2 *) &Ls[buf][(lk3 + LKS3 * q) * LDL + 2 * li2] = cst;
-#pragma unroll
-        for (int q = 0; q < UQ3; ++q) {
-            *(d2 *) &Us[buf][(uj3 + UJS3 * q) * 16 + 2 * uk2] = cst;
-        }
-        return;
-#endif
 #pragma unroll
         for (int q = 0; q < LQ3; ++q) *(d2 *) &Ls[buf][(lk3 + LKS3 * q) * LDL + 2 * li2] = wl[q];
 #pragma unroll
@@ -1923,95 +1869,41 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
         }
     };
 
-    auto fetch_into = [&](double *pl, double *pu, int k0, bool restart = false) {
-#if SLUAMD_EXP_NOLOAD
-        // 1: no loads at all; 2: none at the (re)start of a source's pipeline only; 3: none in the steady state only
-        if (SLUAMD_EXP_NOLOAD == 1 || (SLUAMD_EXP_NOLOAD <= 3 && (SLUAMD_EXP_NOLOAD == 2) == restart)) {
-#pragma unroll
-            for (int q = 0; q < LQ; ++q) pl[q] = 1.0 + 1e-9 * (k0 + q);
-#pragma unroll
-            for (int q = 0; q < UQ; ++q) pu[q] = 1.0 - 1e-9 * (k0 + q);
-            return;
-        }
-#endif
-#if SLUAMD_SCHUR_FETCH2
-        if (!Z) {
-            // Round 6: the loader's issue cost, not the latency of its loads, is what the K loop pays for (profiles/r06_ab_schur_epilogue.txt: no loads at all
-            // -36 ms in the steady state, the same loads served by L1 / L2 / MALL -6 ... -4 ms, a second register set in flight 0 ms): the compiler's form was four
-            // 64-bit multiply-adds for the L addresses and, per U column, TWO dependent LDS round trips (leading zeros -> branch -> value offset) before each load,
-            // serialised by exec-mask branches -- ~1000 cycles per chunk in which the wave issues no MFMA.  Here: wave-uniform 64-bit bases in SGPRs (the panel
-            // column k0 + LKS q is a scalar multiply), one 32-bit byte offset per thread, all eight map entries read by one batch of LDS loads.
-            const gbytes_t Lb0 = uniform_ptr(Lsrc), Ub0 = uniform_ptr(Uvs);
-#pragma unroll
-            for (int q = 0; q < LQ; ++q) {
-                const int kq = k0 + LKS * q;                                   // uniform
-                const gbytes_t sb = Lb0 + ((uint64_t) kq * (uint64_t) lda_s << 3);   // uniform: SALU
-                pl[q] = (lrow_ok && kq + lk < ns_s) ? *(gdouble_t) (sb + (uint64_t) lvo) : 0.0;
-            }
-            int ldq[UQ], cpq[UQ];
-#pragma unroll
-            for (int q = 0; q < UQ; ++q) { ldq[q] = ldS[uj + UJS * q]; cpq[q] = cpS[uj + UJS * q]; }
-#pragma unroll
-            for (int q = 0; q < UQ; ++q) { asm volatile("" : "+v"(ldq[q]), "+v"(cpq[q])); }      // (keeps the eight reads in ONE batch in front of the branches)
-            const int kg = k0 + uk;
-#pragma unroll
-            for (int q = 0; q < UQ; ++q) {
-                const uint32_t uvo = (uint32_t) (cpq[q] - ldq[q] + kg) << 3;
-                pu[q] = (kg >= ldq[q] && kg < ns_s) ? *(gdouble_t) (Ub0 + (uint64_t) uvo) : 0.0;
-            }
-            return;
-        }
-#endif
+    // ---- the complex loader: one predicated 8-byte load per element of the chunk, k-major U stage ----
+    auto fetch_z = [&](int k0) {
 #pragma unroll
         for (int q = 0; q < LQ; ++q) {
             const int kg = k0 + lk + LKS * q;
-            if (Z) pl[q] = (lrow_ok && kg < ns_s) ? zsgn * Lrow[(size_t) (kg >> 1) * 2 * lda_s] : 0.0;
-#if SLUAMD_EXP_NOLOAD >= 4      // 4 / 5 / 6: the same load instructions with their addresses wrapped into a 2 MB / 16 KB / 64 MB window of the arena (always L2 / L1 / MALL hits)
-            else pl[q] = (lrow_ok && kg < ns_s) ? T.val[((size_t) (Lrow - T.val) + (size_t) kg * lda_s) & (SLUAMD_EXP_NOLOAD == 4 ? 0x3FFFF : (SLUAMD_EXP_NOLOAD == 5 ? 0x7FF : 0x7FFFFF))] : 0.0;
-#else
-            else pl[q] = (lrow_ok && kg < ns_s) ? Lrow[(size_t) kg * lda_s] : 0.0;
-#endif
+            pl[q] = (lrow_ok && kg < ns_s) ? zsgn * Lrow[(size_t) (kg >> 1) * 2 * lda_s] : 0.0;
         }
         const int kg = k0 + uk;
 #pragma unroll
         for (int q = 0; q < UQ; ++q) {
             const int ld = ldS[uj + UJS * q];
-            if (Z) pu[q] = ((kg >> 1) >= ld && kg < ns_s) ? Uvs[2 * (cpS[uj + UJS * q] + ((kg >> 1) - ld)) + (kg & 1)] : 0.0;
-#if SLUAMD_EXP_NOLOAD >= 4
-            else pu[q] = (kg >= ld && kg < ns_s) ? T.val[((size_t) (Uvs - T.val) + cpS[uj + UJS * q] + (kg - ld)) & (SLUAMD_EXP_NOLOAD == 4 ? 0x3FFFF : (SLUAMD_EXP_NOLOAD == 5 ? 0x7FF : 0x7FFFFF))] : 0.0;
-#else
-            else pu[q] = (kg >= ld && kg < ns_s) ? Uvs[cpS[uj + UJS * q] + (kg - ld)] : 0.0;
-#endif
+            pu[q] = ((kg >> 1) >= ld && kg < ns_s) ? Uvs[2 * (cpS[uj + UJS * q] + ((kg >> 1) - ld)) + (kg & 1)] : 0.0;
         }
     };
-    auto stash_from = [&](const double *pl, const double *pu, int buf) {
+    auto stash_z = [&](int buf) {
 #pragma unroll
         for (int q = 0; q < LQ; ++q) Ls[buf][(lk + LKS * q) * LDL + li] = pl[q];
 #pragma unroll
         for (int q = 0; q < UQ; ++q) Us[buf][uidx(uk, uj + UJS * q)] = pu[q];
     };
     int kend_cur = 0;                            // end of the current source's K range (this workgroup's share of it)
-#ifdef SLUAMD_EXP_COUNT
-    int cnt_fast = 0, cnt_slow = 0;
-#endif
-    auto fetch = [&](int k0, int tb, bool restart = false) {       // tb: the stage this chunk goes to (the LDS-DMA loads write it at once, every other form at `stash`)
-        if (F3 && !SLUAMD_EXP_NOLOAD) {
-            cur_fast = SLUAMD_SCHUR_CLEAN && clean && k0 + KC <= kend_cur;       // workgroup-uniform
-#ifdef SLUAMD_EXP_COUNT
-            if (cur_fast) ++cnt_fast; else ++cnt_slow;
-#endif
+    auto fetch = [&](int k0, int tb) {           // tb: the stage this chunk goes to (the LDS-DMA loads write it at once, every other form at `stash`)
+        if constexpr (Z) fetch_z(k0);
+        else {
+            cur_fast = clean && k0 + KC <= kend_cur;       // workgroup-uniform
             if (cur_fast) fetch_clean(k0, tb); else fetch3(k0);
-        } else fetch_into(pl, pu, k0, restart);
+        }
     };
     auto stash = [&](int buf) {
-        if (F3 && !SLUAMD_EXP_NOLOAD) { if (cur_fast) stash_clean(buf); else stash3(buf); }
-        else stash_from(pl, pu, buf);
+        if constexpr (Z) stash_z(buf);
+        else if (cur_fast) stash_clean(buf);
+        else stash3(buf);
     };
 
     int buf = 0;
-#if SLUAMD_EXP_VALU
-    int dummy0 = tid, dummy1 = tid + 1, dummy2 = tid + 2, dummy3 = tid + 3;
-#endif
     for (int src = 0; src <= nprev; ++src) {       // farthest predecessor first, k itself last
         int kbeg;
         if (MM == 2 && src < nprev) {
@@ -2020,43 +1912,40 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
             const int nss = ph[0];
             const int64_t co = ((int64_t) ph[8] << 32) | (uint32_t) ph[7], ro = ((int64_t) ph[10] << 32) | (uint32_t) ph[9];
             const int *cinfo = T.pair_colinfo + co;
-            const int ra = (li < nr) ? T.pair_rowmap[ro + li] : -1;
             for (int t = tid; t < TNv; t += NT) {
                 s_cptr2[t] = (t < nc) ? cinfo[2 * t] : 0;
                 s_lead2[t] = (t < nc) ? cinfo[2 * t + 1] : nss;
             }
             __syncthreads();
             ns_s = __builtin_amdgcn_readfirstlane(nss); lda_s = __builtin_amdgcn_readfirstlane(ph[1]);
-            Lsrc = T.val + (((int64_t) ph[4] << 32) | (uint32_t) ph[3]); lvo = (uint32_t) (max(ra, 0) + lk * lda_s) << 3;
-            if (F3) l3_source(2 * li2 < nr ? T.pair_rowmap[ro + 2 * li2] : -1, 2 * li2 + 1 < nr ? T.pair_rowmap[ro + 2 * li2 + 1] : -1, lda_s);
-            Lrow = T.val + (((int64_t) ph[4] << 32) | (uint32_t) ph[3]) + max(ra, 0);
+            Lsrc = T.val + (((int64_t) ph[4] << 32) | (uint32_t) ph[3]);
+            if (W16) l3_source(2 * li2 < nr ? T.pair_rowmap[ro + 2 * li2] : -1, 2 * li2 + 1 < nr ? T.pair_rowmap[ro + 2 * li2 + 1] : -1, lda_s);
             Uvs = T.val + (((int64_t) ph[6] << 32) | (uint32_t) ph[5]);
-            kbeg = __builtin_amdgcn_readfirstlane(ph[2]); lrow_ok = ra >= 0;
+            kbeg = __builtin_amdgcn_readfirstlane(ph[2]);
             cpS = s_cptr2; ldS = s_lead2;
         } else if (src < nprev) {
             const int pj = 3 * k + (nprev - 1 - src);
             const int ks = T.fuse_prev[pj];
             const int nss = T.xsup[ks + 1] - T.xsup[ks];
             const int *cinfo = T.pair_colinfo + 2 * (size_t) (T.pair_coff[pj] + stc);
-            const int ra = (li < nr) ? T.pair_rowmap[T.pair_roff[pj] + Rw + li] : -1;
             for (int t = tid; t < TNv; t += NT) {
                 s_cptr2[t] = (t < nc) ? cinfo[2 * t] : 0;
                 s_lead2[t] = (t < nc) ? cinfo[2 * t + 1] : nss;
             }
             __syncthreads();
-            ns_s = __builtin_amdgcn_readfirstlane(nss); lda_s = __builtin_amdgcn_readfirstlane(T.sn_nsupr[ks]); Lrow = T.val + T.sn_lval[ks] + max(ra, 0); Uvs = T.val + T.sn_uval[ks];
-            Lsrc = T.val + T.sn_lval[ks]; lvo = (uint32_t) (max(ra, 0) + lk * lda_s) << 3;
-            if (F3) { const int64_t ro = (int64_t) T.pair_roff[pj] + Rw; l3_source(2 * li2 < nr ? T.pair_rowmap[ro + 2 * li2] : -1, 2 * li2 + 1 < nr ? T.pair_rowmap[ro + 2 * li2 + 1] : -1, lda_s); }
-            kbeg = __builtin_amdgcn_readfirstlane((nss - T.sn_ldu[ks]) & ~3); lrow_ok = ra >= 0;
+            ns_s = __builtin_amdgcn_readfirstlane(nss); lda_s = __builtin_amdgcn_readfirstlane(T.sn_nsupr[ks]); Uvs = T.val + T.sn_uval[ks];
+            Lsrc = T.val + T.sn_lval[ks];
+            if (W16) { const int64_t ro = (int64_t) T.pair_roff[pj] + Rw; l3_source(2 * li2 < nr ? T.pair_rowmap[ro + 2 * li2] : -1, 2 * li2 + 1 < nr ? T.pair_rowmap[ro + 2 * li2 + 1] : -1, lda_s); }
+            kbeg = __builtin_amdgcn_readfirstlane((nss - T.sn_ldu[ks]) & ~3);
             cpS = s_cptr2; ldS = s_lead2;
         } else {
-            ns_s = __builtin_amdgcn_readfirstlane(ZS * ns); lda_s = __builtin_amdgcn_readfirstlane(lda); Lrow = Lp + lrow0; Uvs = Uv; lrow_ok = li < nr;
-            Lsrc = Lp; lvo = (uint32_t) (lrow0 + lk * lda) << 3;
-            if (F3) l3_source(2 * li2 < nr ? 2 * li2 : -1, 2 * li2 + 1 < nr ? 2 * li2 + 1 : -1, lda);
+            ns_s = __builtin_amdgcn_readfirstlane(ZS * ns); lda_s = __builtin_amdgcn_readfirstlane(lda); Uvs = Uv;
+            Lsrc = Lp;
+            if (W16) l3_source(2 * li2 < nr ? 2 * li2 : -1, 2 * li2 + 1 < nr ? 2 * li2 + 1 : -1, lda);
             kbeg = __builtin_amdgcn_readfirstlane(kbeg_own);
             cpS = s_cptr; ldS = s_lead;
         }
-        if (F3 && SLUAMD_SCHUR_CLEAN) source_clean(kbeg, rows_ok3);
+        if (W16) source_clean(kbeg, rows_ok3);
         int kend = ns_s;
         if (SK) {   // this workgroup's share of the source's chunks
             const int nch = (ns_s - kbeg + KC - 1) / KC;
@@ -2064,11 +1953,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
             kend = min(ns_s, kbeg + c1 * KC); kbeg += c0 * KC;
             if (kbeg >= kend) continue;
         }
-        // chunk at which the destination lines are touched: the one before the last chunk of the last source
         kend_cur = kend;
-        const int ktouch = (src == nprev && has_dst) ? max(kbeg, kbeg + ((kend - 1 - kbeg) / KC - 1) * KC) : -1;
-#if SLUAMD_SCHUR_TIGHT
-        if (DMA && clean && !SLUAMD_EXP_NOLOAD && SLUAMD_SCHUR_TOUCH == 0) {
+        if (DMA && clean) {
             // the full chunks of a clean source in a loop of their own: four LDS-DMA loads, the MFMAs, one wait, one barrier -- none of the general loader's state
             // (predicates, registers of the staged loads, which-path flags) is live or merged at its joins
             const int nfull = (kend - kbeg) / KC;
@@ -2079,56 +1965,24 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
                 for (int c = 0; c < nfull; ++c) {
                     const bool more = c + 1 < nfull;
                     if (more) fetch_clean(kbeg + KC, buf ^ 1);
-                    if (wave_on) schur_chunk<NBR, NBC, LDL, LDU, USW>(Ls[buf], Us[buf], rm0, cn0, lane, acc, pa);
+                    if (wave_on) schur_chunk<NBR, NBC, LDL, LDU, W16>(Ls[buf], Us[buf], rm0, cn0, lane, acc, pa);
                     if (more) lds_dma_wait();
                     buf ^= 1;
                     kbeg += KC;
                     __syncthreads();
                 }
-#ifdef SLUAMD_EXP_COUNT
-                cnt_fast += nfull;
-#endif
                 if (kbeg >= kend) continue;
             }
         }
-#endif
         // (re)start of the software pipeline: every wave is past the last chunk's MFMAs (closing barrier of the loop)
-        fetch(kbeg, buf, true);
+        fetch(kbeg, buf);
         stash(buf);
         __syncthreads();
         for (int k0 = kbeg; k0 < kend; k0 += KC) {
             const bool more = k0 + KC < kend;
             if (more) fetch(k0 + KC, NBUF == 2 ? buf ^ 1 : 0);
-#if SLUAMD_EXP_VALU
-#pragma unroll
-            for (int e = 0; e < SLUAMD_EXP_VALU / 4; ++e)
-                asm volatile("v_add_u32 %0, %0, %1\n\tv_add_u32 %1, %1, %2\n\tv_add_u32 %2, %2, %3\n\tv_add_u32 %3, %3, %0" : "+v"(dummy0), "+v"(dummy1), "+v"(dummy2), "+v"(dummy3));
-#endif
-            if (SLUAMD_SCHUR_TOUCH && k0 == ktouch) {
-                // one chunk before the last: touch one element of every destination line (16 rows x 1 column of the tile) so
-                // that the fp64 atomics of the epilogue find their lines in L2 instead of each holding an L2 miss slot
-                constexpr int RG = TMv / 16;
-                const int id0 = tid, id1 = tid + NT;
-                const int c0 = id0 / RG, g0 = id0 % RG, c1 = id1 / RG, g1 = id1 % RG;
-#if SLUAMD_SCHUR_TOUCH == 2
-                if (DMA) {
-                    // the touch as two 4-byte loads per lane into a scratch kilobyte of LDS nobody reads: no destination registers (at the 128-VGPR cap the two
-                    // touched values were spilled, i.e. waited for at once), drained with the chunk's own loads / before the scatter
-                    const double *t0 = (id0 < TNv * RG && c0 < nc && g0 * 16 < nr) ? dst + s_colmap[c0] + s_rowmap[g0 * 16] : dst;
-                    const double *t1 = (id1 < TNv * RG && c1 < nc && g1 * 16 < nr) ? dst + s_colmap[c1] + s_rowmap[g1 * 16] : dst;
-                    const uint32_t sink = __builtin_amdgcn_readfirstlane(lds_byte_addr(&s_sink[wave * 64]));
-                    unsigned keep;
-                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
-                                 : "=&s"(keep) : "v"(t0), "v"(t1), "s"(sink) : "memory");
-                } else
-#endif
-                {
-                if (id0 < TNv * RG && c0 < nc && g0 * 16 < nr) touch0 = dst[s_colmap[c0] + s_rowmap[g0 * 16]];
-                if (id1 < TNv * RG && c1 < nc && g1 * 16 < nr) touch1 = dst[s_colmap[c1] + s_rowmap[g1 * 16]];
-                }
-            }
             const double *Lb = Ls[buf], *Ub = Us[buf];
-            if (wave_on) schur_chunk<NBR, NBC, LDL, LDU, USW>(Lb, Ub, rm0, cn0, lane, acc, pa);
+            if (wave_on) schur_chunk<NBR, NBC, LDL, LDU, W16>(Lb, Ub, rm0, cn0, lane, acc, pa);
             if (NBUF == 2) { if (more) stash(buf ^ 1); buf ^= 1; }
             else if (more) { __syncthreads(); stash(0); }   // single stage: every wave is done reading before it is overwritten
             __syncthreads();
@@ -2136,27 +1990,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
     }
 
     // ---- scatter (epilogue) ----------------------------------------------------------------------
-    if (DMA && SLUAMD_SCHUR_TOUCH == 2) lds_dma_wait();
-#ifdef SLUAMD_EXP_COUNT
-    if (tid == 0 && TMv == 128) { atomicAdd(&info[4], cnt_fast); atomicAdd(&info[5], cnt_slow); }
-    if (tid == 0 && TMv == 64) { atomicAdd(&info[6], cnt_fast); atomicAdd(&info[7], cnt_slow); }
-#endif
-#if SLUAMD_EXP_VALU
-    if (__builtin_expect((dummy0 ^ dummy1 ^ dummy2 ^ dummy3) == 0x7fffffff && tid == 777, 0)) atomicAdd(&info[3], 1);
-#endif
     if (!has_dst) return;
-    if (__builtin_expect(touch0 == 1.2345e-300 && touch1 == 1.2345e-300, 0)) atomicAdd(&info[3], 1);   // keeps the touch loads alive
-#if SLUAMD_EXP_EPI == 0
-    {
-        double keep = 0.0;
-#pragma unroll
-        for (int ci = 0; ci < NBC; ++ci)
-#pragma unroll
-            for (int ri = 0; ri < NBR; ++ri) keep += (acc[ci][ri][0] + acc[ci][ri][1]) + (acc[ci][ri][2] + acc[ci][ri][3]);
-        if (__builtin_expect(keep == 1.2345e-300, 0)) atomicAdd(&info[3], 1);
-        return;
-    }
-#endif
 #pragma unroll
     for (int ci = 0; ci < NBC; ++ci)
 #pragma unroll
@@ -2167,11 +2001,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : (TMv == 128 ? 2 : (Z ? 6 : 
 #pragma unroll
                 for (int ri = 0; ri < NBR; ++ri) {
                     const int row = rm0 + 16 * ri + (lane & 15);
-#if SLUAMD_EXP_EPI == 1
-                    if (row < nr) dcol[s_rowmap[row]] -= acc[ci][ri][r];
-#else
                     if (row < nr) atomic_sub_f64(dcol + s_rowmap[row], acc[ci][ri][r]);
-#endif
                 }
             }
         }

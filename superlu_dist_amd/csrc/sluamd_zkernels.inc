@@ -911,16 +911,13 @@ __global__ __launch_bounds__(256) void kz_bwd_update(DevTables T, const int *__r
 // The level-set form above pays two dependent launches per level and sweep (diagonal solves, updates): 212 launches of ~15 us for the 53 levels of the 2-D
 // configuration, 0.10 of the HBM peak.  ONE launch per level and sweep instead, out of place like the double path's links (x = accumulators, w = solved blocks
 // forward; w = accumulators, x = final solution backward):
-//   forward  unit (k, 256-row strip): EVERY strip's workgroup solves y_k = inv(L_kk) x_k itself -- one wave, in registers, the triangle streamed in eight-column
-//            batches exactly as kz_solve_diag_wave -- while the other waves already have the first columns of their panel rows in flight; strip 0 stores y_k to w;
+//   forward  unit (k, 256-row strip): EVERY strip's workgroup solves y_k = inv(L_kk) x_k itself -- one wave, in registers, the whole triangle loaded in one
+//            round trip (zsolve64_wave) -- while the other waves already have the first columns of their panel rows in flight; strip 0 stores y_k to w;
 //            then x[rows] -= L(rows, k) y_k as kz_fwd_update.  (A supernode without off-diagonal rows still gets one unit: LevelSched::zffu_prefix.)
 //   backward unit (k, 64-column chunk): w_k -= U(k, chunk) x[columns] as kz_bwd_update (fp64 atomics), then every wave drains, ONE lane releases at agent
 //            scope and takes a ticket of supernode k; the workgroup that takes the LAST ticket acquires, reads the completed w_k and solves
 //            x_k = inv(U_kk) w_k (and resets the ticket counter for the next sweep).  Few workgroups per level here: the agent-scope hand-off that was too
 //            expensive for the double path at 100^3 (NOTEBOOK.md section 5) costs less than the launch it replaces.
-#ifndef SLUAMD_ZSOLVE_UPFRONT
-#define SLUAMD_ZSOLVE_UPFRONT 1
-#endif
 template <bool LOWER>
 __device__ __forceinline__ zc zsolve64_wave(const zc *A, int lda, int ns, int lane, zc b)
 {   // one wave: b = row `lane` of the right-hand side; returns row `lane` of inv(L) b (unit lower) or inv(U) b
@@ -928,7 +925,6 @@ __device__ __forceinline__ zc zsolve64_wave(const zc *A, int lda, int ns, int la
     const zc zero = make_double2(0.0, 0.0);
     zc dinv = make_double2(1.0, 0.0);
     if (!LOWER && rok) dinv = z_div(make_double2(1.0, 0.0), A[lane + (size_t) lane * lda]);
-#if SLUAMD_ZSOLVE_UPFRONT
     // the whole triangle in ONE round trip: row `lane` of every column, in registers (the substitution itself is ~1 us; eight dependent batches were ~8)
     zc col[64];
 #pragma unroll
@@ -943,36 +939,6 @@ __device__ __forceinline__ zc zsolve64_wave(const zc *A, int lda, int ns, int la
         }
     }
     return b;
-#else
-    const int nbat = (ns + 7) >> 3;
-    auto load_batch = [&](int t, zc (&col)[8]) {
-        const int j0 = LOWER ? 8 * t : 8 * (nbat - 1 - t);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int j = j0 + u;
-            col[u] = (rok && j < ns && (LOWER ? lane > j : lane < j)) ? A[lane + (size_t) j * lda] : zero;
-        }
-    };
-    zc cur[8], nxt[8];
-    load_batch(0, cur);
-    for (int t = 0; t < nbat; ++t) {
-        if (t + 1 < nbat) load_batch(t + 1, nxt);
-        const int j0 = LOWER ? 8 * t : 8 * (nbat - 1 - t);
-#pragma unroll
-        for (int uu = 0; uu < 8; ++uu) {
-            const int u = LOWER ? uu : 7 - uu;
-            const int j = j0 + u;
-            if (j < ns) {      // wave-uniform
-                if (!LOWER && lane == j) b = z_mul(b, dinv);
-                const zc xj = make_double2(lane_bcast(b.x, j), lane_bcast(b.y, j));
-                b = z_fnma(b, cur[u], xj);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) cur[u] = nxt[u];
-    }
-    return b;
-#endif
 }
 
 // Wave `wave` of a 64-column chunk of U(k, :) on a latency-bound level: its sixteen columns (wave, wave + 4, ...) with ALL their loads in flight at once --
@@ -999,10 +965,7 @@ __device__ __forceinline__ zc z_bwd_cols(const zc *Uv, const zc *xr, const int *
     return make_double2(acc0.x + acc1.x, acc0.y + acc1.y);
 }
 
-#ifndef SLUAMD_ZFWD_BATCH
-#define SLUAMD_ZFWD_BATCH 8
-#endif
-constexpr int ZFW = SLUAMD_ZFWD_BATCH;     // panel columns per batch of a thread's loads in the fused forward unit
+constexpr int ZFW = 8;     // panel columns per batch of a thread's loads in the fused forward unit
 __global__ __launch_bounds__(256) void kz_fwd_fused(DevTables T, const int *__restrict__ nodes, const int *__restrict__ prefix, int nn,
                                                     zc *__restrict__ x, zc *__restrict__ w, int64_t ldx, int nrhs)
 {
