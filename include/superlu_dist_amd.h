@@ -287,6 +287,12 @@ int sluamd_symb_partition(sluamd_symb_t s, int32_t npdep, int32_t *sn_tree);
  * `index_entries` may be NULL; sn_tree as for sluamd_dCreateLUHandleFromSymbGrid (NULL when npdep == 1). */
 int sluamd_symb_grid_footprint(sluamd_symb_t s, int32_t nprow, int32_t npcol, int32_t npdep, const int32_t *sn_tree,
                                int64_t *values, int64_t *replicated, int64_t *index_entries);
+/* The symbolic structure of the block-diagonal matrix diag(A, ..., A) with `count` copies of the m x m pattern `s` was made for (sluamd_dsymbfact[_unsym]),
+ * matrix-major: xsup, every L block's row set and every Ufstnz entry are those of `s` shifted by k m for copy k, supernode ids by k nsupers; the final
+ * column permutation is perm_big[k m + i] = k m + perm_c_out[i].  `*out` is a full sluamd_symb_t (sluamd_symb_info, _export, _view, _partition,
+ * sluamd_dCreateLUHandleFromSymb, sluamd_symb_free); `s` is not modified and may be freed first.  The cost is linear in the output: no symbolic
+ * factorisation of count m columns runs.  Errors (SLUAMD_EINVAL): null arguments, count <= 0, count m beyond the 32-bit indices of the ABI. */
+int sluamd_symb_replicate(sluamd_symb_t s, int32_t count, sluamd_symb_t *out);
 /* re-run the device-side distribution (zero-fill + scatter of A) on such a handle: refactor loops */
 int sluamd_dResetValues(sluamd_handle_t h);
 
@@ -501,6 +507,58 @@ int sluamd_dUpdateValues(sluamd_handle_t h, const double *nzval, sluamd_update_t
 int sluamd_dUpdateValues_dev(sluamd_handle_t h, const double *d_nzval, sluamd_update_t *out);             /* device pointer */
 int sluamd_zUpdateValues(sluamd_handle_t h, const sluamd_doublecomplex *nzval, sluamd_update_t *out);
 int sluamd_zUpdateValues_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_nzval, sluamd_update_t *out);
+
+/* ---- Fixed-size batches: `count` systems A_k X_k = B_k of order m that share ONE sparsity pattern and differ in values, with info, berr and refinement steps
+ * per matrix (the role of the reference's pdgssvx3d_csc_batch, SRC/double/pdgssvx3d_csc_batch.c, reached through pddrive3d -b).  Time stepping and ensembles:
+ * hundreds of small systems, each of which would pay its own symbolic factorisation, plan, tables and arena as a handle of its own, with kernels too small
+ * to fill the device.  The batch is the block-diagonal matrix diag(A_0 .. A_{count-1}) on ONE ordinary 1 x 1 x 1 double handle, planned for the replicated
+ * structure (sluamd_symb_replicate): count copies of one elimination tree are count-wide DAG levels of the same kernels.
+ *   s: the symbolic structure of ONE matrix (maxsup <= 256), rowptr / colind its CSR pattern, perm_c_final the perm_c_out of its symbolic factorisation;
+ *   nzval: matrix k's values at nzval + k stride (stride >= nnz), in the order of the shared CSR;
+ *   B, X: matrix k's m x nrhs column-major block at B + k strideB / X + k strideX, leading dimensions ldb, ldx >= m, the caller's ordering.
+ * sluamd_dBatchCreate plans once and distributes the values; sluamd_dBatchUpdateValues[_dev] is the same distribution path for new values of the same pattern
+ * (Fact = SamePattern_SameRowPerm) and leaves the batch UNFACTORED; the _dev form reads d_nzval in the order of the handle's stream and the caller keeps it
+ * unchanged until the next synchronising call (a factorisation or a solve).  The values are gathered through the entry map of one matrix plus the per-copy
+ * offset; no count-times-larger map exists.
+ * sluamd_dBatchFactor: info[k] = the smallest column of matrix k (1-based, in A_k's numbering after perm_c) whose U diagonal entry is exactly zero, else 0 --
+ * what sluamd_pdgstrf3d returns for A_k factored alone under SLUAMD_INFO_FIRST.  A singular A_k disturbs no other matrix: its inf / NaN stay inside its own
+ * blocks, and so do its solutions'.
+ * sluamd_dBatchSolve[_dev]: pack (xp[k m + perm_c[i], j] = B_k[i, j]), the handle's solve (trans = SLUAMD_NOTRANS / _TRANS / _CONJ), unpack: the only passes over
+ * the right-hand sides when refine == 0.  refine != 0 (SLUAMD_NOTRANS only, as sluamd_pdgssvx3d_solve): the loop of sluamd_pdgsrfs3d with the stopping rule
+ * per matrix -- berr[k nrhs + j], steps[k] (those of the last right-hand side), SAFE1 / SAFE2 formed from m so that a matrix sees the constants it would see
+ * alone; one copy of count doubles to the host per sweep; a column ends when no matrix continues; a matrix that has stopped keeps the X and berr of its
+ * stopping sweep while the others go on.  The loop refines against the matrix ATTACHED to the batch's handle, which is the batch's own block-diagonal
+ * matrix (order count m, column k m + j for entry (i, j) of matrix k) unless the caller attached another one through sluamd_BatchHandle; such a matrix
+ * must be block diagonal too (the residual of matrix k reads X_k only), and sluamd_dBatchUpdateValues refuses while it is attached.
+ * berr and steps may be NULL when refine == 0 (steps is then all zero).  nrhs == 0 returns 0.
+ * sluamd_BatchHandle: the handle, borrowed (sluamd_get_stats, sluamd_setup_times, sluamd_plan_table; it dies with the batch).
+ * Not available on a batch: complex16 and process grids (no entry point takes either), RowPerm and the single-matrix sluamd_dEquilibrate made through the
+ * borrowed handle (every later batch call returns SLUAMD_EINVAL), replace_tiny_pivot (it needs a threshold
+ * eps anorm_k per matrix inside the diagonal LU kernels), supernodes wider than 256 columns.  Other errors (SLUAMD_EINVAL): count <= 0, stride < nnz,
+ * ldb or ldx < m, strides smaller than a block, a solve of an unfactored batch, refine with a transposed system or without berr.
+ * sluamd_dBatchEquilibrate: pdgsequ + pdlaqgs PER MATRIX, once per batch, before the factorisation.  out[k] is what sluamd_dEquilibrate returns for A_k alone:
+ * equed, rowcnd, colcnd, amax, R and C (sluamd_BatchGetScalings: count m values each, matrix-major, ones where a side is not scaled) bit for bit -- the maxima
+ * are exact --, anorm with the summation caveat of sluamd_equil_t::anorm.  A matrix with an exactly zero row or column gets its own out[k].info (i + 1, or
+ * m + j + 1, in its own numbering) and stays unscaled with equed = N; the others proceed.  The scaled values replace the attached ones and are distributed
+ * into the store: the batch is UNFACTORED afterwards.  sluamd_dBatchUpdateValues[_dev] on an equilibrated batch re-applies the stored R, C and equed of every
+ * matrix, (a r[i]) c[j] in that order, as sluamd_dUpdateValues does.  sluamd_dBatchSolve takes B and returns X in the caller's scaling (B scaled by R, X by C;
+ * the roles swapped for a transposed system); with refine the scaled system is refined and berr is that of the scaled system, as in the reference.
+ * Errors (SLUAMD_EINVAL): a second call; a batch whose handle had another matrix attached, or was equilibrated / row-permuted through sluamd_BatchHandle
+ * (every batch call refuses such a handle). */
+typedef struct sluamd_batch_s *sluamd_batch_t;
+int sluamd_dBatchCreate(sluamd_batch_t *b, sluamd_symb_t s, int32_t count, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const double *nzval,
+                        int64_t stride, const sluamd_int_t *perm_c_final, const sluamd_options_t *opt);
+int sluamd_dBatchUpdateValues(sluamd_batch_t b, const double *nzval, int64_t stride);
+int sluamd_dBatchUpdateValues_dev(sluamd_batch_t b, const double *d_nzval, int64_t stride);
+int sluamd_dBatchEquilibrate(sluamd_batch_t b, sluamd_equil_t *out /* [count] */);
+int sluamd_BatchGetScalings(sluamd_batch_t b, double *r /* [count m] */, double *c /* [count m] */);
+int sluamd_dBatchFactor(sluamd_batch_t b, int32_t *info /* [count] */);
+int sluamd_dBatchSolve(sluamd_batch_t b, int trans, const double *B, int64_t ldb, int64_t strideB, double *X, int64_t ldx, int64_t strideX, int32_t nrhs,
+                       int refine, double *berr /* [count * nrhs] */, int32_t *steps /* [count] */);
+int sluamd_dBatchSolve_dev(sluamd_batch_t b, int trans, const double *d_B, int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t nrhs,
+                           int refine, double *berr, int32_t *steps);
+sluamd_handle_t sluamd_BatchHandle(sluamd_batch_t b);
+void sluamd_BatchDestroy(sluamd_batch_t b);
 
 /* ------------------------------------------------------------------------------------------------
  * Process grids: nprow x npcol x npdep ranks, one rank per GPU (gridinfo3d_t, superlu_defs.h:385-420).

@@ -71,6 +71,8 @@ EXPORTS = [
     "sluamd_dEquilibrateWith", "sluamd_zEquilibrateWith", "sluamd_dLargeDiag", "sluamd_zLargeDiag", "sluamd_SetRowPerm",
     "sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev",
     "sluamd_dUpdateValues", "sluamd_dUpdateValues_dev", "sluamd_zUpdateValues", "sluamd_zUpdateValues_dev",
+    "sluamd_symb_replicate", "sluamd_dBatchCreate", "sluamd_dBatchUpdateValues", "sluamd_dBatchUpdateValues_dev", "sluamd_dBatchFactor", "sluamd_dBatchEquilibrate", "sluamd_BatchGetScalings",
+    "sluamd_dBatchSolve", "sluamd_dBatchSolve_dev", "sluamd_BatchHandle", "sluamd_BatchDestroy",
     "sluamd_comm_rccl_unique_id", "sluamd_comm_create_rccl", "sluamd_comm_create_callbacks", "sluamd_comm_create_local",
     "sluamd_comm_selftest", "sluamd_comm_rank", "sluamd_comm_size", "sluamd_comm_destroy", "sluamd_dCreateLUHandleGrid",
     "sluamd_dCreateLUHandleFromSymbGrid", "sluamd_zCreateLUHandleGrid", "sluamd_zCreateLUHandleFromSymbGrid",
@@ -180,6 +182,22 @@ def bind(L):
     for name in ("sluamd_dUpdateValues", "sluamd_dUpdateValues_dev", "sluamd_zUpdateValues", "sluamd_zUpdateValues_dev"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Update)]
+    L.sluamd_symb_replicate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+    # batches: only in the product library (the CPU test build has no batch kernels)
+    if hasattr(L, "sluamd_dBatchCreate"):
+        L.sluamd_dBatchCreate.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, P_int, P_int, P_dbl, C.c_int64, P_int, C.POINTER(Options)]
+        L.sluamd_dBatchUpdateValues.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.sluamd_dBatchUpdateValues_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.sluamd_dBatchFactor.argtypes = [C.c_void_p, P_int]
+        L.sluamd_dBatchEquilibrate.argtypes = [C.c_void_p, C.POINTER(Equil)]
+        L.sluamd_BatchGetScalings.argtypes = [C.c_void_p, P_dbl, P_dbl]
+        for name in ("sluamd_dBatchSolve", "sluamd_dBatchSolve_dev"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int,
+                                         P_dbl, P_int]
+        L.sluamd_BatchHandle.argtypes = [C.c_void_p]
+        L.sluamd_BatchHandle.restype = C.c_void_p
+        L.sluamd_BatchDestroy.argtypes = [C.c_void_p]
+        L.sluamd_BatchDestroy.restype = None
     L.sluamd_PlanTransposedSweeps.argtypes = [C.c_void_p]
     L.sluamd_plan_xlists.argtypes = [C.c_void_p, C.c_int, P_int, C.c_int64, C.POINTER(C.c_int64)]
     L.sluamd_comm_rccl_unique_id.argtypes = [C.c_void_p]

@@ -213,9 +213,9 @@ static int scatter_positions(const Handle &H, const Symb &sy, const HostTables &
 
 static int create_from_symb(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const double *nzval,
                             const sluamd_int_t *perm_c_final, const sluamd_options_t *opt, const Grid &g, const int32_t *sn_tree, Comm *comm,
-                            bool z)
+                            bool z, bool empty = false /* create_symb_handle_empty alone: the structure only, no matrix */)
 {
-    if (!out || !s || !rowptr || !colind || !nzval || !perm_c_final) { set_error("null argument"); return SLUAMD_EINVAL; }
+    if (!out || !s || (!empty && (!rowptr || !colind || !nzval || !perm_c_final))) { set_error("null argument"); return SLUAMD_EINVAL; }
     *out = nullptr;
     if (g.size() > 1 && !comm) { set_error("a process grid with more than one rank needs a communicator"); return SLUAMD_EINVAL; }
     sluamd_options_t o;
@@ -238,7 +238,7 @@ static int create_from_symb(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_
     if ((rc = slots_from_symb(*H, *sy, g, sn_tree, in))) return fail(rc);
     H->setup.lap("slots_from_symbolic");
     if ((rc = plan_and_upload(H, in, t))) return fail(rc);
-    {   // device-side distribution of A's values (the arena is zero-filled)
+    if (!empty) {   // device-side distribution of A's values (the arena is zero-filled)
         std::vector<int64_t> pos;
         if ((rc = scatter_positions(*H, *sy, t, rowptr, colind, perm_c_final, pos))) return fail(rc);
         H->setup.lap("scatter_positions");
@@ -266,6 +266,11 @@ static int create_from_symb(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_
     }
     *out = hh;
     return 0;
+}
+
+int create_symb_handle_empty(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_options_t *opt)
+{
+    return create_from_symb(out, s, nullptr, nullptr, nullptr, nullptr, opt, Grid{}, nullptr, nullptr, false, true);
 }
 
 }  // namespace sluamd

@@ -750,6 +750,90 @@ int sluamd_symb_export(sluamd_symb_t s, sluamd_int_t *xsup, int64_t *lidx_off, s
 
 void sluamd_symb_free(sluamd_symb_t s) { delete reinterpret_cast<Symb *>(s); }
 
+/* The symbolic structure of diag(A, ..., A), `count` copies of the m x m pattern of `s`, matrix-major: copy c holds columns [c m, (c + 1) m) and supernodes
+ * [c nsupers, (c + 1) nsupers).  Every array of the store is the one of `s` repeated with its column / row entries shifted by c m, its supernode ids by
+ * c nsupers and its value offsets by c nnz: linear in the output, no symbolic factorisation of count m columns. */
+int sluamd_symb_replicate(sluamd_symb_t s, int32_t count, sluamd_symb_t *out)
+{
+    if (!s || !out || count <= 0) { set_error("sluamd_symb_replicate: null argument or count <= 0"); return SLUAMD_EINVAL; }
+    *out = nullptr;
+    const Symb *a = reinterpret_cast<const Symb *>(s);
+    const HostStruct &ha = a->hs;
+    const int64_t m = ha.n;
+    const int ns = ha.nsupers;
+    if (m * count > 0x7fffffffLL || (int64_t) ns * count > 0x7fffffffLL) { set_error("sluamd_symb_replicate: count * n exceeds 32-bit indices"); return SLUAMD_EINVAL; }
+    Symb *b = new Symb();
+    HostStruct &hb = b->hs;
+    hb.n = m * count;
+    hb.nsupers = ns * count;
+    hb.nnzL = ha.nnzL * count; hb.nnzU = ha.nnzU * count;
+    b->flops = a->flops * count;
+    const int64_t nli = (int64_t) ha.lidx.size(), nui = (int64_t) ha.uidx.size(), nsr = (int64_t) a->srows.size(), nuc = (int64_t) a->ucol_col.size();
+    const bool unsym = !a->ucol_off.empty();
+    hb.xsup.resize((size_t) ns * count + 1);
+    hb.lidx_off.resize((size_t) ns * count + 1); hb.uidx_off.resize((size_t) ns * count + 1);
+    hb.lval_off.resize((size_t) ns * count + 1); hb.uval_off.resize((size_t) ns * count + 1);
+    hb.lidx.resize((size_t) (nli * count)); hb.uidx.resize((size_t) (nui * count));
+    hb.present.assign((size_t) ns * count, 1);
+    b->supno.resize((size_t) (m * count));
+    b->perm_c_final.resize((size_t) (m * count));
+    b->srow_off.resize((size_t) ns * count + 1); b->srows.resize((size_t) (nsr * count));
+    if (unsym) {
+        b->ucol_off.resize((size_t) ns * count + 1);
+        b->ucol_col.resize((size_t) (nuc * count)); b->ucol_fnz.resize((size_t) (nuc * count)); b->ucol_voff.resize((size_t) (nuc * count));
+    }
+    if (!a->sn_parent.empty()) b->sn_parent.resize((size_t) ns * count);
+    for (int c = 0; c < count; ++c) {
+        const int dm = (int) (c * m), dk = c * ns;
+        for (int k = 0; k < ns; ++k) {
+            const size_t K = (size_t) dk + k;
+            hb.xsup[K] = ha.xsup[k] + dm;
+            hb.lidx_off[K] = ha.lidx_off[k] + c * nli; hb.uidx_off[K] = ha.uidx_off[k] + c * nui;
+            hb.lval_off[K] = ha.lval_off[k] + c * ha.nnzL; hb.uval_off[K] = ha.uval_off[k] + c * ha.nnzU;
+            b->srow_off[K] = a->srow_off[k] + c * nsr;
+            if (unsym) b->ucol_off[K] = a->ucol_off[k] + c * nuc;
+            if (!a->sn_parent.empty()) b->sn_parent[K] = a->sn_parent[k] >= 0 ? a->sn_parent[k] + dk : -1;
+            // L: header (blocks, rows), then per block (supernode, rows of the block) + its row subscripts
+            const int *li = ha.lidx.data() + ha.lidx_off[k];
+            int *lo = hb.lidx.data() + hb.lidx_off[K];
+            lo[0] = li[0]; lo[1] = li[1];
+            int p = BC_HEADER;
+            for (int blk = 0; blk < li[0]; ++blk) {
+                const int nbrow = li[p + 1];
+                lo[p] = li[p] + dk; lo[p + 1] = nbrow;
+                for (int i = 0; i < nbrow; ++i) lo[p + LB_DESCRIPTOR + i] = li[p + LB_DESCRIPTOR + i] + dm;
+                p += LB_DESCRIPTOR + nbrow;
+            }
+            // U: header (blocks, values, length), then per block (supernode, values of the block) + the first nonzero row of each of its columns
+            if (ha.uidx_off[k + 1] > ha.uidx_off[k]) {
+                const int *ui = ha.uidx.data() + ha.uidx_off[k];
+                int *uo = hb.uidx.data() + hb.uidx_off[K];
+                uo[0] = ui[0]; uo[1] = ui[1]; uo[2] = ui[2];
+                int q = BR_HEADER;
+                for (int blk = 0; blk < ui[0]; ++blk) {
+                    const int jb = ui[q], nsj = ha.xsup[jb + 1] - ha.xsup[jb];
+                    uo[q] = jb + dk; uo[q + 1] = ui[q + 1];
+                    for (int j = 0; j < nsj; ++j) uo[q + UB_DESCRIPTOR + j] = ui[q + UB_DESCRIPTOR + j] + dm;
+                    q += UB_DESCRIPTOR + nsj;
+                }
+            }
+        }
+        for (int64_t i = 0; i < m; ++i) { b->supno[(size_t) (dm + i)] = a->supno[i] + dk; b->perm_c_final[(size_t) (dm + i)] = a->perm_c_final[i] + dm; }
+        for (int64_t e = 0; e < nsr; ++e) b->srows[(size_t) (c * nsr + e)] = a->srows[e] + dm;
+        for (int64_t e = 0; e < nuc; ++e) {
+            b->ucol_col[(size_t) (c * nuc + e)] = a->ucol_col[e] + dm; b->ucol_fnz[(size_t) (c * nuc + e)] = a->ucol_fnz[e] + dm;
+            b->ucol_voff[(size_t) (c * nuc + e)] = a->ucol_voff[e];
+        }
+    }
+    const size_t E = (size_t) ns * count;
+    hb.xsup[E] = (int) (m * count);
+    hb.lidx_off[E] = nli * count; hb.uidx_off[E] = nui * count; hb.lval_off[E] = hb.nnzL; hb.uval_off[E] = hb.nnzU;
+    b->srow_off[E] = nsr * count;
+    if (unsym) b->ucol_off[E] = nuc * count;
+    *out = reinterpret_cast<sluamd_symb_t>(b);
+    return 0;
+}
+
 }  // extern "C"
 
 namespace sluamd {

@@ -137,6 +137,25 @@ class Symbolic:
         self.nsupers, self.nnzL, self.nnzU, self.flops = ns.value, nl.value, nu.value, fl.value
         self.lidx_len, self.uidx_len = li.value, ui.value
 
+    def replicate(self, count):
+        """The Symbolic of diag(A, ..., A) with `count` copies of this pattern, matrix-major (sluamd_symb_replicate): no symbolic factorisation runs"""
+        L = _lib.load()
+        count = int(count)
+        out = C.c_void_p()
+        _lib.check(L.sluamd_symb_replicate(self._h, count, C.byref(out)), "sluamd_symb_replicate")
+        r = Symbolic.__new__(Symbolic)
+        nnz = len(self.colind)
+        r.n = self.n * count
+        r.rowptr = np.concatenate([self.rowptr[:-1] + k * nnz for k in range(count)] + [[count * nnz]]).astype(np.int32)
+        r.colind = np.concatenate([self.colind + k * self.n for k in range(count)]).astype(np.int32)
+        r.perm_c = np.concatenate([self.perm_c + k * self.n for k in range(count)]).astype(np.int32)
+        r._h = out
+        ns = C.c_int32(); nl = C.c_int64(); nu = C.c_int64(); li = C.c_int64(); ui = C.c_int64(); fl = C.c_double()
+        L.sluamd_symb_info(r._h, C.byref(ns), C.byref(nl), C.byref(nu), C.byref(li), C.byref(ui), C.byref(fl))
+        r.nsupers, r.nnzL, r.nnzU, r.flops = ns.value, nl.value, nu.value, fl.value
+        r.lidx_len, r.uidx_len = li.value, ui.value
+        return r
+
     def distribute_host(self, nzval):
         L = _lib.load()
         nz = np.ascontiguousarray(nzval, dtype=np.float64)
@@ -785,3 +804,133 @@ def _gssvx3d_equil(h, symb, n, rowptr, colind, nzval, b, keep, refine, trans):
 
 
 pzgssvx3d = pdgssvx3d   # complex16 input (nzval complex) takes the pzgstrf3d / pzgstrs3d path of the same driver
+
+
+class BatchHandle:
+    """sluamd_batch_t: `count` matrices of one sparsity pattern on one handle (block-diagonal factorisation), with info, berr and refinement steps per
+    matrix.  Values [count, nnz] in the order of the shared CSR; right-hand sides [count, n] or [count, n, nrhs]."""
+
+    def __init__(self, b, n, nnz, count):
+        self._b = b
+        self.n, self.nnz, self.count = int(n), int(nnz), int(count)
+
+    @classmethod
+    def create(cls, symb, nzvals, deterministic=False, device=-1, replace_tiny=False):
+        """symb: the Symbolic of ONE matrix; nzvals: [count, >= nnz] (a row's first nnz values are the matrix)"""
+        if np.iscomplexobj(nzvals):
+            raise ValueError("BatchHandle.create: complex16 values are not available on a batch (double precision only)")
+        nz = np.ascontiguousarray(nzvals, dtype=np.float64)
+        if nz.ndim != 2:
+            raise ValueError("nzvals must be [count, nnz]")
+        o = LUHandle._opts(replace_tiny=replace_tiny, deterministic=deterministic, device=device)
+        b = C.c_void_p()
+        _lib.check(_lib.entry("sluamd_dBatchCreate")(C.byref(b), symb._h, nz.shape[0], _pi(symb.rowptr), _pi(symb.colind), _pd(nz), nz.shape[1],
+                                                     _pi(symb.perm_c), C.byref(o)), "sluamd_dBatchCreate")
+        return cls(b, symb.n, len(symb.colind), nz.shape[0])
+
+    def update_values(self, nzvals):
+        """new values of the same pattern: a numpy array [count, >= nnz] (host form) or a torch device tensor of that shape (_dev form); the batch is
+        unfactored afterwards"""
+        if isinstance(nzvals, np.ndarray) or not hasattr(nzvals, "data_ptr"):
+            nz = np.ascontiguousarray(nzvals, dtype=np.float64)
+            if nz.ndim != 2 or nz.shape[0] != self.count:
+                raise ValueError(f"nzvals must be [{self.count}, >= {self.nnz}]")
+            _lib.check(_lib.entry("sluamd_dBatchUpdateValues")(self._b, nz.ctypes.data_as(C.c_void_p), nz.shape[1]), "sluamd_dBatchUpdateValues")
+            return
+        import torch
+        if nzvals.dtype != torch.float64 or nzvals.dim() != 2 or nzvals.shape[0] != self.count or not nzvals.is_contiguous() or not nzvals.is_cuda:
+            raise ValueError(f"device values must be a contiguous float64 device tensor [{self.count}, >= {self.nnz}]")
+        torch.cuda.current_stream(nzvals.device).synchronize()      # what produced the tensor must be complete (contract of the _dev form)
+        _lib.check(_lib.entry("sluamd_dBatchUpdateValues_dev")(self._b, C.c_void_p(nzvals.data_ptr()), int(nzvals.shape[1])), "sluamd_dBatchUpdateValues_dev")
+
+    def equilibrate(self):
+        """pdgsequ + pdlaqgs per matrix (sluamd_dBatchEquilibrate): a list of count dicts like LUHandle.equilibrate's (equed as "N" / "R" / "C" / "B")"""
+        out = (_lib.Equil * self.count)()
+        _lib.check(_lib.entry("sluamd_dBatchEquilibrate")(self._b, out), "sluamd_dBatchEquilibrate")
+        return [{"equed": EQUED[e.equed], "info": e.info, "rowcnd": e.rowcnd, "colcnd": e.colcnd, "amax": e.amax, "anorm": e.anorm} for e in out]
+
+    def scalings(self):
+        """(R, C), each [count, n]: ones where a matrix's side is not scaled"""
+        r = np.ones((self.count, self.n)); c = np.ones((self.count, self.n))
+        _lib.check(_lib.entry("sluamd_BatchGetScalings")(self._b, _pd(r), _pd(c)), "sluamd_BatchGetScalings")
+        return r, c
+
+    def factor(self):
+        """info[count]: per matrix 0, or the 1-based column of its first exactly zero pivot"""
+        info = np.zeros(self.count, dtype=np.int32)
+        _lib.check(_lib.entry("sluamd_dBatchFactor")(self._b, _pi(info)), "sluamd_dBatchFactor")
+        return info
+
+    def solve(self, b, trans="N", refine=False):
+        """b: [count, n] or [count, n, nrhs] -> (x of the same shape, berr [count, nrhs] or None, steps [count])"""
+        b = np.asarray(b, dtype=np.float64)
+        one = b.ndim == 2
+        b3 = b[:, :, None] if one else b
+        if b3.ndim != 3 or b3.shape[0] != self.count or b3.shape[1] != self.n:
+            raise ValueError(f"b must be [{self.count}, {self.n}] or [{self.count}, {self.n}, nrhs]")
+        nrhs = b3.shape[2]
+        B = np.ascontiguousarray(b3.transpose(0, 2, 1))            # [count, nrhs, n]: every matrix's block column-major
+        X = np.zeros_like(B)
+        berr = np.zeros((self.count, max(nrhs, 1)))
+        steps = np.zeros(self.count, dtype=np.int32)
+        _lib.check(_lib.entry("sluamd_dBatchSolve")(self._b, _trans_code(trans), B.ctypes.data_as(C.c_void_p), self.n, self.n * nrhs,
+                                                    X.ctypes.data_as(C.c_void_p), self.n, self.n * nrhs, nrhs, int(bool(refine)), _pd(berr), _pi(steps)),
+                   "sluamd_dBatchSolve")
+        x = X.transpose(0, 2, 1)
+        return (np.ascontiguousarray(x[:, :, 0]) if one else np.ascontiguousarray(x)), (berr[:, :nrhs] if refine else None), steps
+
+    def handle(self):
+        """the batch's handle, borrowed (an LUHandle-shaped view for stats / setup_times / plan_table; it must not outlive the batch)"""
+        fn = _lib.entry("sluamd_BatchHandle")
+        return C.c_void_p(fn(self._b))
+
+    def stats(self):
+        s = Stats()
+        _lib.load().sluamd_get_stats(self.handle(), C.byref(s))
+        return {f[0]: getattr(s, f[0]) for f in Stats._fields_}
+
+    def destroy(self):
+        if self._b:
+            _lib.entry("sluamd_BatchDestroy")(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def pdgssvx3d_batch(n, rowptr, colind, nzvals, b, perm_c=None, relax=32, maxsup=256, equil=False, refine=False, trans="N", deterministic=False,
+                    keep=False):
+    """The batched expert driver on one rank: `count` systems of one pattern, nzvals [count, nnz], b [count, n] or [count, n, nrhs].  One symbolic
+    factorisation (and, when perm_c is None, one nested-dissection ordering) of ONE matrix serves the batch.  Returns (x, info[count], stats); stats carries
+    the per-matrix berr [count, nrhs] and refine_steps [count] when refine is set, and the BatchHandle under "handle" with keep=True.
+    equil: every matrix is equilibrated on its own; stats then holds equed [count] ("N" / "R" / "C" / "B"), rowcnd, colcnd, amax, anorm, equil_info [count]."""
+    if perm_c is None:
+        perm_c = order_nd(n, rowptr, colind)
+    symb = Symbolic(n, rowptr, colind, perm_c, relax=relax, maxsup=min(int(maxsup), 256))
+    bh = BatchHandle.create(symb, nzvals, deterministic=deterministic)
+    symb.free()
+    try:
+        eq = bh.equilibrate() if equil else None
+        info = bh.factor()
+        x, berr, steps = bh.solve(b, trans=trans, refine=refine)
+        st = bh.stats()
+        st["count"] = bh.count
+        if eq is not None:
+            st["equed"] = [e["equed"] for e in eq]
+            for key in ("rowcnd", "colcnd", "amax", "anorm"):
+                st[key] = np.array([e[key] for e in eq])
+            st["equil_info"] = np.array([e["info"] for e in eq], dtype=np.int32)
+        if refine:
+            st["berr"] = berr
+            st["refine_steps"] = steps
+    except Exception:
+        bh.destroy()
+        raise
+    if keep:
+        st["handle"] = bh
+    else:
+        bh.destroy()
+    return x, info, st
