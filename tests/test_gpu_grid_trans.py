@@ -5,10 +5,12 @@ Floating-point part: the operator of grid_cases.check_own_pipeline, made unsymme
 that mixed up rows and columns, or ran untransposed, misses by O(1).  Both assertions are those grid_cases applies to untransposed grid solves, with the
 same constant: residual on op(A) below 1e-10 and 1e-10 from the solution of a 1 x 1 x 1 handle (grid_trans_cases.check_solution), on every rank.
 Exact part: the integer systems of trans_cases (any summation order gives the integer x, partial sums spread over ranks included: the bound is on absolute
-values) through the view path on 1 x 1 x 2, with the untransposed solve of the same handles asserted exact first, which is what proves the factors.  Not on
-an XY grid: the view path there needs the store cut into every rank's block-cyclic share, which no helper of the tests does, the solve of an XY handle
-refuses values that were not factored on it, and a 2 x 2 x 1 handle made from the CSR values already misses the integer x in its UNTRANSPOSED solve -- so
-nothing exact can be asked of the transposed one there."""
+values) through the view path on 1 x 1 x 2, with the untransposed solve of the same handles asserted exact first, which is what proves the factors.  The two
+cases of this file ("levels", "z_levels") stay on 1 x 1 x 2: the view path on an XY grid needs the store cut into every rank's block-cyclic share, which no
+helper of the tests does, the solve of an XY handle refuses values that were not factored on it, and a 2 x 2 x 1 handle made from the CSR values of "levels"
+misses the integer x already in its UNTRANSPOSED solve (SweepCase does not bound the product-form panel solves of an XY layer entry by entry).  That is a
+limitation of "levels", not of XY handles: the exact tests of the transposed sweeps, refinement and expert solve on XY grids -- the cases whose untransposed
+solve IS exact there -- are in test_gpu_grid_trans_exact.py."""
 import ctypes as C
 import numpy as np
 import pytest
