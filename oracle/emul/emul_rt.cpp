@@ -213,7 +213,30 @@ extern "C" void sluamd_emul_sched_stats(unsigned long long *run, unsigned long l
 // (round 6: the untouched zero pages come from mmap(MAP_NORESERVE) -- calloc of an arena larger than RAM + swap is refused under the kernel's heuristic overcommit)
 static std::map<const char *, size_t> g_fresh_zero, g_mapped;
 static bool lazy_zero() { static const bool on = getenv("SLUAMD_EMUL_LAZY_ZERO") != nullptr; return on; }
+static hipError_t emul_malloc(void **p, size_t n);
+// Allocation checks (tests/test_alloc_failure_cpu.py, scripts/devmem_check.cpp): how many emulated hipMalloc calls have succeeded and are not freed yet, how
+// many were made, and a window of calls that fail with hipErrorOutOfMemory (numbered from the sluamd_emul_alloc_fail call; first < 0: off, count < 0: no end).
+// A failed call leaves the sticky error hipGetLastError returns and clears (per thread, as in HIP).
+static std::atomic<long long> g_live_allocs{0}, g_alloc_count{0}, g_fail_first{-1}, g_fail_end{-1};
+static thread_local hipError_t t_last_error = hipSuccess;
+extern "C" long long sluamd_emul_live_allocs() { return g_live_allocs; }
+extern "C" long long sluamd_emul_alloc_count() { return g_alloc_count; }
+extern "C" void sluamd_emul_alloc_fail(long long first, long long count)
+{
+    const long long now = g_alloc_count;
+    g_fail_end = first < 0 ? -1 : count < 0 ? (long long) 1 << 62 : now + first + count;
+    g_fail_first = first < 0 ? -1 : now + first;
+}
+hipError_t hipGetLastError() { const hipError_t e = t_last_error; t_last_error = hipSuccess; return e; }
 hipError_t hipMalloc(void **p, size_t n)
+{
+    const long long id = g_alloc_count++, f0 = g_fail_first;
+    if (f0 >= 0 && id >= f0 && id < g_fail_end) { *p = nullptr; return t_last_error = hipErrorOutOfMemory; }
+    const hipError_t e = emul_malloc(p, n);
+    if (e == hipSuccess) ++g_live_allocs; else t_last_error = e;
+    return e;
+}
+static hipError_t emul_malloc(void **p, size_t n)
 {
     if (lazy_zero() && n >= ((size_t) 256 << 20)) {
         void *m = mmap(nullptr, n, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
@@ -225,6 +248,7 @@ hipError_t hipMalloc(void **p, size_t n)
 hipError_t hipFree(void *p)
 {
     hipDeviceSynchronize();
+    if (p) --g_live_allocs;
     size_t mapped = 0;
     { Guard lk; g_fresh_zero.erase((const char *) p); auto it = g_mapped.find((const char *) p); if (it != g_mapped.end()) { mapped = it->second; g_mapped.erase(it); } }
     if (mapped) munmap(p, mapped); else std::free(p);
@@ -335,9 +359,9 @@ hipError_t hipDeviceSynchronize()
     return hipSuccess;
 }
 
-// the product's pool of physical device chunks (sluamd_devpool.cpp) has nothing to pool on the host: plain allocations
+// the product's pool of physical device chunks (sluamd_devpool.cpp) has nothing to pool on the host: it declines, the caller allocates plainly
 namespace sluamd {
-int devpool_alloc(void **p, size_t bytes, int) { return hipMalloc(p, bytes) == hipSuccess ? 0 : -4; }
+int devpool_alloc(void **p, size_t, int) { *p = nullptr; return -4; }
 void devpool_free(void *p) { if (p) hipFree(p); }
 void devpool_trim(int) {}
 size_t devpool_cached_bytes(int) { return 0; }

@@ -14,7 +14,7 @@
 
 typedef int hipError_t;
 enum { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorUnknown = 999 };
-inline const char *hipGetErrorString(hipError_t) { return "emulated HIP error"; }
+inline const char *hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "emulated hipErrorOutOfMemory" : "emulated HIP error"; }
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyHostToHost };
 struct emul_stream_s;
 typedef emul_stream_s *hipStream_t;
@@ -61,5 +61,5 @@ inline hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
 inline hipError_t hipDeviceGetPCIBusId(char *buf, int len, int) { if (len > 0) buf[0] = 0; return hipErrorUnknown; }     // (no device behind the emulation)
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
 inline hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
-inline hipError_t hipGetLastError() { return hipSuccess; }
+hipError_t hipGetLastError();   // returns and clears the error a failed emulated hipMalloc left
 hipError_t hipDeviceSynchronize();

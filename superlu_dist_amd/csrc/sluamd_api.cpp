@@ -34,7 +34,7 @@ static int copy_values(Handle *H, const sluamd_dLUview_t *lu, int dir)
     if (rc) return rc;
     char *pin = reinterpret_cast<char *>(H->h_pinned);
     const size_t cap = H->pinned_bytes;
-    char *dv = reinterpret_cast<char *>(H->d_val);
+    char *dv = reinterpret_cast<char *>(H->d_val.p);
     // a piece = bytes of the staging buffer <-> host memory: a contiguous run (perm == null), or elements [e0, e0 + bytes / esz) of an L panel in the handle's
     // row order, whose rows the caller keeps in another order inside its blocks (HostStruct::lrow_perm): element (r, c) of the panel <-> host[perm[r] + c * lda]
     struct Piece { char *host; size_t bytes; const int *perm; int64_t e0; int lda; };
@@ -148,6 +148,7 @@ static int create_from_view(sluamd_handle_t *out, const sluamd_dLUview_t *lu, co
     read_env(H->env);
     auto fail = [&](int code) { sluamd_dDestroyLUHandle(hh); return code; };
     if (hipGetDevice(&H->device) != hipSuccess) { set_error("hipGetDevice failed"); return fail(SLUAMD_EHIP); }
+    H->d_misc.device = H->dist.bufs.device = H->device;
     SlotInput in;
     HostTables t;
     if ((rc = slots_from_view(*H, lu, forests, comm, in))) return fail(rc);
@@ -232,6 +233,7 @@ static int create_from_symb(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_
     read_env(H->env);
     auto fail = [&](int code) { sluamd_dDestroyLUHandle(hh); return code; };
     if (hipGetDevice(&H->device) != hipSuccess) { set_error("hipGetDevice failed"); return fail(SLUAMD_EHIP); }
+    H->d_misc.device = H->dist.bufs.device = H->device;
     SlotInput in;
     HostTables t;
     H->setup.start();
@@ -249,17 +251,16 @@ static int create_from_symb(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_
             if (pos[e] >= 0) { pos2.push_back(pos[e]); ent2.push_back((int) e); for (int q = 0; q < w; ++q) val2.push_back(nzval[e * w + q]); }
         const int64_t nnz = (int64_t) pos2.size();
         const size_t esz = z ? 16 : 8;
-        if (hipMalloc((void **) &H->d_apos, sizeof(int64_t) * std::max<int64_t>(nnz, 1)) != hipSuccess ||
-            hipMalloc((void **) &H->d_aent, sizeof(int) * std::max<int64_t>(nnz, 1)) != hipSuccess ||
-            hipMalloc((void **) &H->d_aval, esz * std::max<int64_t>(nnz, 1)) != hipSuccess) { set_error("hipMalloc failed"); return fail(SLUAMD_ENOMEM); }
+        if ((rc = H->d_apos.alloc(nnz, H->device, "the arena positions of A's entries")) || (rc = H->d_aent.alloc(nnz, H->device, "the CSR indices of A's entries")) ||
+            (rc = H->d_aval.alloc(nnz * w, H->device, "the values of A's entries"))) return fail(rc);
         H->a_nnz = nnz;
         H->a_csr_nnz = (int64_t) pos.size();
         if (nnz) {
-            if (hipMemcpy(H->d_apos, pos2.data(), sizeof(int64_t) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(H->d_aent, ent2.data(), sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(H->d_aval, val2.data(), esz * nnz, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); return fail(SLUAMD_EHIP); }
-            if (z) eng::zscatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, nnz);
-            else eng::scatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, nnz);
+            if (hipMemcpy(H->d_apos.p, pos2.data(), sizeof(int64_t) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(H->d_aent.p, ent2.data(), sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(H->d_aval.p, val2.data(), esz * nnz, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); return fail(SLUAMD_EHIP); }
+            if (z) eng::zscatter_values(H->stream, H->d_val.p, H->d_apos.p, H->d_aval.p, nnz);
+            else eng::scatter_values(H->stream, H->d_val.p, H->d_apos.p, H->d_aval.p, nnz);
         }
         if (hipStreamSynchronize(H->stream) != hipSuccess) { set_error("distribution kernel failed"); return fail(SLUAMD_EHIP); }
         H->setup.lap("values_upload_scatter");
@@ -364,7 +365,7 @@ int sluamd_factor_info(sluamd_handle_t h, int *info, int *tiny)
 {
     if (!h) return SLUAMD_EINVAL;
     int res[8];
-    HIPCHK(hipMemcpy(res, h->H.d_info, sizeof(res), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(res, h->H.d_info.p, sizeof(res), hipMemcpyDeviceToHost));
     if (info) *info = h->H.env.info_last ? res[4] : ((res[0] == 0x7fffffff) ? 0 : res[0]);
     if (tiny) *tiny = res[1];
     return 0;
@@ -412,17 +413,12 @@ int sluamd_pzgstrs3d(sluamd_handle_t h, sluamd_doublecomplex *x, int64_t ldx, in
     Handle *H = &h->H;
     HIPCHK(hipSetDevice(H->device));
     const int64_t need = 2 * ldx * nrhs;   // in doubles
-    if (need > H->x_cap) {
-        if (H->d_x) hipFree(H->d_x);
-        H->d_x = nullptr; H->x_cap = 0;
-        HIPCHK(hipMalloc((void **) &H->d_x, sizeof(double) * need));
-        H->x_cap = need;
-    }
-    HIPCHK(hipMemcpy(H->d_x, x, sizeof(double) * need, hipMemcpyHostToDevice));
+    if (int rc = H->d_x.reserve(need, H->device, "the right-hand sides")) return rc;
+    HIPCHK(hipMemcpy(H->d_x.p, x, sizeof(double) * need, hipMemcpyHostToDevice));
     hipStream_t s = H->stream;
     HIPCHK(hipEventRecord(H->ev0, s));
     {   // the same driver as the double path: level sweeps per Z level, Z exchanges / gather on grids (x seen as 2 n doubles there)
-        const int rc = run_solve_dev(H, H->d_x, ldx, nrhs);
+        const int rc = run_solve_dev(H, H->d_x.p, ldx, nrhs);
         if (rc) return rc;
     }
     HIPCHK(hipGetLastError());
@@ -430,7 +426,7 @@ int sluamd_pzgstrs3d(sluamd_handle_t h, sluamd_doublecomplex *x, int64_t ldx, in
     HIPCHK(hipStreamSynchronize(s));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev0, H->ev1));
     H->st.t_solve_ms = ms;
-    HIPCHK(hipMemcpy(x, H->d_x, sizeof(double) * need, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(x, H->d_x.p, sizeof(double) * need, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -463,21 +459,16 @@ static int solve_dist_host(sluamd_handle_t h, double *B, int64_t ldb, int32_t nr
     const int vs = z ? 2 : 1;
     const int64_t ldd = std::max<int64_t>(m_loc, 1);
     const int64_t need = ldd * nrhs * vs;
-    if (need > H->bloc_cap) {
-        if (H->d_bloc) hipFree(H->d_bloc);
-        H->d_bloc = nullptr; H->bloc_cap = 0;
-        HIPCHK(hipMalloc((void **) &H->d_bloc, sizeof(double) * (size_t) need));
-        H->bloc_cap = need;
-    }
-    for (int q = 0; q < nrhs && m_loc; ++q) HIPCHK(hipMemcpy(H->d_bloc + (size_t) q * ldd * vs, B + (size_t) q * ldb * vs, sizeof(double) * (size_t) m_loc * vs, hipMemcpyHostToDevice));
+    if (int rc = H->d_bloc.reserve(need, H->device, "the local rows of B")) return rc;
+    for (int q = 0; q < nrhs && m_loc; ++q) HIPCHK(hipMemcpy(H->d_bloc.p + (size_t) q * ldd * vs, B + (size_t) q * ldb * vs, sizeof(double) * (size_t) m_loc * vs, hipMemcpyHostToDevice));
     HIPCHK(hipEventRecord(H->ev0, H->stream));
-    int rc = run_solve_dist(H, H->d_bloc, ldd, nrhs, m_loc, fst_row, perm_in, perm_out);
+    int rc = run_solve_dist(H, H->d_bloc.p, ldd, nrhs, m_loc, fst_row, perm_in, perm_out);
     if (rc) return rc;
     HIPCHK(hipEventRecord(H->ev1, H->stream));
     HIPCHK(hipStreamSynchronize(H->stream));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev0, H->ev1));
     H->st.t_solve_ms = ms;
-    for (int q = 0; q < nrhs && m_loc; ++q) HIPCHK(hipMemcpy(B + (size_t) q * ldb * vs, H->d_bloc + (size_t) q * ldd * vs, sizeof(double) * (size_t) m_loc * vs, hipMemcpyDeviceToHost));
+    for (int q = 0; q < nrhs && m_loc; ++q) HIPCHK(hipMemcpy(B + (size_t) q * ldb * vs, H->d_bloc.p + (size_t) q * ldd * vs, sizeof(double) * (size_t) m_loc * vs, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -500,16 +491,11 @@ int sluamd_pdgstrs3d(sluamd_handle_t h, double *x, int64_t ldx, int32_t nrhs)
     Handle *H = &h->H;
     HIPCHK(hipSetDevice(H->device));
     const int64_t need = ldx * nrhs;
-    if (need > H->x_cap) {
-        if (H->d_x) hipFree(H->d_x);
-        H->d_x = nullptr; H->x_cap = 0;
-        HIPCHK(hipMalloc((void **) &H->d_x, sizeof(double) * need));
-        H->x_cap = need;
-    }
-    HIPCHK(hipMemcpy(H->d_x, x, sizeof(double) * need, hipMemcpyHostToDevice));
-    int rc = sluamd_pdgstrs3d_dev(h, H->d_x, ldx, nrhs);
+    if (int rc = H->d_x.reserve(need, H->device, "the right-hand sides")) return rc;
+    HIPCHK(hipMemcpy(H->d_x.p, x, sizeof(double) * need, hipMemcpyHostToDevice));
+    int rc = sluamd_pdgstrs3d_dev(h, H->d_x.p, ldx, nrhs);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(x, H->d_x, sizeof(double) * need, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(x, H->d_x.p, sizeof(double) * need, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -521,19 +507,18 @@ int reset_store(Handle *H, bool scatter)
 {
     HIPCHK(hipSetDevice(H->device));
     H->dinv_ready = false; H->inv_ready = false; H->factored = false;
-    HIPCHK(hipMemsetAsync(H->d_val, 0, (H->z ? 16 : 8) * (size_t) H->own_len, H->stream));
-    if (scatter && H->a_nnz && !H->z) eng::scatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, H->a_nnz);
-    if (scatter && H->a_nnz && H->z) eng::zscatter_values(H->stream, H->d_val, H->d_apos, H->d_aval, H->a_nnz);
+    HIPCHK(hipMemsetAsync(H->d_val.p, 0, (H->z ? 16 : 8) * (size_t) H->own_len, H->stream));
+    if (scatter && H->a_nnz && !H->z) eng::scatter_values(H->stream, H->d_val.p, H->d_apos.p, H->d_aval.p, H->a_nnz);
+    if (scatter && H->a_nnz && H->z) eng::zscatter_values(H->stream, H->d_val.p, H->d_apos.p, H->d_aval.p, H->a_nnz);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 void free_rfs(Handle *H)
 {
-    void **ps[] = {(void **) &H->d_rfs_rp, (void **) &H->d_rfs_ci, (void **) &H->d_rfs_pc, (void **) &H->d_rfs_av, (void **) &H->d_rfs_work, (void **) &H->d_rfs_s,
-                   (void **) &H->d_rfs_tcp, (void **) &H->d_rfs_tri, (void **) &H->d_rfs_tpos,       // (the transposed index belongs to the pattern that goes)
-                   (void **) &H->d_rp_pr, (void **) &H->d_rp_pcpr, (void **) &H->d_rp_rs};          // (and so does the row permutation of sluamd_SetRowPerm)
-    for (void **p : ps) { if (*p) hipFree(*p); *p = nullptr; }
+    H->d_rfs_rp.reset(); H->d_rfs_ci.reset(); H->d_rfs_pc.reset(); H->d_rfs_av.reset(); H->d_rfs_work.reset(); H->d_rfs_s.reset();
+    H->d_rfs_tcp.reset(); H->d_rfs_tri.reset(); H->d_rfs_tpos.reset();       // (the transposed index belongs to the pattern that goes)
+    H->d_rp_pr.reset(); H->d_rp_pcpr.reset(); H->d_rp_rs.reset();            // (and so does the row permutation of sluamd_SetRowPerm)
     H->rfs_nnz = 0;
     H->rfs_z = false;
 }
@@ -549,16 +534,15 @@ int attach_rfs(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, co
     const size_t vs = z ? 2 : 1;      // doubles per value
     free_rfs(H);
     auto bail = [&](const char *what) { set_error(std::string(what) + " failed in " + who); free_rfs(H); return SLUAMD_EHIP; };
-    if (hipMalloc((void **) &H->d_rfs_rp, sizeof(int) * (n + 1)) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void **) &H->d_rfs_ci, sizeof(int) * std::max<int64_t>(nnz, 1)) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void **) &H->d_rfs_av, sizeof(double) * vs * std::max<int64_t>(nnz, 1)) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void **) &H->d_rfs_pc, sizeof(int) * n) != hipSuccess) return bail("hipMalloc");
-    if (hipMalloc((void **) &H->d_rfs_work, sizeof(double) * vs * 3 * (size_t) n) != hipSuccess) return bail("hipMalloc");   // r_perm | b | x
-    if (hipMalloc((void **) &H->d_rfs_s, sizeof(unsigned long long)) != hipSuccess) return bail("hipMalloc");
-    if (hipMemcpy(H->d_rfs_rp, rowptr, sizeof(int) * (n + 1), hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
-    if (hipMemcpy(H->d_rfs_ci, colind, sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
-    if (hipMemcpy(H->d_rfs_av, nzval, sizeof(double) * vs * nnz, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
-    if (hipMemcpy(H->d_rfs_pc, perm_c, sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
+    int rc;
+    if ((rc = H->d_rfs_rp.alloc(n + 1, H->device, "the attached matrix (row pointers)")) || (rc = H->d_rfs_ci.alloc(nnz, H->device, "the attached matrix (column indices)")) ||
+        (rc = H->d_rfs_av.alloc((int64_t) vs * nnz, H->device, "the attached matrix (values)")) || (rc = H->d_rfs_pc.alloc(n, H->device, "the attached matrix (perm_c)")) ||
+        (rc = H->d_rfs_work.alloc((int64_t) vs * 3 * n, H->device, "the refinement work vectors")) ||   // r_perm | b | x
+        (rc = H->d_rfs_s.alloc(1, H->device, "the refinement's backward-error word"))) { free_rfs(H); return rc; }
+    if (hipMemcpy(H->d_rfs_rp.p, rowptr, sizeof(int) * (n + 1), hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
+    if (hipMemcpy(H->d_rfs_ci.p, colind, sizeof(int) * nnz, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
+    if (hipMemcpy(H->d_rfs_av.p, nzval, sizeof(double) * vs * nnz, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
+    if (hipMemcpy(H->d_rfs_pc.p, perm_c, sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess) return bail("hipMemcpy");
     H->rfs_nnz = nnz;
     H->rfs_z = z;
     return 0;
@@ -577,9 +561,9 @@ struct DRfs {   // the double kernels of the refinement driver (sluamd_refine.h)
     static constexpr const char *attach = "sluamd_dAttachMatrix", *other = "sluamd_pzgsrfs3d";
     static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
     {
-        eng::rfs_residual(s, (int) H->hs.n, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, x, b, H->d_rfs_pc, r_perm, H->d_rfs_s, safe1, safe2);
+        eng::rfs_residual(s, (int) H->hs.n, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
     }
-    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x) { eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc, dx_perm, x); }
+    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x) { eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x); }
     static int solve(Handle *H, double *r_perm, int n) { return run_solve_dev(H, r_perm, n, 1); }
 };
 }  // namespace
@@ -606,25 +590,8 @@ void sluamd_dDestroyLUHandle(sluamd_handle_t h)
     if (H->ustream) hipStreamSynchronize(H->ustream);
     if (H->u2stream) hipStreamSynchronize(H->u2stream);
     if (H->rstream) hipStreamSynchronize(H->rstream);
-    for (void *p : H->d_misc) hipFree(p);
-    if (H->d_val) devpool_free(H->d_val);       // (plain allocations are recognised and freed as such)
-    if (H->d_info) hipFree(H->d_info);
-    if (H->d_x) hipFree(H->d_x);
-    if (H->d_xtmp) hipFree(H->d_xtmp);
-    if (H->d_w) hipFree(H->d_w);
-    if (H->d_apos) hipFree(H->d_apos);
-    if (H->d_aval) hipFree(H->d_aval);
-    if (H->d_aent) hipFree(H->d_aent);
-    if (H->d_eq_r) hipFree(H->d_eq_r);
-    if (H->d_eq_c) hipFree(H->d_eq_c);
-    if (H->d_eq_work) hipFree(H->d_eq_work);
-    if (H->d_upd_stage) hipFree(H->d_upd_stage);
-    if (H->d_upd_ij) hipFree(H->d_upd_ij);
     if (H->ev_upd) hipEventDestroy(H->ev_upd);
     if (H->h_pinned) hipHostFree(H->h_pinned);
-    if (H->d_bloc) hipFree(H->d_bloc);
-    for (void *q : H->dist.bufs) hipFree(q);
-    free_rfs(H);
     for (auto &e : H->ev_schur) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &e : H->ev_panel) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &e : H->ev_xchg) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
@@ -640,7 +607,7 @@ void sluamd_dDestroyLUHandle(sluamd_handle_t h)
     for (auto e : H->red_pool) hipEventDestroy(e);
     if (H->red_all) hipEventDestroy(H->red_all);
     if (H->stream) hipStreamDestroy(H->stream);
-    delete h;
+    delete h;      // the device buffers (DevBuf / DevBag / PoolBuf members of Handle) release themselves here
 }
 
 int sluamd_setup_times(sluamd_handle_t h, char *buf, int32_t cap)
@@ -779,7 +746,7 @@ int sluamd_zCreateLUHandleFromSymbGrid(sluamd_handle_t *out, sluamd_symb_t s, co
 // zero-fill + scatter, asynchronous on the handle's stream.
 int sluamd_dResetValues(sluamd_handle_t h)
 {
-    if (!h || !h->H.d_apos) { set_error("handle has no device-side copy of A"); return SLUAMD_EINVAL; }
+    if (!h || !h->H.d_apos.p) { set_error("handle has no device-side copy of A"); return SLUAMD_EINVAL; }
     return reset_store(&h->H, true);
 }
 

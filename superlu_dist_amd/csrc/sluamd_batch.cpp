@@ -17,19 +17,19 @@ struct sluamd_batch_s {
     sluamd_handle_t h = nullptr;        // the handle on the replicated structure (owned)
     int m = 0, count = 0, ns = 0;       // order, matrices, supernodes of ONE matrix
     int64_t nnz = 0;                    // entries of ONE matrix
-    int2 *d_map = nullptr;              // [nnz] (slot, offset inside the slot) of every entry of one matrix
-    int *d_pc = nullptr;                // [m] perm_c of one matrix
-    int64_t *d_dpos = nullptr;          // [count m] arena position of every column's U diagonal entry
-    int *d_info = nullptr;              // [count]
-    int *d_go = nullptr;                // [count] refinement: the matrix continues
-    unsigned long long *d_s = nullptr;  // [count] refinement: backward errors of a sweep
-    double *d_stage = nullptr; int64_t stage_cap = 0;   // host-pointer value updates
-    double *d_xp = nullptr; int64_t xp_cap = 0;         // packed right-hand sides, count m x nrhs
-    double *d_bx = nullptr; int64_t bx_cap = 0;         // host-pointer solves: [B | X]
-    double *d_bs = nullptr; int64_t bs_cap = 0;         // refinement of scaled systems: B' = s_in o B, count m x nrhs
+    DevBuf<int2> d_map;                 // [nnz] (slot, offset inside the slot) of every entry of one matrix
+    DevBuf<int> d_pc;                   // [m] perm_c of one matrix
+    DevBuf<int64_t> d_dpos;             // [count m] arena position of every column's U diagonal entry
+    DevBuf<int> d_info;                 // [count]
+    DevBuf<int> d_go;                   // [count] refinement: the matrix continues
+    DevBuf<unsigned long long> d_s;     // [count] refinement: backward errors of a sweep
+    DevBuf<double> d_stage;                             // host-pointer value updates
+    DevBuf<double> d_xp;                                // packed right-hand sides, count m x nrhs
+    DevBuf<double> d_bx;                                // host-pointer solves: [B | X]
+    DevBuf<double> d_bs;                                // refinement of scaled systems: B' = s_in o B, count m x nrhs
     // sluamd_dBatchEquilibrate: R and C by global row / column (ones where a matrix's equed leaves that side alone), the pdlaqgs decision of every matrix
     // (bit 0: rows, bit 1: columns) on both sides, the per-matrix reduction records {min, max, first zero} x count
-    double *d_r = nullptr, *d_c = nullptr; int *d_mode = nullptr; unsigned long long *d_red = nullptr;
+    DevBuf<double> d_r, d_c; DevBuf<int> d_mode; DevBuf<unsigned long long> d_red;
     std::vector<int> mode;
     bool eq_done = false, scaled = false;               // scaled: some matrix has equed != N
     bool factored = false;
@@ -41,31 +41,15 @@ void batch_free(sluamd_batch_t b)
 {
     if (!b) return;
     if (b->h) { hipSetDevice(b->h->H.device); if (b->h->H.stream) hipStreamSynchronize(b->h->H.stream); }
-    void *ps[] = {b->d_map, b->d_pc, b->d_dpos, b->d_info, b->d_go, b->d_s, b->d_stage, b->d_xp, b->d_bx, b->d_bs, b->d_r, b->d_c, b->d_mode, b->d_red};
-    for (void *p : ps) if (p) hipFree(p);
     if (b->h) sluamd_dDestroyLUHandle(b->h);
-    delete b;
-}
-
-int grow(double **p, int64_t *cap, int64_t need, hipStream_t s, const char *what)
-{
-    if (need <= *cap) return 0;
-    if (*p) { HIPCHK(hipStreamSynchronize(s)); hipFree(*p); }
-    *p = nullptr; *cap = 0;
-    if (hipMalloc((void **) p, sizeof(double) * (size_t) need) != hipSuccess) {
-        (void) hipGetLastError();
-        set_error(std::string("batch: no device memory for ") + what + " (" + std::to_string(need) + " doubles)");
-        return SLUAMD_ENOMEM;
-    }
-    *cap = need;
-    return 0;
+    delete b;       // the buffers release themselves
 }
 
 // the borrowed handle must still be the batch's own: an equilibration or a row permutation made through it would be ignored by the batch's pack / unpack
 int own_state(sluamd_batch_t b, const std::string &me)
 {
     const Handle *H = &b->h->H;
-    if (H->eq_done || H->d_rp_pr) { set_error(me + "the batch's handle was equilibrated or row-permuted through sluamd_BatchHandle: RowPerm and the single-matrix equilibration are not available on a batch (sluamd_dBatchEquilibrate is)"); return SLUAMD_EINVAL; }
+    if (H->eq_done || H->d_rp_pr.p) { set_error(me + "the batch's handle was equilibrated or row-permuted through sluamd_BatchHandle: RowPerm and the single-matrix equilibration are not available on a batch (sluamd_dBatchEquilibrate is)"); return SLUAMD_EINVAL; }
     return 0;
 }
 
@@ -74,7 +58,7 @@ int store_from_attached(sluamd_batch_t b)
 {
     Handle *H = &b->h->H;
     if (int rc = reset_store(H, false)) return rc;
-    beng::batch_values(H->stream, b->nnz, b->count, b->ns, b->nnz, H->d_rfs_av, b->d_map, H->T.sn_lval, H->T.sn_uval, nullptr, H->d_val);
+    beng::batch_values(H->stream, b->nnz, b->count, b->ns, b->nnz, H->d_rfs_av.p, b->d_map.p, H->T.sn_lval, H->T.sn_uval, nullptr, H->d_val.p);
     HIPCHK(hipGetLastError());
     b->factored = false;
     return 0;
@@ -87,15 +71,15 @@ int distribute(sluamd_batch_t b, const double *d_nz, int64_t stride)
     Handle *H = &b->h->H;
     if (!b->scaled) {
         if (int rc = reset_store(H, false)) return rc;
-        beng::batch_values(H->stream, b->nnz, b->count, b->ns, stride, d_nz, b->d_map, H->T.sn_lval, H->T.sn_uval, H->d_rfs_av, H->d_val);
+        beng::batch_values(H->stream, b->nnz, b->count, b->ns, stride, d_nz, b->d_map.p, H->T.sn_lval, H->T.sn_uval, H->d_rfs_av.p, H->d_val.p);
         HIPCHK(hipGetLastError());
         b->factored = false;
         return 0;
     }
     const int64_t n = (int64_t) b->m * b->count;
-    beng::batch_values(H->stream, b->nnz, b->count, b->ns, stride, d_nz, b->d_map, H->T.sn_lval, H->T.sn_uval, H->d_rfs_av, nullptr);
-    HIPCHK(hipMemsetAsync(H->d_rfs_work, 0, sizeof(double) * (size_t) n, H->stream));
-    beng::batch_eq_scale(H->stream, n, b->m, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, b->d_r, b->d_c, b->d_mode, H->d_rfs_work);
+    beng::batch_values(H->stream, b->nnz, b->count, b->ns, stride, d_nz, b->d_map.p, H->T.sn_lval, H->T.sn_uval, H->d_rfs_av.p, nullptr);
+    HIPCHK(hipMemsetAsync(H->d_rfs_work.p, 0, sizeof(double) * (size_t) n, H->stream));
+    beng::batch_eq_scale(H->stream, n, b->m, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, b->d_r.p, b->d_c.p, b->d_mode.p, H->d_rfs_work.p);
     return store_from_attached(b);
 }
 
@@ -107,14 +91,14 @@ int update_values(sluamd_batch_t b, const double *nzval, int64_t stride, bool ho
     if (stride < b->nnz) { set_error(me + "stride is smaller than the number of entries of one matrix"); return SLUAMD_EINVAL; }
     Handle *H = &b->h->H;
     if (int rc = own_state(b, me)) return rc;
-    if (!H->d_rfs_av || H->rfs_nnz != b->nnz * b->count) { set_error(me + "the matrix attached to the batch's handle is not the batch's own block-diagonal matrix"); return SLUAMD_EINVAL; }
+    if (!H->d_rfs_av.p || H->rfs_nnz != b->nnz * b->count) { set_error(me + "the matrix attached to the batch's handle is not the batch's own block-diagonal matrix"); return SLUAMD_EINVAL; }
     HIPCHK(hipSetDevice(H->device));
     const double *d_nz = nzval;
     if (host) {
         const int64_t len = stride * (b->count - 1) + b->nnz;
-        if (int rc = grow(&b->d_stage, &b->stage_cap, len, H->stream, "the staged values")) return rc;
-        HIPCHK(hipMemcpyAsync(b->d_stage, nzval, sizeof(double) * (size_t) len, hipMemcpyHostToDevice, H->stream));
-        d_nz = b->d_stage;
+        if (int rc = b->d_stage.reserve(len, H->device, "the staged values")) return rc;
+        HIPCHK(hipMemcpyAsync(b->d_stage.p, nzval, sizeof(double) * (size_t) len, hipMemcpyHostToDevice, H->stream));
+        d_nz = b->d_stage.p;
     }
     if (int rc = distribute(b, d_nz, stride)) return rc;
     if (host) HIPCHK(hipStreamSynchronize(H->stream));          // the caller may reuse nzval
@@ -128,22 +112,22 @@ int solve_dev(sluamd_batch_t b, int trans, const double *B, int64_t ldb, int64_t
     hipStream_t s = H->stream;
     const int m = b->m, count = b->count;
     const int64_t n = (int64_t) m * count;
-    if (int rc = grow(&b->d_xp, &b->xp_cap, n * nrhs, s, "the packed right-hand sides")) return rc;
+    if (int rc = b->d_xp.reserve(n * nrhs, H->device, "the packed right-hand sides")) return rc;
     // A' = R A C per matrix: op = N scales B by R and X by C, op = T / C the other way round (pdgssvx3d.c:1450-1465, :1806-1821)
-    const double *s_in = !b->scaled ? nullptr : trans == SLUAMD_NOTRANS ? b->d_r : b->d_c, *s_out = !b->scaled ? nullptr : trans == SLUAMD_NOTRANS ? b->d_c : b->d_r;
-    beng::batch_pack(s, m, count, nrhs, b->d_pc, s_in, B, ldb, strideB, b->d_xp, n);
+    const double *s_in = !b->scaled ? nullptr : trans == SLUAMD_NOTRANS ? b->d_r.p : b->d_c.p, *s_out = !b->scaled ? nullptr : trans == SLUAMD_NOTRANS ? b->d_c.p : b->d_r.p;
+    beng::batch_pack(s, m, count, nrhs, b->d_pc.p, s_in, B, ldb, strideB, b->d_xp.p, n);
     HIPCHK(hipGetLastError());
-    if (int rc = sluamd_pdgstrs3d_trans_dev(b->h, trans, b->d_xp, n, nrhs)) return rc;
-    beng::batch_unpack(s, m, count, nrhs, b->d_pc, refine ? nullptr : s_out, b->d_xp, n, X, ldx, strideX);
+    if (int rc = sluamd_pdgstrs3d_trans_dev(b->h, trans, b->d_xp.p, n, nrhs)) return rc;
+    beng::batch_unpack(s, m, count, nrhs, b->d_pc.p, refine ? nullptr : s_out, b->d_xp.p, n, X, ldx, strideX);
     HIPCHK(hipGetLastError());
     if (!refine) { HIPCHK(hipStreamSynchronize(s)); if (steps) std::fill(steps, steps + count, 0); return 0; }
     // the SCALED system is refined, as in the reference: X holds X' (unscaled above), B' = s_in o B goes to a block of its own (matrix k at k m, ld count m),
     // and X = s_out o X' at the end
     int64_t sB = strideB;
     if (b->scaled) {
-        if (int rc = grow(&b->d_bs, &b->bs_cap, n * nrhs, s, "the scaled right-hand sides")) return rc;
-        beng::batch_pack(s, m, count, nrhs, nullptr, s_in, B, ldb, strideB, b->d_bs, n);
-        B = b->d_bs; ldb = n; sB = m;
+        if (int rc = b->d_bs.reserve(n * nrhs, H->device, "the scaled right-hand sides")) return rc;
+        beng::batch_pack(s, m, count, nrhs, nullptr, s_in, B, ldb, strideB, b->d_bs.p, n);
+        B = b->d_bs.p; ldb = n; sB = m;
     }
     // The loop of sluamd_refine.h with lstres, the step count and the continue / stop decision per matrix.  SAFE1 / SAFE2 from m: the constants a matrix
     // would see alone.  One D2H copy of count doubles per sweep; a column ends when no matrix continues; a matrix that has stopped keeps the X and berr of
@@ -151,7 +135,7 @@ int solve_dev(sluamd_batch_t b, int trans, const double *B, int64_t ldb, int64_t
     const int ITMAX = 20;
     const double eps = 0x1p-53, safmin = 2.2250738585072014e-308;
     const double safe1 = (double) (m + 1) * safmin, safe2 = safe1 / eps;
-    double *r_perm = H->d_rfs_work;
+    double *r_perm = H->d_rfs_work.p;
     std::vector<double> sv(count), lstres(count);
     std::vector<int> cnt(count), go(count), live(count);
     for (int j = 0; j < nrhs; ++j) {
@@ -159,9 +143,9 @@ int solve_dev(sluamd_batch_t b, int trans, const double *B, int64_t ldb, int64_t
         double *Xc = X + (size_t) j * ldx;
         std::fill(lstres.begin(), lstres.end(), 3.0); std::fill(cnt.begin(), cnt.end(), 0); std::fill(live.begin(), live.end(), 1);
         for (;;) {
-            HIPCHK(hipMemsetAsync(b->d_s, 0, sizeof(unsigned long long) * count, s));
-            beng::batch_residual(s, n, m, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, Xc, strideX, Bc, sB, H->d_rfs_pc, r_perm, b->d_s, safe1, safe2);
-            HIPCHK(hipMemcpyAsync(sv.data(), b->d_s, sizeof(double) * count, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemsetAsync(b->d_s.p, 0, sizeof(unsigned long long) * count, s));
+            beng::batch_residual(s, n, m, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, Xc, strideX, Bc, sB, H->d_rfs_pc.p, r_perm, b->d_s.p, safe1, safe2);
+            HIPCHK(hipMemcpyAsync(sv.data(), b->d_s.p, sizeof(double) * count, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             int any = 0;
             for (int k = 0; k < count; ++k) {
@@ -173,9 +157,9 @@ int solve_dev(sluamd_batch_t b, int trans, const double *B, int64_t ldb, int64_t
                 any |= go[k];
             }
             if (!any) break;
-            HIPCHK(hipMemcpyAsync(b->d_go, go.data(), sizeof(int) * count, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(b->d_go.p, go.data(), sizeof(int) * count, hipMemcpyHostToDevice, s));
             if (int rc = run_solve_dev(H, r_perm, n, 1)) return rc;
-            beng::batch_update(s, n, m, H->d_rfs_pc, b->d_go, r_perm, Xc, strideX);
+            beng::batch_update(s, n, m, H->d_rfs_pc.p, b->d_go.p, r_perm, Xc, strideX);
             HIPCHK(hipStreamSynchronize(s));          // go[] is pageable host memory, rewritten by the next sweep
             for (int k = 0; k < count; ++k) if (go[k]) { lstres[k] = sv[k]; ++cnt[k]; }
         }
@@ -201,14 +185,14 @@ int solve(sluamd_batch_t b, int trans, const double *B, int64_t ldb, int64_t str
     if (!b->factored) { set_error(me + "the batch holds no factors: call sluamd_dBatchFactor first (value updates leave the batch unfactored)"); return SLUAMD_EINVAL; }
     Handle *H = &b->h->H;
     if (int rc = own_state(b, me)) return rc;
-    if (refine && (!H->d_rfs_rp || H->rfs_z || H->hs.n != (int64_t) b->m * b->count)) { set_error(me + "no double matrix is attached to the batch's handle"); return SLUAMD_EINVAL; }
+    if (refine && (!H->d_rfs_rp.p || H->rfs_z || H->hs.n != (int64_t) b->m * b->count)) { set_error(me + "no double matrix is attached to the batch's handle"); return SLUAMD_EINVAL; }
     if (nrhs == 0) { if (steps) std::fill(steps, steps + b->count, 0); return 0; }
     HIPCHK(hipSetDevice(H->device));
     if (!host) return solve_dev(b, trans, B, ldb, strideB, X, ldx, strideX, nrhs, refine, berr, steps);
     // host pointers: the blocks are staged as they lie (strides kept), B behind X in one buffer
     const int64_t lenB = strideB * (b->count - 1) + ldb * (nrhs - 1) + b->m, lenX = strideX * (b->count - 1) + ldx * (nrhs - 1) + b->m;
-    if (int rc = grow(&b->d_bx, &b->bx_cap, lenB + lenX, H->stream, "the staged right-hand sides and solutions")) return rc;
-    double *dB = b->d_bx, *dX = b->d_bx + lenB;
+    if (int rc = b->d_bx.reserve(lenB + lenX, H->device, "the staged right-hand sides and solutions")) return rc;
+    double *dB = b->d_bx.p, *dX = b->d_bx.p + lenB;
     HIPCHK(hipMemcpy(dB, B, sizeof(double) * (size_t) lenB, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dX, X, sizeof(double) * (size_t) lenX, hipMemcpyHostToDevice));      // (the gaps between the blocks of X go back unchanged)
     if (int rc = solve_dev(b, trans, dB, ldb, strideB, dX, ldx, strideX, nrhs, refine, berr, steps)) return rc;
@@ -275,14 +259,15 @@ int sluamd_dBatchCreate(sluamd_batch_t *out, sluamd_symb_t s, int32_t count, con
             if (!(H->h_flags[K] & SNF_OWN_DIAG)) return fail(SLUAMD_ESTRUCT, "a diagonal block is not stored at the top of its own L slot");     // (always is on 1 x 1 x 1)
             for (int c = H->hs.xsup[K]; c < H->hs.xsup[K + 1]; ++c) dpos[c] = H->h_dptr[K] + (int64_t) (c - H->hs.xsup[K]) * (std::max(H->h_nsupr[K], 1) + 1);
         }
-        if (hipMalloc((void **) &b->d_map, sizeof(int2) * std::max<int64_t>(nnz, 1)) != hipSuccess || hipMalloc((void **) &b->d_pc, sizeof(int) * m) != hipSuccess ||
-            hipMalloc((void **) &b->d_dpos, sizeof(int64_t) * n) != hipSuccess || hipMalloc((void **) &b->d_info, sizeof(int) * count) != hipSuccess ||
-            hipMalloc((void **) &b->d_go, sizeof(int) * count) != hipSuccess || hipMalloc((void **) &b->d_s, sizeof(unsigned long long) * count) != hipSuccess ||
-            hipMalloc((void **) &b->d_mode, sizeof(int) * count) != hipSuccess || hipMalloc((void **) &b->d_red, 3 * sizeof(unsigned long long) * count) != hipSuccess)
-            return fail(SLUAMD_ENOMEM, "hipMalloc failed");
-        if (hipMemcpy(b->d_map, map.data(), sizeof(int2) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(b->d_pc, perm_c_final, sizeof(int) * m, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(b->d_dpos, dpos.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice) != hipSuccess) return fail(SLUAMD_EHIP, "hipMemcpy failed");
+        const int dev = H->device;
+        if ((rc = b->d_map.alloc(nnz, dev, "the batch's entry map")) || (rc = b->d_pc.alloc(m, dev, "the batch's perm_c")) ||
+            (rc = b->d_dpos.alloc(n, dev, "the batch's diagonal positions")) || (rc = b->d_info.alloc(count, dev, "the batch's info words")) ||
+            (rc = b->d_go.alloc(count, dev, "the batch's refinement flags")) || (rc = b->d_s.alloc(count, dev, "the batch's backward-error words")) ||
+            (rc = b->d_mode.alloc(count, dev, "the batch's scaling modes")) || (rc = b->d_red.alloc(3 * (int64_t) count, dev, "the batch's reduction records")))
+            return fail(rc, nullptr);
+        if (hipMemcpy(b->d_map.p, map.data(), sizeof(int2) * nnz, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(b->d_pc.p, perm_c_final, sizeof(int) * m, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(b->d_dpos.p, dpos.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice) != hipSuccess) return fail(SLUAMD_EHIP, "hipMemcpy failed");
     }
     // the store takes the values from the attached copy, through the kernel and the entry map sluamd_dBatchUpdateValues uses: they cross to the device once
     if ((rc = store_from_attached(b))) return fail(rc, nullptr);
@@ -305,9 +290,9 @@ int sluamd_dBatchFactor(sluamd_batch_t b, int32_t *info)
     if (int rc = sluamd_pdgstrf3d(b->h, 0.0, &all)) return rc;
     // per matrix: the smallest column whose U diagonal entry is exactly zero, over a preset of INT_MAX
     std::vector<int> h((size_t) b->count, 0x7fffffff);
-    HIPCHK(hipMemcpyAsync(b->d_info, h.data(), sizeof(int) * b->count, hipMemcpyHostToDevice, H->stream));
-    beng::batch_info(H->stream, (int64_t) b->m * b->count, b->m, b->d_dpos, H->d_val, b->d_info);
-    HIPCHK(hipMemcpyAsync(h.data(), b->d_info, sizeof(int) * b->count, hipMemcpyDeviceToHost, H->stream));
+    HIPCHK(hipMemcpyAsync(b->d_info.p, h.data(), sizeof(int) * b->count, hipMemcpyHostToDevice, H->stream));
+    beng::batch_info(H->stream, (int64_t) b->m * b->count, b->m, b->d_dpos.p, H->d_val.p, b->d_info.p);
+    HIPCHK(hipMemcpyAsync(h.data(), b->d_info.p, sizeof(int) * b->count, hipMemcpyDeviceToHost, H->stream));
     HIPCHK(hipStreamSynchronize(H->stream));
     HIPCHK(hipGetLastError());
     for (int k = 0; k < b->count; ++k) info[k] = h[k] == 0x7fffffff ? 0 : h[k];
@@ -324,23 +309,22 @@ int sluamd_dBatchEquilibrate(sluamd_batch_t b, sluamd_equil_t *out)
     Handle *H = &b->h->H;
     if (int rc = own_state(b, me)) return rc;
     if (b->eq_done) { set_error(me + "the batch has been equilibrated already"); return SLUAMD_EINVAL; }
-    if (!H->d_rfs_av || H->rfs_nnz != b->nnz * b->count) { set_error(me + "the matrix attached to the batch's handle is not the batch's own block-diagonal matrix"); return SLUAMD_EINVAL; }
+    if (!H->d_rfs_av.p || H->rfs_nnz != b->nnz * b->count) { set_error(me + "the matrix attached to the batch's handle is not the batch's own block-diagonal matrix"); return SLUAMD_EINVAL; }
     HIPCHK(hipSetDevice(H->device));
     typedef unsigned long long u64;
     const int m = b->m, count = b->count;
     const int64_t n = (int64_t) m * count, nnz = H->rfs_nnz;
     hipStream_t s = H->stream;
-    if (!b->d_r && (hipMalloc((void **) &b->d_r, sizeof(double) * n) != hipSuccess || hipMalloc((void **) &b->d_c, sizeof(double) * n) != hipSuccess)) {
-        (void) hipGetLastError();
-        if (b->d_r) { hipFree(b->d_r); b->d_r = nullptr; }
-        set_error(me + "no device memory for R and C"); return SLUAMD_ENOMEM;
+    if (!b->d_r) {
+        int rc;
+        if ((rc = b->d_r.alloc(n, H->device, "the batch's row scalings R")) || (rc = b->d_c.alloc(n, H->device, "the batch's column scalings C"))) { b->d_r.reset(); return rc; }
     }
     std::vector<u64> red((size_t) 3 * count), init((size_t) 3 * count);
     for (int k = 0; k < count; ++k) { init[3 * k] = ~0ull; init[3 * k + 1] = 0; init[3 * k + 2] = ~0ull; }
     auto seg = [&](const double *v) -> int {     // red[3 k ..] = {min, max, first zero} of matrix k's part of v
-        HIPCHK(hipMemcpyAsync(b->d_red, init.data(), sizeof(u64) * init.size(), hipMemcpyHostToDevice, s));
-        beng::batch_seg_reduce(s, n, m, v, b->d_red);
-        HIPCHK(hipMemcpyAsync(red.data(), b->d_red, sizeof(u64) * red.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(b->d_red.p, init.data(), sizeof(u64) * init.size(), hipMemcpyHostToDevice, s));
+        beng::batch_seg_reduce(s, n, m, v, b->d_red.p);
+        HIPCHK(hipMemcpyAsync(red.data(), b->d_red.p, sizeof(u64) * red.size(), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
     };
@@ -349,20 +333,20 @@ int sluamd_dBatchEquilibrate(sluamd_batch_t b, sluamd_equil_t *out)
     const double THRESH = 0.1, small = smlnum / 0x1p-52, large = 1.0 / small;
     for (int k = 0; k < count; ++k) out[k] = sluamd_equil_t{SLUAMD_EQUED_N, 0, 0.0, 0.0, 0.0, 0.0};
     // rows (pdgsequ.c:130-169); the global record of eq_rowmax lands in the first slot of d_red and is not read
-    HIPCHK(hipMemcpyAsync(b->d_red, init.data(), sizeof(u64) * 3, hipMemcpyHostToDevice, s));
-    eng::eq_rowmax(s, false, (int) n, nnz, H->d_rfs_rp, H->d_rfs_av, b->d_r, b->d_red);
-    if (int rc = seg(b->d_r)) return rc;
+    HIPCHK(hipMemcpyAsync(b->d_red.p, init.data(), sizeof(u64) * 3, hipMemcpyHostToDevice, s));
+    eng::eq_rowmax(s, false, (int) n, nnz, H->d_rfs_rp.p, H->d_rfs_av.p, b->d_r.p, b->d_red.p);
+    if (int rc = seg(b->d_r.p)) return rc;
     for (int k = 0; k < count; ++k) {
         const double rcmin = std::min(bignum, dbl(red[3 * k])), rcmax = dbl(red[3 * k + 1]);
         out[k].amax = rcmax;
         if (rcmin == 0.0) out[k].info = (int32_t) red[3 * k + 2] + 1;
         else out[k].rowcnd = std::max(rcmin, smlnum) / std::min(rcmax, bignum);
     }
-    eng::eq_invert(s, (int) n, b->d_r, smlnum, bignum);
+    eng::eq_invert(s, (int) n, b->d_r.p, smlnum, bignum);
     // columns under the row scaling (:174-213); a matrix that stopped at a zero row is carried along and not read
-    HIPCHK(hipMemsetAsync(b->d_c, 0, sizeof(double) * (size_t) n, s));
-    eng::eq_colmax(s, false, (int) n, nnz, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, b->d_r, b->d_c);
-    if (int rc = seg(b->d_c)) return rc;
+    HIPCHK(hipMemsetAsync(b->d_c.p, 0, sizeof(double) * (size_t) n, s));
+    eng::eq_colmax(s, false, (int) n, nnz, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, b->d_r.p, b->d_c.p);
+    if (int rc = seg(b->d_c.p)) return rc;
     b->mode.assign(count, 0);
     b->scaled = false;
     for (int k = 0; k < count; ++k) {
@@ -377,14 +361,14 @@ int sluamd_dBatchEquilibrate(sluamd_batch_t b, sluamd_equil_t *out)
         out[k].equed = md == 0 ? SLUAMD_EQUED_N : md == 1 ? SLUAMD_EQUED_R : md == 2 ? SLUAMD_EQUED_C : SLUAMD_EQUED_B;
         if (md) b->scaled = true;
     }
-    eng::eq_invert(s, (int) n, b->d_c, smlnum, bignum);
-    HIPCHK(hipMemcpyAsync(b->d_mode, b->mode.data(), sizeof(int) * count, hipMemcpyHostToDevice, s));
+    eng::eq_invert(s, (int) n, b->d_c.p, smlnum, bignum);
+    HIPCHK(hipMemcpyAsync(b->d_mode.p, b->mode.data(), sizeof(int) * count, hipMemcpyHostToDevice, s));
     // every matrix's own scaling in place + the column sums of what is left; anorm per matrix = the largest of its column sums
-    HIPCHK(hipMemsetAsync(H->d_rfs_work, 0, sizeof(double) * (size_t) n, s));
-    beng::batch_eq_scale(s, n, m, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, b->d_r, b->d_c, b->d_mode, H->d_rfs_work);
-    if (int rc = seg(H->d_rfs_work)) return rc;
+    HIPCHK(hipMemsetAsync(H->d_rfs_work.p, 0, sizeof(double) * (size_t) n, s));
+    beng::batch_eq_scale(s, n, m, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, b->d_r.p, b->d_c.p, b->d_mode.p, H->d_rfs_work.p);
+    if (int rc = seg(H->d_rfs_work.p)) return rc;
     for (int k = 0; k < count; ++k) out[k].anorm = dbl(red[3 * k + 1]);
-    beng::batch_eq_ones(s, n, m, b->d_mode, b->d_r, b->d_c);
+    beng::batch_eq_ones(s, n, m, b->d_mode.p, b->d_r.p, b->d_c.p);
     if (b->scaled) { if (int rc = store_from_attached(b)) return rc; }
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
@@ -399,8 +383,8 @@ int sluamd_BatchGetScalings(sluamd_batch_t b, double *r, double *c)
     const size_t n = (size_t) b->m * b->count;
     if (!b->eq_done) { if (r) std::fill(r, r + n, 1.0); if (c) std::fill(c, c + n, 1.0); return 0; }
     HIPCHK(hipSetDevice(b->h->H.device));
-    if (r) HIPCHK(hipMemcpy(r, b->d_r, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (c) HIPCHK(hipMemcpy(c, b->d_c, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (r) HIPCHK(hipMemcpy(r, b->d_r.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (c) HIPCHK(hipMemcpy(c, b->d_c.p, sizeof(double) * n, hipMemcpyDeviceToHost));
     return 0;
 }
 

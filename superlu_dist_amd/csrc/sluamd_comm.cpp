@@ -5,17 +5,14 @@
 namespace sluamd {
 
 // ---- default host-buffer exchange: stage through device memory and reuse the device point-to-point path ----
-void Comm::hfree_()
-{
-    for (auto &o : hops_) if (o.d) hipFree(o.d);
-    hops_.clear();
-}
+void Comm::hfree_() { hops_.clear(); }
 int Comm::hbegin() { hfree_(); return begin(); }
 int Comm::hsend(const void *buf, int64_t bytes, int dst)
 {
-    void *d = nullptr;
-    if (hipMalloc(&d, (size_t) std::max<int64_t>(bytes, 8)) != hipSuccess) { hfree_(); set_error("hipMalloc of a host-exchange staging buffer failed"); return SLUAMD_ENOMEM; }
-    hops_.push_back({const_cast<void *>(buf), d, bytes, false});
+    HOp o{const_cast<void *>(buf), {}, bytes, false};
+    if (int rc = o.d.alloc(std::max<int64_t>(bytes, 8), -1, "a host-exchange staging buffer")) { hfree_(); return rc; }
+    void *d = o.d.p;
+    hops_.push_back(std::move(o));
     if (hipMemcpy(d, buf, (size_t) bytes, hipMemcpyHostToDevice) != hipSuccess) { hfree_(); set_error("hipMemcpy to a host-exchange staging buffer failed"); return SLUAMD_EHIP; }
     const int rc = send(d, bytes, dst);
     if (rc) hfree_();
@@ -23,9 +20,10 @@ int Comm::hsend(const void *buf, int64_t bytes, int dst)
 }
 int Comm::hrecv(void *buf, int64_t bytes, int src)
 {
-    void *d = nullptr;
-    if (hipMalloc(&d, (size_t) std::max<int64_t>(bytes, 8)) != hipSuccess) { hfree_(); set_error("hipMalloc of a host-exchange staging buffer failed"); return SLUAMD_ENOMEM; }
-    hops_.push_back({buf, d, bytes, true});
+    HOp o{buf, {}, bytes, true};
+    if (int rc = o.d.alloc(std::max<int64_t>(bytes, 8), -1, "a host-exchange staging buffer")) { hfree_(); return rc; }
+    void *d = o.d.p;
+    hops_.push_back(std::move(o));
     const int rc = recv(d, bytes, src);
     if (rc) hfree_();
     return rc;
@@ -40,7 +38,7 @@ int Comm::hend()
     if (!rc && hipStreamSynchronize(hs) != hipSuccess) { set_error("hipStreamSynchronize failed in a host-buffer exchange"); rc = SLUAMD_EHIP; }
     if (!rc)
         for (auto &o : hops_)
-            if (o.is_recv && o.bytes && hipMemcpy(o.h, o.d, (size_t) o.bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("hipMemcpy from a host-exchange staging buffer failed"); rc = SLUAMD_EHIP; break; }
+            if (o.is_recv && o.bytes && hipMemcpy(o.h, o.d.p, (size_t) o.bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("hipMemcpy from a host-exchange staging buffer failed"); rc = SLUAMD_EHIP; break; }
     hipStreamDestroy(hs);
     hfree_();
     return rc;
@@ -263,12 +261,13 @@ int sluamd_comm_selftest(sluamd_comm_t comm, int64_t bytes)
     Comm *c = comm->c;
     const int P = c->grid.size(), me = c->grid.rank(), nxt = (me + 1) % P, prv = (me + P - 1) % P;
     const size_t n = (size_t) bytes;
-    unsigned char *d_src = nullptr, *d_dst = nullptr;
+    DevBuf<unsigned char> src, dst;
     hipStream_t s = nullptr;
     std::vector<unsigned char> h(n), hsrc(n, (unsigned char) (0x50 + me)), hdst(n, 0);
     int rc = 0;
-    auto done = [&](int r, const char *msg) { if (msg) set_error(msg); if (d_src) hipFree(d_src); if (d_dst) hipFree(d_dst); if (s) hipStreamDestroy(s); return r; };
-    if (hipMalloc((void **) &d_src, n) != hipSuccess || hipMalloc((void **) &d_dst, n) != hipSuccess) return done(SLUAMD_ENOMEM, "sluamd_comm_selftest: hipMalloc failed");
+    auto done = [&](int r, const char *msg) { if (msg) set_error(msg); if (s) hipStreamDestroy(s); return r; };
+    if ((rc = src.alloc(bytes, -1, "the send buffer of sluamd_comm_selftest")) || (rc = dst.alloc(bytes, -1, "the receive buffer of sluamd_comm_selftest"))) return rc;
+    unsigned char *const d_src = src.p, *const d_dst = dst.p;
     if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, 0) != hipSuccess) return done(SLUAMD_EHIP, "sluamd_comm_selftest: stream creation failed");
     // (1) device group, stream-ordered: fill(src) -> exchange -> nothing else; the receive buffer is cleared on the same stream first
     if (hipMemsetAsync(d_src, 0xA0 + me, n, s) != hipSuccess || hipMemsetAsync(d_dst, 0, n, s) != hipSuccess) return done(SLUAMD_EHIP, "sluamd_comm_selftest: memset failed");

@@ -42,7 +42,7 @@ struct Comm {
     virtual int hend();
 
 protected:
-    struct HOp { void *h; void *d; int64_t bytes; bool is_recv; };
+    struct HOp { void *h; DevBuf<char> d; int64_t bytes; bool is_recv; };
     std::vector<HOp> hops_;
     void hfree_();   // release the device staging of a (possibly failed) host-buffer group
 };

@@ -21,12 +21,11 @@ struct RcclComm : Comm {
     ncclComm_t nc = nullptr;
     int device = 0;
     static constexpr int RED_MAX = 16;
-    int *d_red = nullptr, *h_red = nullptr;   // device / pinned host image of the values of allreduce_min
+    DevBuf<int> d_red; int *h_red = nullptr;   // device / pinned host image of the values of allreduce_min
     struct Op { void *d; int64_t bytes; int peer; bool is_recv; };
     std::vector<Op> ops;
     ~RcclComm() override
     {
-        if (d_red) hipFree(d_red);
         if (h_red) hipHostFree(h_red);
         if (nc) ncclCommDestroy(nc);
     }
@@ -62,9 +61,9 @@ struct RcclComm : Comm {
         // the null stream (which would serialise against the library's blocking streams)
         if (n > RED_MAX) { set_error("allreduce_min: too many values"); return SLUAMD_EINVAL; }
         std::memcpy(h_red, v, sizeof(int) * (size_t) n);
-        HIPCHK(hipMemcpyAsync(d_red, h_red, sizeof(int) * (size_t) n, hipMemcpyHostToDevice, s));
-        NCCLCHK(ncclAllReduce(d_red, d_red, (size_t) n, ncclInt32, ncclMin, nc, s));
-        HIPCHK(hipMemcpyAsync(h_red, d_red, sizeof(int) * (size_t) n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(d_red.p, h_red, sizeof(int) * (size_t) n, hipMemcpyHostToDevice, s));
+        NCCLCHK(ncclAllReduce(d_red.p, d_red.p, (size_t) n, ncclInt32, ncclMin, nc, s));
+        HIPCHK(hipMemcpyAsync(h_red, d_red.p, sizeof(int) * (size_t) n, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         std::memcpy(v, h_red, sizeof(int) * (size_t) n);
         return 0;
@@ -92,7 +91,7 @@ Comm *make_rccl_comm(const void *id128, const Grid &g, int device)
     std::memcpy(&id, id128, sizeof(id));
     ncclResult_t r = ncclCommInitRank(&c->nc, g.size(), id, g.rank());
     if (r != ncclSuccess) return fail(std::string("ncclCommInitRank failed: ") + ncclGetErrorString(r));
-    if (hipMalloc((void **) &c->d_red, sizeof(int) * RcclComm::RED_MAX) != hipSuccess) return fail("hipMalloc failed");
+    if (c->d_red.alloc(RcclComm::RED_MAX, c->device, "the values of allreduce_min")) { delete c; return nullptr; }
     if (hipHostMalloc((void **) &c->h_red, sizeof(int) * RcclComm::RED_MAX, hipHostMallocDefault) != hipSuccess) return fail("hipHostMalloc failed");
     return c;
 }

@@ -5,9 +5,11 @@
 // maps them under a fresh reservation and creates only what is missing.  VERDICT r5 item 5.
 //
 // Scope: arenas of 1 x 1 x 1 handles only (grid handles keep plain hipMalloc: their ranges are RCCL send / receive buffers, and whether RCCL's peer paths
-// take mapped memory could not be tested on a multi-GPU box).  Everything falls back to hipMalloc when a VMM call fails (SLUAMD_NO_DEVPOOL=1 forces that).
-// The pool holds memory the process does not use: sluamd_device_pool_trim() returns it to the driver, and the library trims by itself and retries when one
-// of its own allocations fails.  The CPU test build has its own trivial version (oracle/emul/emul_rt.cpp).
+// take mapped memory could not be tested on a multi-GPU box).  When a VMM call fails, for arenas under one chunk and under SLUAMD_NO_DEVPOOL=1 the pool
+// declines and the caller (PoolBuf::alloc) allocates plainly.
+// The pool holds memory the process does not use: sluamd_device_pool_trim() returns it to the driver, and every device allocation of the library goes
+// through dev_alloc (sluamd_devmem.h), which trims the pool and tries once more when hipMalloc fails.  The CPU test build has its own trivial version
+// (oracle/emul/emul_rt.cpp).
 #include <algorithm>
 #include <cstdlib>
 #include <map>
@@ -28,7 +30,7 @@ bool pool_off() { static const bool off = getenv("SLUAMD_NO_DEVPOOL") != nullptr
 int devpool_alloc(void **p, size_t bytes, int device)
 {
     *p = nullptr;
-    if (pool_off() || bytes < CHUNK) return hipMalloc(p, std::max<size_t>(bytes, 1)) == hipSuccess ? 0 : SLUAMD_ENOMEM;      // (small arenas: nothing to win)
+    if (pool_off() || bytes < CHUNK) return SLUAMD_ENOMEM;      // (small arenas: nothing to win)
     const size_t nch = (bytes + CHUNK - 1) / CHUNK;
     hipMemAllocationProp prop = {};
     prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = device;
@@ -59,8 +61,7 @@ int devpool_alloc(void **p, size_t bytes, int device)
     if (!ok) {
         if (va) { if (mapped) hipMemUnmap(va, mapped * CHUNK); hipMemAddressFree(va, nch * CHUNK); }
         give_back();
-        devpool_trim(device);         // whatever the pool holds goes back to the driver before the plain allocation is tried
-        return hipMalloc(p, bytes) == hipSuccess ? 0 : SLUAMD_ENOMEM;
+        return SLUAMD_ENOMEM;
     }
     {
         std::lock_guard<std::mutex> lk(g_mu);

@@ -28,7 +28,7 @@ int equilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, c
     if (!h || !rowptr || !colind || !nzval || !perm_c || !out) { set_error(me + "null argument"); return SLUAMD_EINVAL; }
     Handle *H = &h->H;
     if (H->z != z) { set_error(me + (z ? "double handle: call sluamd_dEquilibrate" : "complex16 handle: call sluamd_zEquilibrate")); return SLUAMD_EINVAL; }
-    if (!H->d_aent || H->a_csr_nnz < 0) { set_error(me + "the handle was not created from the symbolic structure (sluamd_[dz]CreateLUHandleFromSymb[Grid]): the caller of a view-created handle scales its own values"); return SLUAMD_EINVAL; }
+    if (!H->d_aent.p || H->a_csr_nnz < 0) { set_error(me + "the handle was not created from the symbolic structure (sluamd_[dz]CreateLUHandleFromSymb[Grid]): the caller of a view-created handle scales its own values"); return SLUAMD_EINVAL; }
     if (n != H->hs.n || rowptr[n] != H->a_csr_nnz) { set_error(me + "n or the number of entries differs from the matrix the handle was created from"); return SLUAMD_EINVAL; }
     if (H->eq_done) { set_error(me + "the handle has been equilibrated already"); return SLUAMD_EINVAL; }
     const double smlnum = 0x1p-1022, bignum = 1.0 / smlnum;          // dmach_dist("S")
@@ -50,16 +50,13 @@ int equilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, c
     *out = sluamd_equil_t{SLUAMD_EQUED_N, 0, 0.0, 0.0, 0.0, 0.0};
     if (n == 0) { out->rowcnd = out->colcnd = 1.0; H->eq_done = true; return 0; }      // pdgsequ.c:114-119
     // eq_done is set on success only: a failed call leaves the handle open for another one, which attaches the caller's (unscaled) values afresh
-    struct Red { unsigned long long *p = nullptr; ~Red() { if (p) hipFree(p); } } red_guard;
-    if (H->d_eq_r) { hipFree(H->d_eq_r); H->d_eq_r = nullptr; }
-    if (H->d_eq_c) { hipFree(H->d_eq_c); H->d_eq_c = nullptr; }
     hipStream_t s = H->stream;
     const int64_t nnz = H->rfs_nnz;
-    u64 *d_red = nullptr;
-    HIPCHK(hipMalloc((void **) &H->d_eq_r, sizeof(double) * n));
-    HIPCHK(hipMalloc((void **) &H->d_eq_c, sizeof(double) * n));
-    HIPCHK(hipMalloc((void **) &d_red, 3 * sizeof(u64)));
-    red_guard.p = d_red;
+    DevBuf<u64> red_buf;
+    if (int rc = H->d_eq_r.alloc(n, H->device, "the row scalings R")) return rc;
+    if (int rc = H->d_eq_c.alloc(n, H->device, "the column scalings C")) return rc;
+    if (int rc = red_buf.alloc(3, H->device, "the reduction words of the equilibration")) return rc;
+    u64 *const d_red = red_buf.p;
     // the three global values of one reduction launch: {min, max, first index of an exact zero}
     u64 red[3];
     auto reset = [&]() { const u64 init[3] = {~0ull, 0ull, ~0ull}; return hipMemcpyAsync(d_red, init, sizeof init, hipMemcpyHostToDevice, s) == hipSuccess ? hipStreamSynchronize(s) : hipErrorUnknown; };
@@ -67,30 +64,30 @@ int equilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, c
     int mode = 0;                                                   // bit 0: rows, bit 1: columns
     if (with) {   // amax of the unscaled matrix (the row maxima land in the work vector the column sums zero-fill below); R and C as given
         HIPCHK(reset());
-        eng::eq_rowmax(s, z, n, nnz, H->d_rfs_rp, H->d_rfs_av, H->d_rfs_work, d_red);
+        eng::eq_rowmax(s, z, n, nnz, H->d_rfs_rp.p, H->d_rfs_av.p, H->d_rfs_work.p, d_red);
         HIPCHK(fetch());
         out->amax = as_double(red[1]);
         out->rowcnd = cnd[0]; out->colcnd = cnd[1];
-        if (r_in) HIPCHK(hipMemcpyAsync(H->d_eq_r, r_in, sizeof(double) * n, hipMemcpyHostToDevice, s));
-        if (c_in) HIPCHK(hipMemcpyAsync(H->d_eq_c, c_in, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        if (r_in) HIPCHK(hipMemcpyAsync(H->d_eq_r.p, r_in, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        if (c_in) HIPCHK(hipMemcpyAsync(H->d_eq_c.p, c_in, sizeof(double) * n, hipMemcpyHostToDevice, s));
         mode = (r_in ? 1 : 0) | (c_in ? 2 : 0);
     } else do {
         HIPCHK(reset());
-        eng::eq_rowmax(s, z, n, nnz, H->d_rfs_rp, H->d_rfs_av, H->d_eq_r, d_red);
+        eng::eq_rowmax(s, z, n, nnz, H->d_rfs_rp.p, H->d_rfs_av.p, H->d_eq_r.p, d_red);
         HIPCHK(fetch());
         double rcmin = std::min(bignum, as_double(red[0])), rcmax = as_double(red[1]);
         out->amax = rcmax;
         if (rcmin == 0.0) { out->info = (int32_t) red[2] + 1; break; }                     // pdgsequ.c:158-164
-        eng::eq_invert(s, n, H->d_eq_r, smlnum, bignum);
+        eng::eq_invert(s, n, H->d_eq_r.p, smlnum, bignum);
         out->rowcnd = std::max(rcmin, smlnum) / std::min(rcmax, bignum);
-        HIPCHK(hipMemsetAsync(H->d_eq_c, 0, sizeof(double) * n, s));
-        eng::eq_colmax(s, z, n, nnz, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, H->d_eq_r, H->d_eq_c);
+        HIPCHK(hipMemsetAsync(H->d_eq_c.p, 0, sizeof(double) * n, s));
+        eng::eq_colmax(s, z, n, nnz, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, H->d_eq_r.p, H->d_eq_c.p);
         HIPCHK(reset());
-        eng::eq_reduce(s, n, H->d_eq_c, d_red);
+        eng::eq_reduce(s, n, H->d_eq_c.p, d_red);
         HIPCHK(fetch());
         rcmin = std::min(bignum, as_double(red[0])); rcmax = as_double(red[1]);
         if (rcmin == 0.0) { out->info = n + (int32_t) red[2] + 1; break; }                 // pdgsequ.c:202-208
-        eng::eq_invert(s, n, H->d_eq_c, smlnum, bignum);
+        eng::eq_invert(s, n, H->d_eq_c.p, smlnum, bignum);
         out->colcnd = std::max(rcmin, smlnum) / std::min(rcmax, bignum);
         // pdlaqgs.c:107-146
         const double THRESH = 0.1, small = smlnum / 0x1p-52, large = 1.0 / small;          // dmach("Safe minimum") / dmach("Precision")
@@ -98,32 +95,22 @@ int equilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, c
         else mode = out->colcnd >= THRESH ? 1 : 3;
     } while (0);
     // scaling in place + the 1-norm of what is left (mode 0: the norm alone); the column sums go through the refinement's work vector
-    double *colsum = H->d_rfs_work;
+    double *colsum = H->d_rfs_work.p;
     HIPCHK(hipMemsetAsync(colsum, 0, sizeof(double) * n, s));
-    eng::eq_scale_norm(s, z, n, nnz, H->d_rfs_rp, H->d_rfs_ci, H->d_rfs_av, H->d_eq_r, H->d_eq_c, mode, colsum);
+    eng::eq_scale_norm(s, z, n, nnz, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, H->d_eq_r.p, H->d_eq_c.p, mode, colsum);
     HIPCHK(reset());
     eng::eq_reduce(s, n, colsum, d_red);
     HIPCHK(fetch());
     out->anorm = as_double(red[1]);
     out->equed = mode == 0 ? SLUAMD_EQUED_N : mode == 1 ? SLUAMD_EQUED_R : mode == 2 ? SLUAMD_EQUED_C : SLUAMD_EQUED_B;
     if (mode) {   // the store takes the scaled values (equed == N: it holds them already)
-        eng::eq_gather(s, z, H->a_nnz, H->d_aent, H->d_rfs_av, H->d_aval);
+        eng::eq_gather(s, z, H->a_nnz, H->d_aent.p, H->d_rfs_av.p, H->d_aval.p);
         if (int rc = sluamd_dResetValues(h)) return rc;
     }
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     H->eq_row = (mode & 1) != 0; H->eq_col = (mode & 2) != 0;
     H->eq_done = true;
-    return 0;
-}
-
-int ensure_work(Handle *H, int64_t doubles)
-{
-    if (doubles <= H->eq_work_cap) return 0;
-    if (H->d_eq_work) hipFree(H->d_eq_work);
-    H->d_eq_work = nullptr; H->eq_work_cap = 0;
-    HIPCHK(hipMalloc((void **) &H->d_eq_work, sizeof(double) * (size_t) doubles));
-    H->eq_work_cap = doubles;
     return 0;
 }
 
@@ -136,7 +123,7 @@ int check_solve(sluamd_handle_t h, int trans, const void *B, int64_t ldb, const 
     if (trans != SLUAMD_NOTRANS && trans != SLUAMD_TRANS && trans != SLUAMD_CONJ) { set_error(me + "trans must be SLUAMD_NOTRANS, SLUAMD_TRANS or SLUAMD_CONJ"); return SLUAMD_EINVAL; }
     const Handle *H = &h->H;
     if (H->z != z) { set_error(me + (z ? "double handle: call sluamd_pdgssvx3d_solve" : "complex16 handle: call sluamd_pzgssvx3d_solve")); return SLUAMD_EINVAL; }
-    if (!H->d_rfs_pc || H->rfs_z != z) { set_error(me + "no matrix attached (perm_c): call sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix first"); return SLUAMD_EINVAL; }
+    if (!H->d_rfs_pc.p || H->rfs_z != z) { set_error(me + "no matrix attached (perm_c): call sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix first"); return SLUAMD_EINVAL; }
     if (refine && trans != SLUAMD_NOTRANS) { set_error(me + "refine with a transposed system is not part of this call: solve with refine = 0, then refine the attached (scaled) system with sluamd_p[dz]gsrfs3d_trans"); return SLUAMD_EINVAL; }
     if (trans != SLUAMD_NOTRANS && H->grid.size() > 1 && !H->xt_ready) { set_error(me + "transposed solves need a 1 x 1 x 1 handle, or a grid handle after sluamd_PlanTransposedSweeps"); return SLUAMD_EINVAL; }
     if (steps) *steps = 0;
@@ -152,15 +139,15 @@ int solve_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, doub
     const bool z = H->z;
     const int n = (int) H->hs.n;
     hipStream_t s = H->stream;
-    const double *R = H->eq_row ? H->d_eq_r : nullptr, *Cs = H->eq_col ? H->d_eq_c : nullptr;
+    const double *R = H->eq_row ? H->d_eq_r.p : nullptr, *Cs = H->eq_col ? H->d_eq_c.p : nullptr;
     const double *s_in = trans == SLUAMD_NOTRANS ? R : Cs, *s_out = trans == SLUAMD_NOTRANS ? Cs : R;      // pdgssvx3d.c:1450-1465, :1806-1821
     // sluamd_SetRowPerm: the handle holds Pr A, B and X are in A's ordering.  Row i of A is row perm_r[i] of the attached system, so whatever is indexed by
     // the ROWS -- B and R of op = N, X and R of op = T / C -- goes through perm_r; the column side is untouched
-    const int *p_in = H->d_rfs_pc, *p_out = H->d_rfs_pc, *p_rows = nullptr;
-    if (H->d_rp_pr) {
-        p_rows = H->d_rp_pr;
-        if (trans == SLUAMD_NOTRANS) { p_in = H->d_rp_pcpr; if (R) s_in = H->d_rp_rs; }
-        else { p_out = H->d_rp_pcpr; if (R) s_out = H->d_rp_rs; }
+    const int *p_in = H->d_rfs_pc.p, *p_out = H->d_rfs_pc.p, *p_rows = nullptr;
+    if (H->d_rp_pr.p) {
+        p_rows = H->d_rp_pr.p;
+        if (trans == SLUAMD_NOTRANS) { p_in = H->d_rp_pcpr.p; if (R) s_in = H->d_rp_rs.p; }
+        else { p_out = H->d_rp_pcpr.p; if (R) s_out = H->d_rp_rs.p; }
     }
     eng::eq_permscale(s, z, false, n, nrhs, p_in, s_in, d_B, ldb, xp, n);
     HIPCHK(hipGetLastError());
@@ -191,12 +178,12 @@ int solve_entry(sluamd_handle_t h, int trans, const void *B, int64_t ldb, void *
     HIPCHK(hipSetDevice(H->device));
     const int vs = z ? 2 : 1;
     const int64_t n = H->hs.n, blk = n * nrhs * vs;              // doubles of one n x nrhs block
-    if (int rc = ensure_work(H, host ? 3 * blk : blk)) return rc;
-    if (!host) return solve_dev(h, trans, (const double *) B, ldb, (double *) X, ldx, nrhs, refine, berr, steps, H->d_eq_work);
-    double *d_b = H->d_eq_work + blk, *d_x = H->d_eq_work + 2 * blk;
+    if (int rc = H->d_eq_work.reserve(host ? 3 * blk : blk, H->device, "the work block of the expert solve")) return rc;
+    if (!host) return solve_dev(h, trans, (const double *) B, ldb, (double *) X, ldx, nrhs, refine, berr, steps, H->d_eq_work.p);
+    double *d_b = H->d_eq_work.p + blk, *d_x = H->d_eq_work.p + 2 * blk;
     const size_t row = sizeof(double) * (size_t) n * vs;
     HIPCHK(hipMemcpy2D(d_b, row, B, sizeof(double) * (size_t) ldb * vs, row, (size_t) nrhs, hipMemcpyHostToDevice));
-    if (int rc = solve_dev(h, trans, d_b, n, d_x, n, nrhs, refine, berr, steps, H->d_eq_work)) return rc;
+    if (int rc = solve_dev(h, trans, d_b, n, d_x, n, nrhs, refine, berr, steps, H->d_eq_work.p)) return rc;
     HIPCHK(hipMemcpy2D(X, sizeof(double) * (size_t) ldx * vs, d_x, row, row, (size_t) nrhs, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -234,7 +221,7 @@ int sluamd_SetRowPerm(sluamd_handle_t h, const sluamd_int_t *perm_r)
     const std::string me = "sluamd_SetRowPerm: ";
     if (!h || !perm_r) { set_error(me + "null argument"); return SLUAMD_EINVAL; }
     Handle *H = &h->H;
-    if (!H->d_rfs_pc) { set_error(me + "no matrix attached (perm_c): call sluamd_[dz]EquilibrateWith, sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix first"); return SLUAMD_EINVAL; }
+    if (!H->d_rfs_pc.p) { set_error(me + "no matrix attached (perm_c): call sluamd_[dz]EquilibrateWith, sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix first"); return SLUAMD_EINVAL; }
     if (H->factored) { set_error(me + "the handle holds factors: set the row permutation before the factorisation"); return SLUAMD_EINVAL; }
     const int64_t n = H->hs.n;
     std::vector<uint8_t> seen((size_t) n, 0);
@@ -244,16 +231,15 @@ int sluamd_SetRowPerm(sluamd_handle_t h, const sluamd_int_t *perm_r)
         seen[j] = 1;
     }
     HIPCHK(hipSetDevice(H->device));
-    void **ps[] = {(void **) &H->d_rp_pr, (void **) &H->d_rp_pcpr, (void **) &H->d_rp_rs};
-    auto drop = [&]() { for (void **p : ps) { if (*p) hipFree(*p); *p = nullptr; } };
+    auto drop = [&]() { H->d_rp_pr.reset(); H->d_rp_pcpr.reset(); H->d_rp_rs.reset(); };
     drop();
     if (n == 0) return 0;
-    hipError_t e = hipMalloc((void **) &H->d_rp_pr, sizeof(int) * (size_t) n);
-    if (e == hipSuccess) e = hipMalloc((void **) &H->d_rp_pcpr, sizeof(int) * (size_t) n);
-    if (e == hipSuccess && H->eq_row) e = hipMalloc((void **) &H->d_rp_rs, sizeof(double) * (size_t) n);
-    if (e == hipSuccess) e = hipMemcpyAsync(H->d_rp_pr, perm_r, sizeof(int) * (size_t) n, hipMemcpyHostToDevice, H->stream);
+    int rc;
+    if ((rc = H->d_rp_pr.alloc(n, H->device, "the row permutation perm_r")) || (rc = H->d_rp_pcpr.alloc(n, H->device, "the composed permutation perm_c o perm_r")) ||
+        (H->eq_row && (rc = H->d_rp_rs.alloc(n, H->device, "the permuted row scalings")))) { drop(); return rc; }
+    hipError_t e = hipMemcpyAsync(H->d_rp_pr.p, perm_r, sizeof(int) * (size_t) n, hipMemcpyHostToDevice, H->stream);
     if (e == hipSuccess) {
-        eng::rp_compose(H->stream, (int) n, H->d_rp_pr, H->d_rfs_pc, H->eq_row ? H->d_eq_r : nullptr, H->d_rp_pcpr, H->d_rp_rs);
+        eng::rp_compose(H->stream, (int) n, H->d_rp_pr.p, H->d_rfs_pc.p, H->eq_row ? H->d_eq_r.p : nullptr, H->d_rp_pcpr.p, H->d_rp_rs.p);
         e = hipStreamSynchronize(H->stream);
     }
     if (e == hipSuccess) e = hipGetLastError();
@@ -267,8 +253,8 @@ int sluamd_GetScalings(sluamd_handle_t h, double *r, double *c)
     Handle *H = &h->H;
     HIPCHK(hipSetDevice(H->device));
     const size_t n = (size_t) H->hs.n;
-    if (r) { if (H->eq_row) HIPCHK(hipMemcpy(r, H->d_eq_r, sizeof(double) * n, hipMemcpyDeviceToHost)); else std::fill(r, r + n, 1.0); }
-    if (c) { if (H->eq_col) HIPCHK(hipMemcpy(c, H->d_eq_c, sizeof(double) * n, hipMemcpyDeviceToHost)); else std::fill(c, c + n, 1.0); }
+    if (r) { if (H->eq_row) HIPCHK(hipMemcpy(r, H->d_eq_r.p, sizeof(double) * n, hipMemcpyDeviceToHost)); else std::fill(r, r + n, 1.0); }
+    if (c) { if (H->eq_col) HIPCHK(hipMemcpy(c, H->d_eq_c.p, sizeof(double) * n, hipMemcpyDeviceToHost)); else std::fill(c, c + n, 1.0); }
     return 0;
 }
 

@@ -40,8 +40,8 @@ static int exchange(Handle *H, const std::vector<XMsg> &sends, const std::vector
     int rc = c->begin();
     if (rc) return rc;
     const int vs = H->z ? 2 : 1;     // doubles per value (arena offsets / lengths are in values)
-    for (auto &m : sends) if ((rc = c->send(H->d_val + m.off * vs, m.len * 8 * vs, m.peer))) return rc;
-    for (auto &m : recvs) if ((rc = c->recv(H->d_val + m.off * vs, m.len * 8 * vs, m.peer))) return rc;
+    for (auto &m : sends) if ((rc = c->send(H->d_val.p + m.off * vs, m.len * 8 * vs, m.peer))) return rc;
+    for (auto &m : recvs) if ((rc = c->recv(H->d_val.p + m.off * vs, m.len * 8 * vs, m.peer))) return rc;
     return c->end(s);
 }
 
@@ -58,10 +58,10 @@ static void group_inverse(Handle *H, int gi, hipStream_t st)
 {
     const Handle::SolveGroup &G = H->groups[gi];
     hipMemsetAsync(H->T.inv + G.ginv, 0, sizeof(double) * (size_t) 2 * G.nG * G.nG, st);
-    hipMemsetAsync(H->d_gscr, 0, sizeof(double) * (size_t) (2 * GRP_SCR), st);       // LG | UG (the sums TL / TU are written before they are read)
-    eng::grp_gather(st, H->T, H->d_grpdesc + gi, H->d_gscr);
+    hipMemsetAsync(H->d_gscr.p, 0, sizeof(double) * (size_t) (2 * GRP_SCR), st);       // LG | UG (the sums TL / TU are written before they are read)
+    eng::grp_gather(st, H->T, H->d_grpdesc + gi, H->d_gscr.p);
     for (int q = 0; q + 1 < 7; ++q)
-        if (G.tile_off[q + 1] > G.tile_off[q]) { eng::gemm_batched(st, H->T, H->d_gemmdesc, H->d_gemmtiles + G.tile_off[q], G.tile_off[q + 1] - G.tile_off[q], H->d_gscr); H->st.num_launches++; }
+        if (G.tile_off[q + 1] > G.tile_off[q]) { eng::gemm_batched(st, H->T, H->d_gemmdesc, H->d_gemmtiles + G.tile_off[q], G.tile_off[q + 1] - G.tile_off[q], H->d_gscr.p); H->st.num_launches++; }
     H->st.num_launches += 1;
 }
 
@@ -104,18 +104,19 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
             // they go back to the driver when the records need the room.)
             const size_t cached = devpool_cached_bytes(H->device);
             if (bytes > 0 && bytes + tot / 10 >= fr && bytes + tot / 10 < fr + cached) { devpool_trim(H->device); hipMemGetInfo(&fr, &tot); }
-            if (bytes > 0 && bytes + tot / 10 < fr && hipMalloc((void **) &S.d_tmaps, bytes) == hipSuccess) {
-                H->d_misc.push_back(S.d_tmaps);
+            // (the one caller that ignores dev_alloc's verdict: without the records the tiles chase their tables)
+            if (bytes > 0 && bytes + tot / 10 < fr && S.d_tmaps.alloc(S.m_off[2 * S.nlevels], H->device, "the tile records of the Schur update") != 0) set_error("");
+            if (S.d_tmaps) {
                 for (int l = 0; l < S.nlevels; ++l)
                     for (int g = 0; g < 2; ++g) {
                         const int u0 = S.u_off[(2 * l + g) * 4], nu = S.u_off[(2 * l + g) * 4 + 4] - u0;
                         if (!nu) continue;
-                        if (H->z) eng::zschur(s, g == 0 ? 0 : 1, T, nullptr, nullptr, 0, 0, nu, H->d_info, S.d_ulist + u0, 0, S.d_tmaps + S.m_off[2 * l + g], 1);
-                        else eng::schur(s, g == 0 ? (H->env.schur_4waves ? 1 : 0) : 2, T, nullptr, nullptr, 0, 0, nu, H->d_info, S.d_ulist + u0, 0, S.d_tmaps + S.m_off[2 * l + g], 1);
+                        if (H->z) eng::zschur(s, g == 0 ? 0 : 1, T, nullptr, nullptr, 0, 0, nu, H->d_info.p, S.d_ulist + u0, 0, S.d_tmaps.p + S.m_off[2 * l + g], 1);
+                        else eng::schur(s, g == 0 ? (H->env.schur_4waves ? 1 : 0) : 2, T, nullptr, nullptr, 0, 0, nu, H->d_info.p, S.d_ulist + u0, 0, S.d_tmaps.p + S.m_off[2 * l + g], 1);
                     }
                 S.maps_state = 1;
                 H->st.bytes_device += (int64_t) bytes;
-            } else (void) hipGetLastError();
+            }
         }
     }
     auto schur = [&](hipStream_t st, bool big, int ntile, const int *nodes, const int *prefix, int nn, int id_base,
@@ -123,8 +124,8 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         if (H->profile && H->env.profile_dump) H->schur_rec.push_back({cur_level, cur_pass, big ? 1 : 0, ntile, S.max_nsupc[cur_level]});
         if (H->profile) { if (H->ev_schur_big.size() <= H->ev_schur_used) H->ev_schur_big.resize(H->ev_schur_used + 1); H->ev_schur_big[H->ev_schur_used] = big ? 1 : 0; }
         ev_begin(H, H->ev_schur, H->ev_schur_used, st);
-        if (H->z) eng::zschur(st, big ? 0 : 1, T, nodes, prefix, nn, id_base, ntile, H->d_info, ulist, prio, tmaps, tmaps ? 2 : 0, xoff, xmax);     // complex16: k_schur on the real embedding
-        else eng::schur(st, big ? (H->env.schur_4waves ? 1 : 0) : 2, T, nodes, prefix, nn, id_base, ntile, H->d_info, ulist, prio, tmaps, tmaps ? 2 : 0, ksplit, xoff, xmax);
+        if (H->z) eng::zschur(st, big ? 0 : 1, T, nodes, prefix, nn, id_base, ntile, H->d_info.p, ulist, prio, tmaps, tmaps ? 2 : 0, xoff, xmax);     // complex16: k_schur on the real embedding
+        else eng::schur(st, big ? (H->env.schur_4waves ? 1 : 0) : 2, T, nodes, prefix, nn, id_base, ntile, H->d_info.p, ulist, prio, tmaps, tmaps ? 2 : 0, ksplit, xoff, xmax);
         ev_end(H, H->ev_schur, H->ev_schur_used, st);
         H->st.num_launches++; H->st.schur_launches++; H->st.schur_tiles += ntile;
     };
@@ -155,9 +156,9 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         }
         ev_begin(H, H->ev_panel, H->ev_panel_used, ps);
         if (H->z) {   // Local_Zgstrf2 (pzgstrf2.c); the complex panel solves substitute on the factored block: no inverses
-            eng::zdiag_lu(ps, T, nodes, nn, mx, H->opt.replace_tiny_pivot, thresh, H->d_info);
+            eng::zdiag_lu(ps, T, nodes, nn, mx, H->opt.replace_tiny_pivot, thresh, H->d_info.p);
             if (xy) {   // zDiagFactIBCast (ztrfCommWrapper.c): packed diagonal blocks down the process column and along the process row
-                eng::pack_diag(ps, T, nodes, S.d_dg_prefix + po, S.d_dg_off + po, nn, S.dg_prefix[po + nn], H->d_val + 2 * S.dg_stage_off[l], 2);
+                eng::pack_diag(ps, T, nodes, S.d_dg_prefix + po, S.d_dg_off + po, nn, S.dg_prefix[po + nn], H->d_val.p + 2 * S.dg_stage_off[l], 2);
                 ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
                 if (!rc_x) rc_x = exchange(H, S.x_diag_send[l], S.x_diag_recv[l], ps);
                 ev_end(H, H->ev_xchg, H->ev_xchg_used, ps);
@@ -168,9 +169,9 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         }
         // bit 2: the single-supernode levels at the top of the tree get the diagonal kernel built for the whole register file (no scratch)
         const int big_regs = (H->env.diag_tail > 0 && nn == 1 && l >= S.nlevels - H->env.diag_tail) ? 4 : 0;
-        eng::diag_lu(ps, T, nodes, nn, mx, (H->opt.replace_tiny_pivot ? 1 : 0) | (H->env.diag_v1 ? 2 : 0) | big_regs, thresh, H->d_info);   // Local_Dgstrf2 (+ dinv of the owned blocks)
+        eng::diag_lu(ps, T, nodes, nn, mx, (H->opt.replace_tiny_pivot ? 1 : 0) | (H->env.diag_v1 ? 2 : 0) | big_regs, thresh, H->d_info.p);   // Local_Dgstrf2 (+ dinv of the owned blocks)
         if (xy) {   // dDiagFactIBCast (dtrfCommWrapper.c:32-118): diagonal blocks down the process column and along the process row
-            eng::pack_diag(ps, T, nodes, S.d_dg_prefix + po, S.d_dg_off + po, nn, S.dg_prefix[po + nn], H->d_val + S.dg_stage_off[l]);
+            eng::pack_diag(ps, T, nodes, S.d_dg_prefix + po, S.d_dg_off + po, nn, S.dg_prefix[po + nn], H->d_val.p + S.dg_stage_off[l]);
             ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
             if (!rc_x) rc_x = exchange(H, S.x_diag_send[l], S.x_diag_recv[l], ps);
             ev_end(H, H->ev_xchg, H->ev_xchg_used, ps);
@@ -245,7 +246,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
             const int cnt = g == 0 ? nbig : nn - nbig;
             if (!cnt) continue;
             const int u0 = S.u_off[(2 * l + g) * 4 + p0], nu = S.u_off[(2 * l + g) * 4 + p1 + 1] - u0;
-            const int *tm = S.maps_state == 1 ? S.d_tmaps + S.m_off[2 * l + g] + (int64_t) (u0 - S.u_off[(2 * l + g) * 4]) * eng::schur_rec_ints(g == 0 ? 0 : 2, H->z) : nullptr;
+            const int *tm = S.maps_state == 1 ? S.d_tmaps.p + S.m_off[2 * l + g] + (int64_t) (u0 - S.u_off[(2 * l + g) * 4]) * eng::schur_rec_ints(g == 0 ? 0 : 2, H->z) : nullptr;
             // the diagonal-block tiles of the next level (part 0, on the panel stream) when they are few: split K over several workgroups per tile
             const int ks = (lookahead && p0 == 0 && p1 == 0 && g == 0 && nu <= 64 && !H->z && !H->env.schur_4waves) ? H->env.ksplit : 1;
             // a launch of the bulk alone: the XCDs' ranges of equal modelled cost (balance_bulk)
@@ -355,15 +356,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
     return rc_x;
 }
 
-static int ensure_xtmp(Handle *H, int64_t doubles)
-{
-    if (doubles <= H->xtmp_cap) return 0;
-    if (H->d_xtmp) hipFree(H->d_xtmp);
-    H->d_xtmp = nullptr; H->xtmp_cap = 0;
-    if (hipMalloc((void **) &H->d_xtmp, sizeof(double) * (size_t) doubles) != hipSuccess) { set_error("hipMalloc of the exchange buffer failed"); return SLUAMD_ENOMEM; }
-    H->xtmp_cap = doubles;
-    return 0;
-}
+static int ensure_xtmp(Handle *H, int64_t doubles) { return H->d_xtmp.reserve(doubles, H->device, "the exchange staging buffer"); }
 
 // own-slot ranges [L | U] of the ancestor forests above Z level zl: contiguous by construction of the arena
 static void ancestor_ranges(const Handle *H, int zl, std::vector<std::pair<int64_t, int64_t>> &out)
@@ -447,16 +440,16 @@ static int reduce_ancestors(Handle *H, int zl)
         const auto &r = rg[q.r];
         if ((rc = c->begin())) return rc;
         if (receiver) {
-            if ((rc = c->recv(H->d_xtmp, q.len * 8 * vs, peer))) return rc;
+            if ((rc = c->recv(H->d_xtmp.p, q.len * 8 * vs, peer))) return rc;
             if ((rc = c->end(rs))) return rc;
-            eng::add_atomic(rs, q.len * vs, H->d_xtmp, H->d_val + (r.first + q.o) * vs);   // the next chunk's receive into the staging buffer is ordered behind this on rs
+            eng::add_atomic(rs, q.len * vs, H->d_xtmp.p, H->d_val.p + (r.first + q.o) * vs);   // the next chunk's receive into the staging buffer is ordered behind this on rs
             const bool is_l = r.first < H->hs.nnzL;
             done[is_l ? 0 : 1] = r.first + q.o + q.len;
             hipEvent_t e = red_event(H);
             HIPCHK(hipEventRecord(e, rs));
             H->red_events.push_back({has_l ? done[0] : INT64_MAX, has_u ? done[1] : INT64_MAX, e});
         } else {
-            if ((rc = c->send(H->d_val + (r.first + q.o) * vs, q.len * 8 * vs, peer))) return rc;
+            if ((rc = c->send(H->d_val.p + (r.first + q.o) * vs, q.len * 8 * vs, peer))) return rc;
             if ((rc = c->end(rs))) return rc;
         }
     }
@@ -481,7 +474,7 @@ int run_factor(Handle *H, double thresh, int *info)
     const Grid &g = H->grid;
     if (g.size() > 1 && !H->comm) { set_error("handle of a multi-rank grid has no communicator"); return SLUAMD_EINVAL; }
     int init[8] = {0x7fffffff, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(H->d_info, init, sizeof(init), hipMemcpyHostToDevice, H->stream));
+    HIPCHK(hipMemcpyAsync(H->d_info.p, init, sizeof(init), hipMemcpyHostToDevice, H->stream));
     H->st.num_launches = 0; H->st.schur_launches = 0; H->st.schur_tiles = 0;
     H->profile = H->opt.verbose >= 2 || H->env.profile;
     H->ev_schur_used = H->ev_panel_used = H->ev_xchg_used = H->ev_red_used = 0;
@@ -506,7 +499,7 @@ int run_factor(Handle *H, double thresh, int *info)
     if (H->red_all) { HIPCHK(hipStreamWaitEvent(H->stream, H->red_all, 0)); H->red_events.clear(); }   // the last reduction's additions belong to the factorisation
     HIPCHK(hipEventRecord(H->ev1, H->stream));
     int res[8];
-    HIPCHK(hipMemcpyAsync(res, H->d_info, sizeof(res), hipMemcpyDeviceToHost, H->stream));
+    HIPCHK(hipMemcpyAsync(res, H->d_info.p, sizeof(res), hipMemcpyDeviceToHost, H->stream));
     HIPCHK(hipStreamSynchronize(H->stream));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev0, H->ev1));
     H->st.t_factor_ms = ms;
@@ -584,7 +577,7 @@ static int runs_on_device(Handle *H, const LevelSched::XSeg &m, const int **d)
         int64_t tot = 0;
         for (auto &r : m.runs) { h.push_back(r.first); h.push_back(r.second); h.push_back((int) tot); tot += r.second; }
         int *p = nullptr;
-        if (upload(H->d_misc, h, &p)) return SLUAMD_EHIP;
+        if (int rc = upload(H->d_misc, h, &p, "an x-segment run list")) return rc;
         m.d_runs = p;
     }
     *d = m.d_runs;
@@ -609,18 +602,18 @@ int xseg_exchange(Handle *H, double *d_x, int64_t ldx, int nrhs, const std::vect
         const int *dr;
         if ((rc = runs_on_device(H, snd[i], &dr))) return rc;
         so[i] = off;
-        eng::xseg_copy(s, d_x, ldx, nrhs, dr, (int) snd[i].runs.size(), snd[i].total, H->d_xtmp + off, pack_mode);
+        eng::xseg_copy(s, d_x, ldx, nrhs, dr, (int) snd[i].runs.size(), snd[i].total, H->d_xtmp.p + off, pack_mode);
         off += snd[i].total * nrhs;
     }
     for (size_t i = 0; i < rcv.size(); ++i) { ro[i] = off; off += rcv[i].total * nrhs; }
     if ((rc = c->begin())) return rc;
-    for (size_t i = 0; i < snd.size(); ++i) if ((rc = c->send(H->d_xtmp + so[i], snd[i].total * nrhs * 8, snd[i].peer))) return rc;
-    for (size_t i = 0; i < rcv.size(); ++i) if ((rc = c->recv(H->d_xtmp + ro[i], rcv[i].total * nrhs * 8, rcv[i].peer))) return rc;
+    for (size_t i = 0; i < snd.size(); ++i) if ((rc = c->send(H->d_xtmp.p + so[i], snd[i].total * nrhs * 8, snd[i].peer))) return rc;
+    for (size_t i = 0; i < rcv.size(); ++i) if ((rc = c->recv(H->d_xtmp.p + ro[i], rcv[i].total * nrhs * 8, rcv[i].peer))) return rc;
     if ((rc = c->end(s))) return rc;
     for (size_t i = 0; i < rcv.size(); ++i) {
         const int *dr;
         if ((rc = runs_on_device(H, rcv[i], &dr))) return rc;
-        eng::xseg_copy(s, d_x, ldx, nrhs, dr, (int) rcv[i].runs.size(), rcv[i].total, H->d_xtmp + ro[i], unpack_mode);
+        eng::xseg_copy(s, d_x, ldx, nrhs, dr, (int) rcv[i].runs.size(), rcv[i].total, H->d_xtmp.p + ro[i], unpack_mode);
     }
     // the staging buffer is reused by the next exchange: a stream-ordered transport (RCCL) packs, moves and unpacks in the order of
     // stream s already; the host-driven ones read and write the staging buffer from the host side
@@ -640,15 +633,7 @@ int xseg_exchange(Handle *H, double *d_x, int64_t ldx, int nrhs, const std::vect
 // run by the diagonal workgroup itself -- serial 64-row strips, 7.05 -> 8.1 ms.)
 
 // second vector of the sweeps below: the diagonal solves are out of place (strips of one supernode = independent workgroups)
-int ensure_w(Handle *H, int64_t doubles)
-{
-    if (doubles <= H->w_cap) return 0;
-    if (H->d_w) hipFree(H->d_w);
-    H->d_w = nullptr; H->w_cap = 0;
-    if (hipMalloc((void **) &H->d_w, sizeof(double) * (size_t) doubles) != hipSuccess) { set_error("hipMalloc of the solve work vector failed"); return SLUAMD_ENOMEM; }
-    H->w_cap = doubles;
-    return 0;
-}
+int ensure_w(Handle *H, int64_t doubles) { return H->d_w.reserve(doubles, H->device, "the second vector of the sweeps"); }
 
 // Joined links (LevelSched::join): ONE launch per level.  Forward: the joined units of level l + 1 apply the level-l updates to their own block of the
 // right-hand side and ADD their share of y_j = Linv_j (...) into w (zeroed first); every other row of the level-l panels is updated by the regular units in
@@ -674,7 +659,7 @@ static int solve_fwd_join(Handle *H, LevelSched &S, double *d_x, int64_t ldx, in
     hipStream_t s = H->stream;
     const int nl = S.nlevels;
     if (nl == 0) return 0;
-    double *w = H->d_w;
+    double *w = H->d_w.p;
     const int4 *fr = S.d_fwd_recs, *dr = S.d_diag_recs;
     zero_forest(H, S, w, ldx, nrhs);
     if (level_joined(H, S, 0, nrhs)) eng::sweep_join(s, true, T, S.d_jf_recs + 8 * (size_t) S.jf_off[0], S.jf_off[1] - S.jf_off[0], S.d_jf_aux, nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[0]);
@@ -702,7 +687,7 @@ static int solve_bwd_join(Handle *H, LevelSched &S, double *d_x, int64_t ldx, in
     hipStream_t s = H->stream;
     const int nl = S.nlevels;
     if (nl == 0) return 0;
-    double *w = H->d_w;
+    double *w = H->d_w.p;
     const int4 *br = S.d_bwd_recs, *dr = S.d_diag_recs;
     zero_forest(H, S, d_x, ldx, nrhs);
     // the chunks of a level whose columns lie beyond the next level run beside the diagonal blocks of the level ABOVE; the top level's (columns of ancestors in
@@ -744,7 +729,7 @@ static int solve_fwd_links(Handle *H, LevelSched &S, double *d_x, int64_t ldx, i
     hipStream_t s = H->stream;
     const int nl = S.nlevels;
     if (nl == 0) return 0;
-    double *w = H->d_w;
+    double *w = H->d_w.p;
     const int4 *fr = S.d_fwd_recs, *dr = S.d_diag_recs;     // unit records (null on complex handles)
     eng::sweep_step(s, true, T, S.d_diag_units + S.du_off[0], S.du_off[1] - S.du_off[0], nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[0], dr ? dr + 2 * (size_t) S.du_off[0] : nullptr, nullptr);
     for (int l = 0; l < nl; ++l) {
@@ -766,7 +751,7 @@ static int solve_bwd_links(Handle *H, LevelSched &S, double *d_x, int64_t ldx, i
     hipStream_t s = H->stream;
     const int nl = S.nlevels;
     if (nl == 0) return 0;
-    double *w = H->d_w;
+    double *w = H->d_w.p;
     const int4 *br = S.d_bwd_recs, *dr = S.d_diag_recs;
     {   // far chunks of the top level (columns of ancestors in other forests, solved before this sweep)
         const int u1 = S.bu_off[2 * (nl - 1) + 1], u2 = S.bu_off[2 * (nl - 1) + 2];
@@ -796,7 +781,7 @@ static int solve_fwd_links_serial(Handle *H, LevelSched &S, double *d_x, int64_t
     hipStream_t s = H->stream;
     const int nl = S.nlevels;
     if (nl == 0) return 0;
-    double *w = H->d_w;
+    double *w = H->d_w.p;
     const int4 *fr = S.d_fwd_recs, *dr = S.d_diag_recs;
     for (int l = 0; l < nl; ++l) {
         const int nd = S.du_off[l + 1] - S.du_off[l];
@@ -814,7 +799,7 @@ static int solve_bwd_links_serial(Handle *H, LevelSched &S, double *d_x, int64_t
     hipStream_t s = H->stream;
     const int nl = S.nlevels;
     if (nl == 0) return 0;
-    double *w = H->d_w;
+    double *w = H->d_w.p;
     const int4 *br = S.d_bwd_recs, *dr = S.d_diag_recs;
     for (int l = nl - 1; l >= 0; --l) {     // every chunk of level l reads x of levels above l (or of other forests) only: all of them, then the level's diagonal units
         for (int u = S.bu_off[2 * l]; u < S.bu_off[2 * l + 2]; ++u)
@@ -903,7 +888,7 @@ int max_rhs_chunk(const Handle *H)
 
 // complex16 on one rank, every supernode <= 64 columns: ONE launch per level and sweep (eng::zsweep_fused) instead of two -- the complex path's stand-in for the
 // joined links of the double path (it keeps no inverses).  Forward: x holds the accumulated right-hand side, w receives y; backward: w accumulates, x receives the solution.
-static bool zsweeps_fused(const Handle *H) { return H->z && H->grid.size() == 1 && H->max_nsupc <= 64 && H->env.z_fuse_max_nodes > 0 && !H->profile && H->d_ztickets; }
+static bool zsweeps_fused(const Handle *H) { return H->z && H->grid.size() == 1 && H->max_nsupc <= 64 && H->env.z_fuse_max_nodes > 0 && !H->profile && H->d_ztickets.p; }
 // Per level, the same form in both sweeps: fused (levels of few supernodes -- the chain at the top of the tree, where a level is launch latency) or the two in-place
 // launches (levels of thousands of supernodes: every strip re-solving its diagonal block and every chunk paying an agent-scope release cost more than a launch:
 // all levels fused 8.2 ms against 3.14 ms on the 1000 x 1000 configuration).  The forms meet in any order: right-hand-side accumulators always live in x; a fused
@@ -917,7 +902,7 @@ static int zsolve_fused(Handle *H, double *x, int64_t ldx, int nr)
         for (int l = 0; l < S.nlevels; ++l) {
             const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
             if (fused(S, l)) {
-                eng::zsweep_fused(s, true, T, S.d_nodes + n0, S.d_zffu_prefix + po, nn, S.zffu_prefix[po + nn], x, H->d_w, ldx, nr, S.max_nsupc[l], nullptr);
+                eng::zsweep_fused(s, true, T, S.d_nodes + n0, S.d_zffu_prefix + po, nn, S.zffu_prefix[po + nn], x, H->d_w.p, ldx, nr, S.max_nsupc[l], nullptr);
                 H->st.solve_launches += 1;
             } else {
                 eng::zsolve_diag(s, true, T, S.d_nodes + n0, nn, x, ldx, nr, S.max_nsupc[l]);
@@ -930,7 +915,7 @@ static int zsolve_fused(Handle *H, double *x, int64_t ldx, int nr)
         for (int l = S.nlevels - 1; l >= 0; --l) {
             const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
             if (fused(S, l)) {
-                eng::zsweep_fused(s, false, T, S.d_nodes + n0, S.d_zbfu_prefix + po, nn, S.zbfu_prefix[po + nn], x, H->d_w, ldx, nr, S.max_nsupc[l], H->d_ztickets);
+                eng::zsweep_fused(s, false, T, S.d_nodes + n0, S.d_zbfu_prefix + po, nn, S.zbfu_prefix[po + nn], x, H->d_w.p, ldx, nr, S.max_nsupc[l], H->d_ztickets.p);
                 H->st.solve_launches += 1;
             } else {
                 eng::zbwd_update(s, T, S.d_nodes + n0, S.d_bwd_prefix + po, nn, S.bwd_prefix[po + nn], x, ldx, nr);
@@ -1073,17 +1058,17 @@ static int allgather_solution(Handle *H, double *x, int64_t ldxd, int nr, hipStr
     const int *dr;
     if (mine.total) {
         if ((rc = runs_on_device(H, mine, &dr))) return rc;
-        eng::xseg_copy(s, x, ldxd, nr, dr, (int) mine.runs.size(), mine.total, H->d_xtmp, 0);
+        eng::xseg_copy(s, x, ldxd, nr, dr, (int) mine.runs.size(), mine.total, H->d_xtmp.p, 0);
     }
     std::vector<int64_t> ro(P, 0);
     int64_t off = mine.total * nr;
     if ((rc = c->begin())) return rc;
     for (int p = 0; p < P; ++p) {
         if (p == me) continue;
-        if (mine.total && (rc = c->send(H->d_xtmp, mine.total * nr * 8, p))) return rc;
+        if (mine.total && (rc = c->send(H->d_xtmp.p, mine.total * nr * 8, p))) return rc;
         const int64_t t = H->owner_runs[p].total * nr;
         ro[p] = off;
-        if (t && (rc = c->recv(H->d_xtmp + off, t * 8, p))) return rc;
+        if (t && (rc = c->recv(H->d_xtmp.p + off, t * 8, p))) return rc;
         off += t;
     }
     if ((rc = c->end(s))) return rc;
@@ -1091,7 +1076,7 @@ static int allgather_solution(Handle *H, double *x, int64_t ldxd, int nr, hipStr
         const LevelSched::XSeg &m = H->owner_runs[p];
         if (p == me || !m.total) continue;
         if ((rc = runs_on_device(H, m, &dr))) return rc;
-        eng::xseg_copy(s, x, ldxd, nr, dr, (int) m.runs.size(), m.total, H->d_xtmp + ro[p], 1);
+        eng::xseg_copy(s, x, ldxd, nr, dr, (int) m.runs.size(), m.total, H->d_xtmp.p + ro[p], 1);
     }
     if (!c->stream_ordered()) HIPCHK(hipStreamSynchronize(s));
     return 0;
@@ -1183,9 +1168,9 @@ int run_grid_solve(Handle *H, double *d_x, int64_t ldx, int nrhs, const GridSwee
             if ((rc = ensure_xtmp(H, std::max<int64_t>(keep.total * nr, 1)))) return rc;
             const int *dr;
             if ((rc = runs_on_device(H, keep, &dr))) return rc;
-            eng::xseg_copy(s, x, ldxd, nr, dr, (int) keep.runs.size(), keep.total, H->d_xtmp, 0);
+            eng::xseg_copy(s, x, ldxd, nr, dr, (int) keep.runs.size(), keep.total, H->d_xtmp.p, 0);
             for (int q = 0; q < nr; ++q) HIPCHK(hipMemsetAsync(x + (size_t) q * ldxd, 0, sizeof(double) * (size_t) H->hs.n * vs, s));
-            eng::xseg_copy(s, x, ldxd, nr, dr, (int) keep.runs.size(), keep.total, H->d_xtmp, 1);
+            eng::xseg_copy(s, x, ldxd, nr, dr, (int) keep.runs.size(), keep.total, H->d_xtmp.p, 1);
             if (!H->comm->stream_ordered()) HIPCHK(hipStreamSynchronize(s));
         }
         if ((rc = grid_sweeps(H, x, ldx, nr, ops))) return rc;
@@ -1209,18 +1194,14 @@ static bool same_perm(const std::vector<int> &kept, bool kept_null, const int *p
     return (int64_t) kept.size() == n && std::memcmp(kept.data(), perm, sizeof(int) * (size_t) n) == 0;
 }
 
-static void free_dist_plan(Handle *H)
-{
-    for (void *p : H->dist.bufs) hipFree(p);
-    H->dist = Handle::DistPlan();
-}
+static void free_dist_plan(Handle *H) { H->dist = Handle::DistPlan(); H->dist.bufs.device = H->device; }
 
 // Routing of the caller's rows of B (row-block distribution over the ranks of layer 0: m_loc rows from fst_row, NRformat_loc) to
 // the ranks that consume them in the sweeps (through perm_in) and of the solution back (through perm_out).  Both sides of a pair
 // derive matching lists from replicated data (the permutation, every rank's range and owner rows): the rows between one pair of
 // ranks travel in ascending order of the row of x.
 static int build_route(Handle *H, const std::vector<int> &src_rank, const std::vector<int> &owner, int64_t m_loc, int64_t fst_row,
-                       const int *perm, Handle::DistRoute &R, std::vector<void *> &bufs)
+                       const int *perm, Handle::DistRoute &R, DevBag &bufs)
 {
     const Grid &g = H->grid;
     const int P = g.size(), me = g.rank();
@@ -1246,8 +1227,9 @@ static int build_route(Handle *H, const std::vector<int> &src_rank, const std::v
         std::vector<int> bi(bs[p].size());
         for (size_t j = 0; j < bi.size(); ++j) bi[j] = bs[p][j].second;
         R.cnt_b[p] = (int64_t) bi.size(); R.cnt_x[p] = (int64_t) xs[p].size();
-        if (!bi.empty() && upload(bufs, bi, &R.d_bidx[p])) return SLUAMD_EHIP;
-        if (!xs[p].empty() && upload(bufs, xs[p], &R.d_xidx[p])) return SLUAMD_EHIP;
+        int rc;
+        if (!bi.empty() && (rc = upload(bufs, bi, &R.d_bidx[p], "the routing table of B's rows"))) return rc;
+        if (!xs[p].empty() && (rc = upload(bufs, xs[p], &R.d_xidx[p], "the routing table of x's rows"))) return rc;
     }
     if (R.cnt_b[me] != R.cnt_x[me]) { set_error("sluamd_pdgstrs3d_dist: inconsistent routing tables"); return SLUAMD_ESTRUCT; }
     return 0;
@@ -1310,8 +1292,8 @@ static int redistribute(Handle *H, bool b2x, double *d_b, int64_t ldb, double *x
     int64_t off = 0;
     for (int p = 0; p < P; ++p) {     // pack
         so[p] = off; off += cs[p] * nr * vs;
-        if (b2x) eng::rows_copy(s, d_b, ldb, nr, R.d_bidx[p], cs[p], H->d_xtmp + so[p], 0, vs);
-        else eng::rows_copy(s, x, ldx, nr, R.d_xidx[p], cs[p], H->d_xtmp + so[p], 0, vs);
+        if (b2x) eng::rows_copy(s, d_b, ldb, nr, R.d_bidx[p], cs[p], H->d_xtmp.p + so[p], 0, vs);
+        else eng::rows_copy(s, x, ldx, nr, R.d_xidx[p], cs[p], H->d_xtmp.p + so[p], 0, vs);
     }
     for (int p = 0; p < P; ++p) { ro[p] = (p == me) ? so[p] : off; if (p != me) off += cr[p] * nr * vs; }     // my own rows need no transport
     if (P > 1) {
@@ -1319,14 +1301,14 @@ static int redistribute(Handle *H, bool b2x, double *d_b, int64_t ldb, double *x
         if ((rc = c->begin())) return rc;
         for (int p = 0; p < P; ++p) {
             if (p == me) continue;
-            if (cs[p] && (rc = c->send(H->d_xtmp + so[p], cs[p] * nr * 8 * vs, p))) return rc;
-            if (cr[p] && (rc = c->recv(H->d_xtmp + ro[p], cr[p] * nr * 8 * vs, p))) return rc;
+            if (cs[p] && (rc = c->send(H->d_xtmp.p + so[p], cs[p] * nr * 8 * vs, p))) return rc;
+            if (cr[p] && (rc = c->recv(H->d_xtmp.p + ro[p], cr[p] * nr * 8 * vs, p))) return rc;
         }
         if ((rc = c->end(s))) return rc;
     }
     for (int p = 0; p < P; ++p) {     // unpack
-        if (b2x) eng::rows_copy(s, x, ldx, nr, R.d_xidx[p], cr[p], H->d_xtmp + ro[p], 1, vs);
-        else eng::rows_copy(s, d_b, ldb, nr, R.d_bidx[p], cr[p], H->d_xtmp + ro[p], 1, vs);
+        if (b2x) eng::rows_copy(s, x, ldx, nr, R.d_xidx[p], cr[p], H->d_xtmp.p + ro[p], 1, vs);
+        else eng::rows_copy(s, d_b, ldb, nr, R.d_bidx[p], cr[p], H->d_xtmp.p + ro[p], 1, vs);
     }
     if (P > 1 && !H->comm->stream_ordered()) HIPCHK(hipStreamSynchronize(s));
     return 0;
@@ -1343,7 +1325,7 @@ int run_solve_dist(Handle *H, double *d_b, int64_t ldb, int nrhs, int64_t m_loc,
     int rc;
     if (g.size() > 1) { if ((rc = grid_solve_checks(H))) return rc; }
     else if (!H->z && (rc = ensure_inv(H))) return rc;
-    const int vs = H->z ? 2 : 1;      // d_b, H->d_x: values of vs doubles; ldb in values
+    const int vs = H->z ? 2 : 1;      // d_b, H->d_x.p: values of vs doubles; ldb in values
     hipStream_t s = H->stream;
     {
         // build_dist_plan is COLLECTIVE (it exchanges every rank's row range): the decision to rebuild must be too -- a rank whose own
@@ -1357,23 +1339,18 @@ int run_solve_dist(Handle *H, double *d_b, int64_t ldb, int nrhs, int64_t m_loc,
     const int64_t n = H->hs.n;
     const int ch = max_rhs_chunk(H);
     const int64_t need = n * std::min(ch, nrhs) * vs;
-    if (need > H->x_cap) {
-        if (H->d_x) hipFree(H->d_x);
-        H->d_x = nullptr; H->x_cap = 0;
-        HIPCHK(hipMalloc((void **) &H->d_x, sizeof(double) * (size_t) need));
-        H->x_cap = need;
-    }
+    if ((rc = H->d_x.reserve(need, H->device, "the right-hand sides"))) return rc;
     for (int j0 = 0; j0 < nrhs; j0 += ch) {
         const int nr = std::min(ch, nrhs - j0);
         double *b = d_b + (size_t) j0 * ldb * vs;
-        HIPCHK(hipMemsetAsync(H->d_x, 0, sizeof(double) * (size_t) n * nr * vs, s));       // zero accumulators everywhere but the consumed rows
-        if ((rc = redistribute(H, true, b, ldb, H->d_x, n, nr, s))) return rc;
-        if (g.size() > 1) { if ((rc = grid_sweeps(H, H->d_x, n, nr))) return rc; }
+        HIPCHK(hipMemsetAsync(H->d_x.p, 0, sizeof(double) * (size_t) n * nr * vs, s));       // zero accumulators everywhere but the consumed rows
+        if ((rc = redistribute(H, true, b, ldb, H->d_x.p, n, nr, s))) return rc;
+        if (g.size() > 1) { if ((rc = grid_sweeps(H, H->d_x.p, n, nr))) return rc; }
         else {
-            for (int z = 0; z < (int) H->sched.size(); ++z) if ((rc = solve_fwd_z(H, z, H->d_x, n, nr))) return rc;
-            for (int z = (int) H->sched.size() - 1; z >= 0; --z) if ((rc = solve_bwd_z(H, z, H->d_x, n, nr))) return rc;
+            for (int z = 0; z < (int) H->sched.size(); ++z) if ((rc = solve_fwd_z(H, z, H->d_x.p, n, nr))) return rc;
+            for (int z = (int) H->sched.size() - 1; z >= 0; --z) if ((rc = solve_bwd_z(H, z, H->d_x.p, n, nr))) return rc;
         }
-        if ((rc = redistribute(H, false, b, ldb, H->d_x, n, nr, s))) return rc;
+        if ((rc = redistribute(H, false, b, ldb, H->d_x.p, n, nr, s))) return rc;
     }
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());

@@ -26,6 +26,9 @@ constexpr int KC = 16;            // K chunk of the Schur GEMM pipeline
 
 void set_error(const std::string &msg);
 const std::string &get_error();
+}  // namespace sluamd
+#include "sluamd_devmem.h"   // dev_alloc / DevBuf / DevBag / PoolBuf: every device allocation of the library
+namespace sluamd {
 
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
@@ -163,12 +166,6 @@ struct DevTables {
 };
 
 // One exchange message of the XY panel exchange: a contiguous range of the value arena sent to / received from one peer
-// value arenas on a process-level pool of physical device chunks (sluamd_devpool.cpp; the CPU test build: oracle/emul/emul_rt.cpp)
-int devpool_alloc(void **p, size_t bytes, int device);
-void devpool_free(void *p);
-void devpool_trim(int device);            // device < 0: every device
-size_t devpool_cached_bytes(int device);
-
 struct XMsg { int peer; int64_t off, len; };   // world rank, arena offset, doubles
 
 struct LevelSched {
@@ -212,7 +209,7 @@ struct LevelSched {
                                     // [diagonal blocks of level l+1 | rest of the level-(l+1) panels | level-(l+2) panels | bulk, 8 x 8 bands per supernode]
     std::vector<int> u_off;         // [8*nlevels+1] offsets into ulist: index (2*level + group) * 4 + part
     std::vector<int64_t> m_off;     // [2*nlevels+1] first int of the tile records of (level, group) in d_tmaps (record of tile u of the group: + (u - u_off[group start]) * rec)
-    int *d_tmaps = nullptr;         // per-tile records of k_schur, built on the first factorisation (owned by Handle::d_misc)
+    DevBuf<int> d_tmaps;            // per-tile records of k_schur, built on the first factorisation
     // Balanced bulk launches (round 6; balance_bulk): k_schur gives XCD x the tiles [x_off[x], x_off[x + 1]) of the launch -- eight contiguous ranges of EQUAL MODELLED COST
     // (K chunks of all sources x share of the waves that run MFMAs) instead of equal counts; the level's supernodes are listed longest tiles first.
     // x_off: 10 ints per (level, group) at 10 * (2 * level + group): nine range boundaries relative to the launch's first tile + the longest range; [9] == 0: not balanced
@@ -226,7 +223,7 @@ struct LevelSched {
     std::vector<std::vector<XMsg>> x_panel_send, x_panel_recv;   // phase 2: L slots along the process row, U slots down the column
     std::vector<int64_t> dg_stage_off;        // [nlevels] arena offset of the level's packed own diagonal blocks
     // solve exchange plan: per level, x segments (as [first row, rows) runs) reduced to / broadcast from the diagonal owners
-    struct XSeg { int peer = -1; std::vector<std::pair<int, int>> runs; int64_t total = 0; mutable int *d_runs = nullptr; /* device image, uploaded on first use (owned by Handle::d_misc) */ };
+    struct XSeg { int peer = -1; std::vector<std::pair<int, int>> runs; int64_t total = 0; mutable int *d_runs = nullptr; /* device image, uploaded on first use (owned by Handle::d_misc / DistPlan::bufs) */ };
     std::vector<std::vector<XSeg>> xs_red_send, xs_red_recv, xs_bc_send, xs_bc_recv;
     // ... and of the TRANSPOSED sweeps (sluamd_tsolve.cpp), where the two directions swap: partial sums of x_k are reduced along process COLUMN k % Pc to the
     // diagonal owner, x_k is broadcast along process ROW k % Pr.  Built on request, after the handle exists (sluamd_PlanTransposedSweeps -> plan_trans_exchange)
@@ -330,11 +327,11 @@ struct Handle {
         double balance_ovh = 4.0;    // SLUAMD_BALANCE_OVH: fixed cost of a tile (record, prologue, scatter) in K-chunk periods of the cost model
     } env;
     // device arenas
-    double *d_val = nullptr;
+    PoolBuf d_val;
     int64_t arena_len = 0;          // elements (doubles, or doublecomplex for z) of the whole arena
     int64_t own_len = 0;            // ... of the resident part [own L | own U]
     int *d_lidx = nullptr, *d_uidx = nullptr, *d_ucolptr = nullptr, *d_unzcol = nullptr, *d_xsup = nullptr;
-    std::vector<void *> d_misc;  // everything else to free
+    DevBag d_misc;               // everything else to free
     DevTables T{};
     std::vector<LevelSched> sched;  // one per Z level (forests) or a single one
     // Merged chain groups of the sweeps (round 5; 1 x 1 x 1 grids, real, SLUAMD_SOLVE_GROUPS): up to four consecutive supernodes of a chain -- the pieces of one
@@ -346,7 +343,7 @@ struct Handle {
     std::vector<int> grp_of;                  // [nsupers] group of a supernode, -1: none
     std::vector<std::vector<int>> lvl_groups;  // [factor level] groups whose last member is factored at that level
     std::vector<LevelSched> ssched;
-    GrpDesc *d_grpdesc = nullptr; GemmDesc *d_gemmdesc = nullptr; int4 *d_gemmtiles = nullptr; double *d_gscr = nullptr;
+    GrpDesc *d_grpdesc = nullptr; GemmDesc *d_gemmdesc = nullptr; int4 *d_gemmtiles = nullptr; DevBuf<double> d_gscr;
     hipStream_t gstream = nullptr;            // group inverses run here, beside the factorisation
     std::vector<std::vector<int>> forest_nodes;   // ascending supernodes of the forest of every Z level on this layer's path (even when not factored here)
     std::vector<uint8_t> z_active;  // [Z levels] this layer factors that level's forest (!myZeroTrIdxs)
@@ -365,36 +362,36 @@ struct Handle {
     hipEvent_t red_all = nullptr;            // everything queued on rstream so far
     std::vector<hipEvent_t> ev_pool;        // look-ahead dependency events
     size_t ev_pool_used = 0;
-    int *d_info = nullptr;      // [0]=first zero pivot column (INT_MAX if none), [1]=tiny pivots, [2]=missing dest blocks, [3]=sink, [4]=last zero pivot column (0 if none)
-    double *d_x = nullptr; int64_t x_cap = 0;
-    double *d_xtmp = nullptr; int64_t xtmp_cap = 0;   // exchange staging of the distributed solve / ancestor reduction
-    double *d_w = nullptr; int64_t w_cap = 0;         // second vector of the 1 x 1-layer sweeps (out-of-place diagonal solves: forward solution, backward accumulators)
-    int64_t *d_apos = nullptr; double *d_aval = nullptr; int64_t a_nnz = 0;  // A's entries for device-side (re)distribution
-    int *d_aent = nullptr; int64_t a_csr_nnz = -1;            // ... and the index of each of them in the caller's CSR (handles created from the symbolic structure)
+    DevBuf<int> d_info;         // [0]=first zero pivot column (INT_MAX if none), [1]=tiny pivots, [2]=missing dest blocks, [3]=sink, [4]=last zero pivot column (0 if none)
+    DevBuf<double> d_x;
+    DevBuf<double> d_xtmp;                            // exchange staging of the distributed solve / ancestor reduction
+    DevBuf<double> d_w;                               // second vector of the 1 x 1-layer sweeps (out-of-place diagonal solves: forward solution, backward accumulators)
+    DevBuf<int64_t> d_apos; DevBuf<double> d_aval; int64_t a_nnz = 0;        // A's entries for device-side (re)distribution
+    DevBuf<int> d_aent; int64_t a_csr_nnz = -1;               // ... and the index of each of them in the caller's CSR (handles created from the symbolic structure)
     // equilibration (sluamd_[dz]Equilibrate, sluamd_equil.cpp): R and C on the device, what was applied, and the work block of the expert solve
-    double *d_eq_r = nullptr, *d_eq_c = nullptr; bool eq_done = false, eq_row = false, eq_col = false;
-    double *d_eq_work = nullptr; int64_t eq_work_cap = 0;     // [xp | B | X] of sluamd_p[dz]gssvx3d_solve (doubles)
+    DevBuf<double> d_eq_r, d_eq_c; bool eq_done = false, eq_row = false, eq_col = false;
+    DevBuf<double> d_eq_work;                                 // [xp | B | X] of sluamd_p[dz]gssvx3d_solve (doubles)
     // sluamd_SetRowPerm (sluamd_equil.cpp): the handle was made from Pr A; perm_r, perm_c o perm_r and (row-scaled handles) R o perm_r, composed once.  They
     // belong to the attached matrix and go with it (free_rfs)
-    int *d_rp_pr = nullptr, *d_rp_pcpr = nullptr; double *d_rp_rs = nullptr;
+    DevBuf<int> d_rp_pr, d_rp_pcpr; DevBuf<double> d_rp_rs;
     // same-pattern value updates (sluamd_[dz]UpdateValues, sluamd_update.cpp): the staging buffer of the host-pointer form (grows once), the event that marks
     // its copy complete, and (row, column) in the caller's CSR of every owned entry -- built on the first update of a handle whose values are scaled
-    double *d_upd_stage = nullptr; int64_t upd_stage_cap = 0; hipEvent_t ev_upd = nullptr;
-    int2 *d_upd_ij = nullptr;
+    DevBuf<double> d_upd_stage; hipEvent_t ev_upd = nullptr;
+    DevBuf<int2> d_upd_ij;
     // iterative refinement (sluamd_dAttachMatrix / sluamd_zAttachMatrix): the ORIGINAL matrix in CSR + perm_c, and work vectors
     // (values and vectors in doubles: 2 per value when rfs_z)
-    int *d_rfs_rp = nullptr, *d_rfs_ci = nullptr, *d_rfs_pc = nullptr; double *d_rfs_av = nullptr;
-    double *d_rfs_work = nullptr; unsigned long long *d_rfs_s = nullptr; int64_t rfs_nnz = 0;
+    DevBuf<int> d_rfs_rp, d_rfs_ci, d_rfs_pc; DevBuf<double> d_rfs_av;
+    DevBuf<double> d_rfs_work; DevBuf<unsigned long long> d_rfs_s; int64_t rfs_nnz = 0;
     bool rfs_z = false;                                     // the attached matrix is complex16
     // transposed index of the attached matrix (sluamd_trefine.cpp), built on the first transposed refinement: column pointers, and per entry in
     // column order (rows ascending inside a column) its row and its position in d_rfs_av.  No values: the kernels read d_rfs_av[d_rfs_tpos[e]]
-    int *d_rfs_tcp = nullptr, *d_rfs_tri = nullptr, *d_rfs_tpos = nullptr;
+    DevBuf<int> d_rfs_tcp, d_rfs_tri, d_rfs_tpos;
     void *h_pinned = nullptr; size_t pinned_bytes = 0;      // bounded pinned staging buffer (value upload / download)
     bool z = false;                                         // complex16 (doublecomplex) values: 16-byte elements
     bool dinv_ready = false;                                // T.dinv holds the inverses for the current factors
     bool inv_ready = false;                                 // T.inv (Linv / Uinv) too
     bool factored = false;                                  // the resident values are FACTORS (run_factor since the last SetValues / ResetValues): sluamd_dGetDiagInv refuses otherwise
-    int *d_ztickets = nullptr;                              // complex fused backward links: one ticket counter per supernode (zero between sweeps)
+    DevBuf<int> d_ztickets;                                 // complex fused backward links: one ticket counter per supernode (zero between sweeps)
     bool profile = false;                                   // per-kernel-family HIP-event timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_schur, ev_panel, ev_xchg, ev_red;
     size_t ev_schur_used = 0, ev_panel_used = 0, ev_xchg_used = 0, ev_red_used = 0;
@@ -428,9 +425,9 @@ struct Handle {
         int64_t m_loc = -1, fst_row = -1;
         std::vector<int> perm_in, perm_out; bool null_in = true, null_out = true;   // the permutations the routes were built for (compared element by element)
         DistRoute in, out;                          // B -> x through perm_in, x -> B through perm_out
-        std::vector<void *> bufs;                   // device allocations of this plan
+        DevBag bufs;                                // device allocations of this plan
     } dist;
-    double *d_bloc = nullptr; int64_t bloc_cap = 0;   // the caller's local rows of B on the device
+    DevBuf<double> d_bloc;                            // the caller's local rows of B on the device
 };
 
 // ------------------------------------------------------------------------------------------------

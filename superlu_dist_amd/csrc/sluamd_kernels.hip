@@ -3464,12 +3464,13 @@ void rows_copy(hipStream_t s, double *v, int64_t ldv, int nrhs, const int *idx, 
 
 int mfma_selftest(const double *A, const double *B, double *D)
 {
-    double *dA, *dB, *dD;
-    HIPCHK(hipMalloc((void **) &dA, 64 * 8)); HIPCHK(hipMalloc((void **) &dB, 64 * 8)); HIPCHK(hipMalloc((void **) &dD, 256 * 8));
+    DevBuf<double> bA, bB, bD;
+    int rc;
+    if ((rc = bA.alloc(64, -1, "operand A of the MFMA self-test")) || (rc = bB.alloc(64, -1, "operand B of the MFMA self-test")) || (rc = bD.alloc(256, -1, "the result of the MFMA self-test"))) return rc;
+    double *dA = bA.p, *dB = bB.p, *dD = bD.p;
     HIPCHK(hipMemcpy(dA, A, 64 * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dB, B, 64 * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_mfma_selftest, dim3(1), dim3(64), 0, 0, dA, dB, dD);
     HIPCHK(hipMemcpy(D, dD, 256 * 8, hipMemcpyDeviceToHost));
-    hipFree(dA); hipFree(dB); hipFree(dD);
     return 0;
 }
 

@@ -1251,26 +1251,30 @@ static void build_solve_sched(Handle &H, const HostTables &t, const std::vector<
 
 static int upload_schedule(Handle &H, LevelSched &S, const HostTables &t)
 {
-    if (upload(H.d_misc, S.nodes, &S.d_nodes)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.tile_prefix, &S.d_tile_prefix)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.ltr_prefix, &S.d_ltr_prefix)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.utr_prefix, &S.d_utr_prefix)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.fwd_prefix, &S.d_fwd_prefix)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.bwd_prefix, &S.d_bwd_prefix)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.inv_prefix, &S.d_inv_prefix)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.zltr_prefix, &S.d_zltr_prefix)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.sn_level, &S.d_sn_level)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.ulist, &S.d_ulist)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.x_off, &S.d_x_off)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.dg_prefix, &S.d_dg_prefix)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.zfwd_prefix, &S.d_zfwd_prefix)) return SLUAMD_EHIP;
-    if (H.z && (upload(H.d_misc, S.zffu_prefix, &S.d_zffu_prefix) || upload(H.d_misc, S.zbfu_prefix, &S.d_zbfu_prefix))) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.finv_prefix, &S.d_finv_prefix)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.dg_off, &S.d_dg_off)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.fwd_units, &S.d_fwd_units)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.bwd_units, &S.d_bwd_units)) return SLUAMD_EHIP;
-    if (upload(H.d_misc, S.diag_units, &S.d_diag_units)) return SLUAMD_EHIP;
-    if (!S.ps_units.empty() && upload(H.d_misc, S.ps_units, &S.d_ps_units)) return SLUAMD_EHIP;
+    int rc;
+    if ((rc = upload(H.d_misc, S.nodes, &S.d_nodes, "the table nodes"))) return rc;
+    if ((rc = upload(H.d_misc, S.tile_prefix, &S.d_tile_prefix, "the table tile_prefix"))) return rc;
+    if ((rc = upload(H.d_misc, S.ltr_prefix, &S.d_ltr_prefix, "the table ltr_prefix"))) return rc;
+    if ((rc = upload(H.d_misc, S.utr_prefix, &S.d_utr_prefix, "the table utr_prefix"))) return rc;
+    if ((rc = upload(H.d_misc, S.fwd_prefix, &S.d_fwd_prefix, "the table fwd_prefix"))) return rc;
+    if ((rc = upload(H.d_misc, S.bwd_prefix, &S.d_bwd_prefix, "the table bwd_prefix"))) return rc;
+    if ((rc = upload(H.d_misc, S.inv_prefix, &S.d_inv_prefix, "the table inv_prefix"))) return rc;
+    if ((rc = upload(H.d_misc, S.zltr_prefix, &S.d_zltr_prefix, "the table zltr_prefix"))) return rc;
+    if ((rc = upload(H.d_misc, S.sn_level, &S.d_sn_level, "the table sn_level"))) return rc;
+    if ((rc = upload(H.d_misc, S.ulist, &S.d_ulist, "the table ulist"))) return rc;
+    if ((rc = upload(H.d_misc, S.x_off, &S.d_x_off, "the table x_off"))) return rc;
+    if ((rc = upload(H.d_misc, S.dg_prefix, &S.d_dg_prefix, "the table dg_prefix"))) return rc;
+    if ((rc = upload(H.d_misc, S.zfwd_prefix, &S.d_zfwd_prefix, "the table zfwd_prefix"))) return rc;
+    if (H.z) {
+        if ((rc = upload(H.d_misc, S.zffu_prefix, &S.d_zffu_prefix, "the table zffu_prefix"))) return rc;
+        if ((rc = upload(H.d_misc, S.zbfu_prefix, &S.d_zbfu_prefix, "the table zbfu_prefix"))) return rc;
+    }
+    if ((rc = upload(H.d_misc, S.finv_prefix, &S.d_finv_prefix, "the table finv_prefix"))) return rc;
+    if ((rc = upload(H.d_misc, S.dg_off, &S.d_dg_off, "the table dg_off"))) return rc;
+    if ((rc = upload(H.d_misc, S.fwd_units, &S.d_fwd_units, "the table fwd_units"))) return rc;
+    if ((rc = upload(H.d_misc, S.bwd_units, &S.d_bwd_units, "the table bwd_units"))) return rc;
+    if ((rc = upload(H.d_misc, S.diag_units, &S.d_diag_units, "the table diag_units"))) return rc;
+    if (!S.ps_units.empty()) if ((rc = upload(H.d_misc, S.ps_units, &S.d_ps_units, "the table ps_units"))) return rc;
     H.setup.lap("upload.schedule_lists");
     if (!H.z) {
         // unit records (k_sweep / k_fwd_update / k_bwd_update): the scalars of every unit in the order of the unit lists
@@ -1319,7 +1323,9 @@ static int upload_schedule(Handle &H, LevelSched &S, const HostTables &t)
             int4 b; lohi(li, b.x, b.y); lohi(li + (int64_t) ns * ns, b.z, b.w);
             S.diag_recs[2 * u] = make_int4(fst, ns, strip, 0); S.diag_recs[2 * u + 1] = b;
         }
-        if (upload(H.d_misc, S.fwd_recs, &S.d_fwd_recs) || upload(H.d_misc, S.bwd_recs, &S.d_bwd_recs) || upload(H.d_misc, S.diag_recs, &S.d_diag_recs)) return SLUAMD_EHIP;
+        if ((rc = upload(H.d_misc, S.fwd_recs, &S.d_fwd_recs, "the table fwd_recs"))) return rc;
+        if ((rc = upload(H.d_misc, S.bwd_recs, &S.d_bwd_recs, "the table bwd_recs"))) return rc;
+        if ((rc = upload(H.d_misc, S.diag_recs, &S.d_diag_recs, "the table diag_recs"))) return rc;
         std::vector<int4>().swap(S.fwd_recs); std::vector<int4>().swap(S.bwd_recs); std::vector<int4>().swap(S.diag_recs);
         H.setup.lap("upload.sweep_unit_records");
         S.join = false;
@@ -1327,8 +1333,12 @@ static int upload_schedule(Handle &H, LevelSched &S, const HostTables &t)
             const std::vector<uint8_t> keep_l = H.h_lrow_near, keep_u = H.h_ucol_near;
             if (build_join(H, S, t)) {
                 S.join = true;
-                if (upload(H.d_misc, S.jf_recs, &S.d_jf_recs) || upload(H.d_misc, S.jf_aux, &S.d_jf_aux) || upload(H.d_misc, S.jb_recs, &S.d_jb_recs) ||
-                    upload(H.d_misc, S.jb_aux, &S.d_jb_aux) || upload(H.d_misc, S.jfu_recs, &S.d_jfu_recs) || upload(H.d_misc, S.jbu_recs, &S.d_jbu_recs)) return SLUAMD_EHIP;
+                if ((rc = upload(H.d_misc, S.jf_recs, &S.d_jf_recs, "the table jf_recs"))) return rc;
+                if ((rc = upload(H.d_misc, S.jf_aux, &S.d_jf_aux, "the table jf_aux"))) return rc;
+                if ((rc = upload(H.d_misc, S.jb_recs, &S.d_jb_recs, "the table jb_recs"))) return rc;
+                if ((rc = upload(H.d_misc, S.jb_aux, &S.d_jb_aux, "the table jb_aux"))) return rc;
+                if ((rc = upload(H.d_misc, S.jfu_recs, &S.d_jfu_recs, "the table jfu_recs"))) return rc;
+                if ((rc = upload(H.d_misc, S.jbu_recs, &S.d_jbu_recs, "the table jbu_recs"))) return rc;
             } else { H.h_lrow_near = keep_l; H.h_ucol_near = keep_u; }
             for (auto *v : {&S.jf_recs, &S.jf_aux, &S.jb_recs, &S.jb_aux, &S.jfu_recs, &S.jbu_recs}) std::vector<int4>().swap(*v);
             H.setup.lap("upload.joined_sweep_tables");
@@ -1502,21 +1512,18 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
     const size_t esz = H->z ? 16 : 8;
     const size_t arena_bytes = esz * (size_t) std::max<int64_t>(H->arena_len, 1);
     std::atomic<int> arena_rc{0};
+    std::string arena_err;          // the helper thread's message (set_error is per thread), read after the join
     struct Joiner { std::thread th; ~Joiner() { if (th.joinable()) th.join(); } } arena_job;
-    arena_job.th = std::thread([H, arena_bytes, &arena_rc] {
+    arena_job.th = std::thread([H, arena_bytes, &arena_rc, &arena_err] {
         if (hipSetDevice(H->device) != hipSuccess) { arena_rc = 3; return; }
         // single-rank handles: from the pool of physical chunks (a later handle of the process re-maps what an earlier one released); grids: plain hipMalloc
         const bool pooled = H->grid.size() == 1 && !H->comm;
-        if (pooled ? devpool_alloc((void **) &H->d_val, arena_bytes, H->device) != 0 : hipMalloc((void **) &H->d_val, arena_bytes) != hipSuccess) {
-            (void) hipGetLastError();
-            devpool_trim(H->device);          // what the pool holds may be what is missing
-            if (hipMalloc((void **) &H->d_val, arena_bytes) != hipSuccess) { H->d_val = nullptr; arena_rc = 1; return; }
-        }
-        if (hipMemset(H->d_val, 0, arena_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) arena_rc = 2;
+        if (H->d_val.alloc(arena_bytes, H->device, pooled, "the value arena")) { arena_err = get_error(); arena_rc = 1; return; }      // (completed after the join, on the caller's thread)
+        if (hipMemset(H->d_val.p, 0, arena_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) arena_rc = 2;
     });
 
     // ---- 4. per-level exchange plan + offsets of the remote slots / scratch diagonal blocks ----
-    H->sched.assign(nz, LevelSched());
+    H->sched.clear(); H->sched.resize(nz);
     std::vector<int64_t> dptr(ns, 0);
     std::vector<int> dlda(ns, 1);
     for (int k = 0; k < ns; ++k) { dptr[k] = hs.lval_off[k]; dlda[k] = 1; }
@@ -1639,19 +1646,24 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
     // The block / tile tables are final here: a helper thread uploads them (pageable copies, ~4 GB/s) while this one builds the schedules.  Nothing below
     // writes the vectors it reads or touches H->d_misc / H->T until the join in step 7.
     int table_rc = 0;
+    std::string table_err;          // the error message is per thread: the helper's comes back with its return code
     size_t table_bytes = 0;
     struct TJoiner { std::thread th; ~TJoiner() { if (th.joinable()) th.join(); } } table_job;
     static const bool sync_tables = getenv("SLUAMD_SYNC_TABLE_UPLOAD") != nullptr;      // development: the upload at its old place, on this thread
-    auto table_upload = [H, &t, &hs, &table_rc, &table_bytes] {
+    auto table_upload = [H, &t, &hs, &table_rc, &table_err, &table_bytes] {
         table_rc = [&]() -> int {
             HIPCHK(hipSetDevice(H->device));
+            int rc;
             auto &K = H->d_misc;
             DevTables &T = H->T;
             const size_t mark = upload_bytes();
-            if (upload(K, hs.lidx, &H->d_lidx) || upload(K, hs.uidx, &H->d_uidx) || upload(K, t.ucolptr, &H->d_ucolptr) ||
-                upload(K, t.unzcol, &H->d_unzcol) || upload(K, hs.xsup, &H->d_xsup)) return SLUAMD_EHIP;
+            if ((rc = upload(K, hs.lidx, &H->d_lidx, "the table lidx"))) return rc;
+            if ((rc = upload(K, hs.uidx, &H->d_uidx, "the table uidx"))) return rc;
+            if ((rc = upload(K, t.ucolptr, &H->d_ucolptr, "the table ucolptr"))) return rc;
+            if ((rc = upload(K, t.unzcol, &H->d_unzcol, "the table unzcol"))) return rc;
+            if ((rc = upload(K, hs.xsup, &H->d_xsup, "the table xsup"))) return rc;
             T.lidx = H->d_lidx; T.uidx = H->d_uidx; T.ucolptr = H->d_ucolptr; T.unzcol = H->d_unzcol; T.xsup = H->d_xsup;
-#define UP(field, vec, type) { type *p_; if (upload(K, vec, &p_)) return SLUAMD_EHIP; T.field = p_; }
+#define UP(field, vec, type) { type *p_; if ((rc = upload(K, vec, &p_, "the table " #field))) return rc; T.field = p_; }
             UP(sn_lval, t.sn_lval, int64_t) UP(sn_uval, t.sn_uval, int64_t) UP(sn_lidx, t.sn_lidx, int64_t) UP(sn_uidx, t.sn_uidx, int64_t)
             UP(sn_dinv, t.sn_dinv, int64_t) UP(sn_dptr, t.sn_dptr, int64_t) UP(sn_inv, t.sn_inv, int64_t)
             UP(sn_nsupr, t.sn_nsupr, int) UP(sn_flags, t.sn_flags, int) UP(sn_ldiag, t.sn_ldiag, int) UP(sn_dlda, t.sn_dlda, int)
@@ -1667,6 +1679,7 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
             table_bytes = upload_bytes() - mark;
             return 0;
         }();
+        if (table_rc) table_err = get_error();
     };
     if (!sync_tables) table_job.th = std::thread(table_upload);
 
@@ -1685,7 +1698,7 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
             int nslev = 0;
             build_solve_groups(*H, in, t, in.lists[zl], lvl[zl], S, slev, nslev, grp_descs, grp_tiles);
             if (!H->groups.empty()) {
-                H->ssched.assign(nz, LevelSched());
+                H->ssched.clear(); H->ssched.resize(nz);
                 build_solve_sched(*H, t, in.lists[zl], slev, nslev, H->ssched[zl]);
                 S.no_join = true;
             } else H->grp_of.clear();
@@ -1750,33 +1763,16 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
     auto &K = H->d_misc;
     DevTables &T = H->T;
     if (sync_tables) { table_upload(); table_bytes = 0; } else table_job.th.join();          // the block / tile tables went up beside the schedule construction
-    if (table_rc) return table_rc;
+    if (table_rc) { set_error(table_err); return table_rc; }
     upload_bytes() += table_bytes;
     H->h_sn_dinv = t.sn_dinv;
-    {
-        double *dv;
-        auto malloc_retry = [&](void **q, size_t bytes) {      // (once more after the arena pool gave its unused chunks back to the driver)
-            if (hipMalloc(q, bytes) == hipSuccess) return true;
-            (void) hipGetLastError();
-            devpool_trim(H->device);
-            return hipMalloc(q, bytes) == hipSuccess;
-        };
-        if (!malloc_retry((void **) &dv, esz * (size_t) std::max<int64_t>(t.dinv_total, 1))) { set_error("hipMalloc(dinv) failed"); return SLUAMD_ENOMEM; }
-        K.push_back(dv); T.dinv = dv;
-    }
-    if (!H->z) {   // Linv / Uinv of the owned diagonal blocks (solve); complex handles use their own first-correct solves
-        double *iv;
-        if (hipMalloc((void **) &iv, sizeof(double) * (size_t) std::max<int64_t>(t.inv_total, 1)) != hipSuccess) {
-            (void) hipGetLastError();
-            devpool_trim(H->device);
-            if (hipMalloc((void **) &iv, sizeof(double) * (size_t) std::max<int64_t>(t.inv_total, 1)) != hipSuccess) { set_error("hipMalloc(inv) failed"); return SLUAMD_ENOMEM; }
-        }
-        K.push_back(iv); T.inv = iv;
-    }
+    if ((rc = K.alloc(&T.dinv, (esz / 8) * (size_t) std::max<int64_t>(t.dinv_total, 1), "the inverted diagonal sub-blocks (dinv)"))) return rc;
+    // Linv / Uinv of the owned diagonal blocks (solve); complex handles use their own first-correct solves
+    if (!H->z && (rc = K.alloc(&T.inv, (size_t) std::max<int64_t>(t.inv_total, 1), "the inverses of the diagonal blocks (Linv / Uinv)"))) return rc;
     if (!H->z && g.Pr * g.Pc == 1 && H->env.solve_join) { H->h_lrow_near.assign(std::max<size_t>(t.lrow.size(), 1), 0); H->h_ucol_near.assign(std::max<size_t>(t.ucol_gc.size(), 1), 0); }
     H->setup.lap("upload.block_tile_tables");
-    for (auto &S : H->sched) if (upload_schedule(*H, S, t)) return SLUAMD_EHIP;
-    for (auto &S : H->ssched) if (S.nlevels && upload_schedule(*H, S, t)) return SLUAMD_EHIP;
+    for (auto &S : H->sched) if ((rc = upload_schedule(*H, S, t))) return rc;
+    for (auto &S : H->ssched) if (S.nlevels && (rc = upload_schedule(*H, S, t))) return rc;
     if (!H->groups.empty()) {
         std::vector<GrpDesc> gd(H->groups.size());
         for (size_t gi = 0; gi < gd.size(); ++gi) {
@@ -1784,9 +1780,10 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
             gd[gi].nm = G.nm; gd[gi].nG = G.nG; gd[gi].ginv = G.ginv;
             for (int m = 0; m < 4; ++m) { gd[gi].k[m] = G.k[m]; gd[gi].o[m] = G.o[m]; gd[gi].w[m] = G.w[m]; }
         }
-        if (upload(K, gd, &H->d_grpdesc) || upload(K, grp_descs, &H->d_gemmdesc) || upload(K, grp_tiles, &H->d_gemmtiles)) return SLUAMD_EHIP;
-        if (hipMalloc((void **) &H->d_gscr, sizeof(double) * (size_t) (4 * GRP_SCR)) != hipSuccess) { set_error("hipMalloc of the group scratch failed"); return SLUAMD_ENOMEM; }
-        K.push_back(H->d_gscr);
+        if ((rc = upload(K, gd, &H->d_grpdesc, "the table gd"))) return rc;
+        if ((rc = upload(K, grp_descs, &H->d_gemmdesc, "the table grp_descs"))) return rc;
+        if ((rc = upload(K, grp_tiles, &H->d_gemmtiles, "the table grp_tiles"))) return rc;
+        if ((rc = H->d_gscr.alloc(4 * GRP_SCR, H->device, "the scratch of the merged chain groups"))) return rc;
         int lo = 0, hi = 0;
         hipDeviceGetStreamPriorityRange(&lo, &hi);
         HIPCHK(hipStreamCreateWithPriority(&H->gstream, hipStreamNonBlocking, lo));
@@ -1800,21 +1797,30 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
     T.lrow_near = nullptr; T.ucol_near = nullptr;
     if (!H->h_lrow_near.empty()) {
         uint8_t *p0, *p1;
-        if (upload(K, H->h_lrow_near, &p0) || upload(K, H->h_ucol_near, &p1)) return SLUAMD_EHIP;
+        if ((rc = upload(K, H->h_lrow_near, &p0, "the table lrow_near"))) return rc;
+        if ((rc = upload(K, H->h_ucol_near, &p1, "the table ucol_near"))) return rc;
         T.lrow_near = p0; T.ucol_near = p1;
         std::vector<uint8_t>().swap(H->h_lrow_near); std::vector<uint8_t>().swap(H->h_ucol_near);
     }
     if (H->fused_pairs) {
         int *p0, *p1, *p2, *p3, *p4, *p5;
-        if (upload(K, H->h_fuse_prev, &p0) || upload(K, H->h_defer, &p1) || upload(K, H->h_pair_roff, &p2) ||
-            upload(K, H->h_pair_coff, &p3) || upload(K, H->h_pair_rowmap, &p4) || upload(K, H->h_pair_colinfo, &p5)) return SLUAMD_EHIP;
+        if ((rc = upload(K, H->h_fuse_prev, &p0, "the table fuse_prev"))) return rc;
+        if ((rc = upload(K, H->h_defer, &p1, "the table defer"))) return rc;
+        if ((rc = upload(K, H->h_pair_roff, &p2, "the table pair_roff"))) return rc;
+        if ((rc = upload(K, H->h_pair_coff, &p3, "the table pair_coff"))) return rc;
+        if ((rc = upload(K, H->h_pair_rowmap, &p4, "the table pair_rowmap"))) return rc;
+        if ((rc = upload(K, H->h_pair_colinfo, &p5, "the table pair_colinfo"))) return rc;
         T.fuse_prev = p0; T.defer = p1; T.pair_roff = p2; T.pair_coff = p3; T.pair_rowmap = p4; T.pair_colinfo = p5;
     }
     H->st.reserved_i = H->fused_pairs;   // K-fused supernode pairs (diagnostic)
     H->st.schur_tiles = 0;               // until the first factorisation: the PLANNED tile executions of one factorisation (list schedules)
     for (auto &S : H->sched) H->st.schur_tiles += (int64_t) S.ulist.size();
-    HIPCHK(hipMalloc((void **) &H->d_info, 8 * sizeof(int)));
-    if (H->z) { std::vector<int> zero(std::max(ns, 1), 0); if (upload(K, zero, &H->d_ztickets)) return SLUAMD_EHIP; }
+    if ((rc = H->d_info.alloc(8, H->device, "the factorisation's info words"))) return rc;
+    if (H->z) {
+        if ((rc = H->d_ztickets.alloc(std::max(ns, 1), H->device, "the ticket counters of the fused backward links"))) return rc;
+        HIPCHK(hipMemset(H->d_ztickets.p, 0, sizeof(int) * (size_t) std::max(ns, 1)));
+        upload_bytes() += sizeof(int) * (size_t) std::max(ns, 1);
+    }
     rc = eng::setup();
     if (rc) return rc;
     H->setup.lap("upload.rest");
@@ -1824,16 +1830,16 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
         size_t fr = 0, tot = 0;
         hipMemGetInfo(&fr, &tot);
         char msg[512];
-        snprintf(msg, sizeof msg, "hipMalloc of the value arena failed: rank (%d,%d,%d) of the %d x %d x %d grid needs %.1f GB (own L/U slots %.1f GB + exchange scratch %.1f GB) "
+        snprintf(msg, sizeof msg, " -- rank (%d,%d,%d) of the %d x %d x %d grid needs %.1f GB (own L/U slots %.1f GB + exchange scratch %.1f GB) "
                  "and %.1f GB of %.1f GB are free on device %d -- use a larger process grid (scripts/capacity.py prints the per-rank storage of a grid)",
                  H->grid.r, H->grid.c, H->grid.z, H->grid.Pr, H->grid.Pc, H->grid.Pz, esz * (double) H->arena_len / 1e9, esz * (double) H->own_len / 1e9,
                  esz * (double) (H->arena_len - H->own_len) / 1e9, fr / 1e9, tot / 1e9, H->device);
-        set_error(msg);
+        set_error(arena_err + msg);
         return SLUAMD_ENOMEM;
     }
     if (arena_rc) { set_error("allocation / zero fill of the value arena failed"); return SLUAMD_EHIP; }
     H->setup.lap("arena_alloc_zero_wait");
-    T.val = H->d_val;
+    T.val = H->d_val.p;
     H->st.nnz_L = hs.nnzL; H->st.nnz_U = hs.nnzU;
     // everything this handle allocated on the device: the value arena, the inverse stores and every uploaded table (index images, block / tile
     // tables, tile lists, unit lists and records, pair maps; round 3 counted the index images only)

@@ -67,13 +67,12 @@ struct HostTables {
 };
 
 inline size_t &upload_bytes() { static thread_local size_t b = 0; return b; }   // bytes of the tables this thread uploaded (handle creation runs on one thread)
+// a host table onto the device, owned by `keep`: SLUAMD_ENOMEM (the message names `what`) or SLUAMD_EHIP
 template <class Tv>
-static int upload(std::vector<void *> &keep, const std::vector<Tv> &h, Tv **d)
+static int upload(DevBag &keep, const std::vector<Tv> &h, Tv **d, const char *what)
 {
-    size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(Tv);
-    upload_bytes() += bytes;
-    HIPCHK(hipMalloc((void **) d, bytes));
-    keep.push_back(*d);
+    upload_bytes() += std::max<size_t>(h.size(), 1) * sizeof(Tv);
+    if (int rc = keep.alloc(d, h.size(), what)) return rc;
     if (!h.empty()) HIPCHK(hipMemcpy(*d, h.data(), h.size() * sizeof(Tv), hipMemcpyHostToDevice));
     return 0;
 }

@@ -4,7 +4,7 @@
 // a policy K:
 //   K::z                 complex16 (values, x, b, r_perm of two doubles)
 //   K::attach, K::other  names for the error messages: this precision's attach call, the other precision's refinement call
-//   K::residual(s, H, x, b, r_perm, safe1, safe2)   r_perm = Pc (b - A x), *H->d_rfs_s = max(*H->d_rfs_s, berr bits)
+//   K::residual(s, H, x, b, r_perm, safe1, safe2)   r_perm = Pc (b - A x), *H->d_rfs_s.p = max(*H->d_rfs_s.p, berr bits)
 //   K::update(s, H, dx_perm, x)                     x += Pc^T dx_perm
 //   K::solve(H, r_perm, n)                          the correction, in place in r_perm: run_solve_dev for A x = b; the transposed policies run the
 //                                                   transposed sweeps (A^T d = r is A1^T (Pc d) = Pc r for the factors of A1 = Pc A Pc^T: the same
@@ -26,7 +26,7 @@ int attach_rfs(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, co
 template <class K> int rfs_checks(const Handle *H)
 {
     if (H->z != K::z) { set_error(std::string(H->z ? "complex16" : "double") + " handle: call " + K::other); return SLUAMD_EINVAL; }
-    if (!H->d_rfs_rp) { set_error(std::string("no matrix attached: call ") + K::attach + " first"); return SLUAMD_EINVAL; }
+    if (!H->d_rfs_rp.p) { set_error(std::string("no matrix attached: call ") + K::attach + " first"); return SLUAMD_EINVAL; }
     if (H->rfs_z != K::z) { set_error(std::string("the attached matrix is ") + (H->rfs_z ? "complex16" : "double") + ": call " + K::other); return SLUAMD_EINVAL; }
     return 0;
 }
@@ -46,7 +46,7 @@ template <class K> int rfs_dev(sluamd_handle_t h, const double *d_B, int64_t ldb
     const int ITMAX = 20;                                   // pdgsrfs.c:371
     const double eps = 0x1p-53, safmin = 2.2250738585072014e-308;
     const double safe1 = (double) (n + 1) * safmin, safe2 = safe1 / eps;
-    double *r_perm = H->d_rfs_work;
+    double *r_perm = H->d_rfs_work.p;
     hipStream_t s = H->stream;
     int count = 0;
     for (int j = 0; j < nrhs; ++j) {
@@ -55,10 +55,10 @@ template <class K> int rfs_dev(sluamd_handle_t h, const double *d_B, int64_t ldb
         double lstres = 3.0;
         count = 0;
         for (;;) {
-            HIPCHK(hipMemsetAsync(H->d_rfs_s, 0, sizeof(unsigned long long), s));
+            HIPCHK(hipMemsetAsync(H->d_rfs_s.p, 0, sizeof(unsigned long long), s));
             K::residual(s, H, Xc, Bc, r_perm, safe1, safe2);
             double sv = 0.0;
-            HIPCHK(hipMemcpyAsync(&sv, H->d_rfs_s, sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(&sv, H->d_rfs_s.p, sizeof(double), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             berr[j] = sv;
             int go = (sv > eps && sv * 2 <= lstres && count < ITMAX) ? 1 : 0;
@@ -89,7 +89,7 @@ template <class K> int rfs_host(sluamd_handle_t h, const double *B, int64_t ldb,
     const int vs = K::z ? 2 : 1;
     const int64_t n = H->hs.n;
     const size_t col = sizeof(double) * (size_t) n * vs;
-    double *d_b = H->d_rfs_work + (size_t) n * vs, *d_x = H->d_rfs_work + 2 * (size_t) n * vs;
+    double *d_b = H->d_rfs_work.p + (size_t) n * vs, *d_x = H->d_rfs_work.p + 2 * (size_t) n * vs;
     int last = 0;
     for (int j = 0; j < nrhs; ++j) {
         HIPCHK(hipMemcpy(d_b, B + (size_t) j * ldb * vs, col, hipMemcpyHostToDevice));

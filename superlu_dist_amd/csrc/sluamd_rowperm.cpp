@@ -16,19 +16,7 @@ using namespace sluamd;
 
 namespace {
 
-struct DevBufs {                // every device allocation of one call, freed on any way out
-    std::vector<void *> p;
-    hipStream_t s = nullptr;
-    ~DevBufs() { for (void *q : p) hipFree(q); if (s) hipStreamDestroy(s); }
-    template <class T> hipError_t get(T **out, size_t cnt)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, sizeof(T) * std::max<size_t>(cnt, 1));
-        if (e == hipSuccess) p.push_back(q);
-        *out = (T *) q;
-        return e;
-    }
-};
+struct OwnStream { hipStream_t s = nullptr; ~OwnStream() { if (s) hipStreamDestroy(s); } };
 
 double exp2_exact(double x) { return x == std::floor(x) && std::fabs(x) < 1000.0 ? std::ldexp(1.0, (int) x) : std::exp2(x); }
 
@@ -63,15 +51,21 @@ int large_diag(int device, int64_t n, const sluamd_int_t *rowptr, const sluamd_i
     auto lap = [&](int k, std::chrono::steady_clock::time_point &t0) { const auto t1 = now(); t_ms[k] += std::chrono::duration<double, std::milli>(t1 - t0).count(); t0 = t1; };
     auto t0 = now();
 
-    DevBufs D;
-    HIPCHK(hipStreamCreate(&D.s));
-    hipStream_t s = D.s;
+    DevBag D;                   // every device allocation of this call, freed on any way out
+    D.device = device;
+    OwnStream own;
+    HIPCHK(hipStreamCreate(&own.s));
+    hipStream_t s = own.s;
     const int ni = (int) n;
     int *d_rp, *d_ci, *d_rowmatch, *d_colmatch, *d_prop, *d_count;
     double *d_av, *d_cmax, *d_cost, *d_u, *d_v;
-    HIPCHK(D.get(&d_rp, (size_t) n + 1)); HIPCHK(D.get(&d_ci, (size_t) nnz)); HIPCHK(D.get(&d_av, (size_t) nnz * (z ? 2 : 1)));
-    HIPCHK(D.get(&d_cmax, (size_t) n)); HIPCHK(D.get(&d_cost, (size_t) nnz)); HIPCHK(D.get(&d_u, (size_t) n)); HIPCHK(D.get(&d_v, (size_t) n));
-    HIPCHK(D.get(&d_rowmatch, (size_t) n)); HIPCHK(D.get(&d_colmatch, (size_t) n)); HIPCHK(D.get(&d_prop, (size_t) n)); HIPCHK(D.get(&d_count, 1));
+    int rc;
+    if ((rc = D.alloc(&d_rp, (size_t) n + 1, "the matching's copy of A (row pointers)")) || (rc = D.alloc(&d_ci, (size_t) nnz, "the matching's copy of A (column indices)")) ||
+        (rc = D.alloc(&d_av, (size_t) nnz * (z ? 2 : 1), "the matching's copy of A (values)")) || (rc = D.alloc(&d_cmax, (size_t) n, "the matching's column maxima")) ||
+        (rc = D.alloc(&d_cost, (size_t) nnz, "the matching's costs")) || (rc = D.alloc(&d_u, (size_t) n, "the matching's row duals")) ||
+        (rc = D.alloc(&d_v, (size_t) n, "the matching's column duals")) || (rc = D.alloc(&d_rowmatch, (size_t) n, "the matching's row matches")) ||
+        (rc = D.alloc(&d_colmatch, (size_t) n, "the matching's column matches")) || (rc = D.alloc(&d_prop, (size_t) n, "the matching's proposals")) ||
+        (rc = D.alloc(&d_count, 1, "the matching's counter"))) return rc;
     HIPCHK(hipMemcpyAsync(d_rp, rowptr, sizeof(int) * ((size_t) n + 1), hipMemcpyHostToDevice, s));
     if (nnz) {
         HIPCHK(hipMemcpyAsync(d_ci, colind, sizeof(int) * (size_t) nnz, hipMemcpyHostToDevice, s));

@@ -19,23 +19,15 @@ using namespace sluamd;
 
 namespace {
 
-bool malloc_retry(Handle *H, void **q, size_t bytes)      // (once more after the arena pool gave its unused chunks back to the driver)
-{
-    if (hipMalloc(q, bytes) == hipSuccess) return true;
-    (void) hipGetLastError();
-    devpool_trim(H->device);
-    return hipMalloc(q, bytes) == hipSuccess;
-}
-
 int ensure_tindex(Handle *H, const char *who)
 {
-    if (H->d_rfs_tcp) return 0;
+    if (H->d_rfs_tcp.p) return 0;
     HIPCHK(hipSetDevice(H->device));
     H->setup.start();
     const int64_t n = H->hs.n, nnz = H->rfs_nnz;
     std::vector<int> rp((size_t) n + 1), ci((size_t) std::max<int64_t>(nnz, 1));
-    HIPCHK(hipMemcpy(rp.data(), H->d_rfs_rp, sizeof(int) * (n + 1), hipMemcpyDeviceToHost));
-    if (nnz) HIPCHK(hipMemcpy(ci.data(), H->d_rfs_ci, sizeof(int) * nnz, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rp.data(), H->d_rfs_rp.p, sizeof(int) * (n + 1), hipMemcpyDeviceToHost));
+    if (nnz) HIPCHK(hipMemcpy(ci.data(), H->d_rfs_ci.p, sizeof(int) * nnz, hipMemcpyDeviceToHost));
     // stable counting sort by column: the rows are visited in ascending order, so they ascend inside every column
     std::vector<int> tcp((size_t) n + 1, 0), tri((size_t) std::max<int64_t>(nnz, 1)), tpos((size_t) std::max<int64_t>(nnz, 1));
     for (int64_t e = 0; e < nnz; ++e) {
@@ -50,17 +42,17 @@ int ensure_tindex(Handle *H, const char *who)
             for (int e = rp[i]; e < rp[i + 1]; ++e) { const int p = next[ci[e]]++; tri[p] = (int) i; tpos[p] = e; }
         }
     }
-    int *d[3] = {nullptr, nullptr, nullptr};
-    const size_t bytes[3] = {sizeof(int) * ((size_t) n + 1), sizeof(int) * tri.size(), sizeof(int) * tpos.size()};
-    const int *src[3] = {tcp.data(), tri.data(), tpos.data()};
-    for (int k = 0; k < 3; ++k)
-        if (!malloc_retry(H, (void **) &d[k], bytes[k]) || hipMemcpy(d[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess) {
+    DevBuf<int> d[3];           // handed to the handle once all three are up
+    const std::vector<int> *src[3] = {&tcp, &tri, &tpos};
+    for (int k = 0; k < 3; ++k) {
+        if (int rc = d[k].alloc((int64_t) src[k]->size(), H->device, "the transposed index of the attached matrix")) return rc;
+        if (hipMemcpy(d[k].p, src[k]->data(), sizeof(int) * src[k]->size(), hipMemcpyHostToDevice) != hipSuccess) {
             (void) hipGetLastError();
-            for (int q = 0; q <= k; ++q) if (d[q]) hipFree(d[q]);
-            set_error(std::string(who) + ": the transposed index of the attached matrix could not be allocated / uploaded");
-            return SLUAMD_ENOMEM;
+            set_error(std::string(who) + ": the transposed index of the attached matrix could not be uploaded");
+            return SLUAMD_EHIP;
         }
-    H->d_rfs_tcp = d[0]; H->d_rfs_tri = d[1]; H->d_rfs_tpos = d[2];
+    }
+    H->d_rfs_tcp = std::move(d[0]); H->d_rfs_tri = std::move(d[1]); H->d_rfs_tpos = std::move(d[2]);
     H->setup.lap("refine.transposed_index");
     return 0;
 }
@@ -70,13 +62,13 @@ template <bool Z, bool CONJ> struct TRfs {
     static constexpr const char *attach = Z ? "sluamd_zAttachMatrix" : "sluamd_dAttachMatrix", *other = Z ? "sluamd_pdgsrfs3d_trans" : "sluamd_pzgsrfs3d_trans";
     static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
     {
-        if (Z) eng::zrfs_residual_t(s, CONJ, (int) H->hs.n, H->d_rfs_tcp, H->d_rfs_tri, H->d_rfs_tpos, H->d_rfs_av, x, b, H->d_rfs_pc, r_perm, H->d_rfs_s, safe1, safe2);
-        else eng::rfs_residual_t(s, (int) H->hs.n, H->d_rfs_tcp, H->d_rfs_tri, H->d_rfs_tpos, H->d_rfs_av, x, b, H->d_rfs_pc, r_perm, H->d_rfs_s, safe1, safe2);
+        if (Z) eng::zrfs_residual_t(s, CONJ, (int) H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
+        else eng::rfs_residual_t(s, (int) H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
     }
     static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x)
     {
-        if (Z) eng::zrfs_update(s, (int) H->hs.n, H->d_rfs_pc, dx_perm, x);
-        else eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc, dx_perm, x);
+        if (Z) eng::zrfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
+        else eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
     }
     static int solve(Handle *H, double *r_perm, int n) { return run_tsolve(H, Z && CONJ, r_perm, n, 1); }
 };

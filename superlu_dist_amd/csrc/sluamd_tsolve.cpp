@@ -163,16 +163,11 @@ int tsolve_host(sluamd_handle_t h, int trans, double *x, int64_t ldx, int32_t nr
     Handle *H = &h->H;
     HIPCHK(hipSetDevice(H->device));
     const int64_t need = ldx * nrhs * (H->z ? 2 : 1);   // in doubles
-    if (need > H->x_cap) {
-        if (H->d_x) hipFree(H->d_x);
-        H->d_x = nullptr; H->x_cap = 0;
-        HIPCHK(hipMalloc((void **) &H->d_x, sizeof(double) * need));
-        H->x_cap = need;
-    }
-    HIPCHK(hipMemcpy(H->d_x, x, sizeof(double) * need, hipMemcpyHostToDevice));
-    int rc = tsolve_dev(h, trans, H->d_x, ldx, nrhs);
+    if (int rc = H->d_x.reserve(need, H->device, "the right-hand sides")) return rc;
+    HIPCHK(hipMemcpy(H->d_x.p, x, sizeof(double) * need, hipMemcpyHostToDevice));
+    int rc = tsolve_dev(h, trans, H->d_x.p, ldx, nrhs);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(x, H->d_x, sizeof(double) * need, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(x, H->d_x.p, sizeof(double) * need, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -23,53 +23,48 @@ int update_values(sluamd_handle_t h, const void *nzval, sluamd_update_t *out, bo
     if (!nzval) { set_error(me + "null values"); return SLUAMD_EINVAL; }
     Handle *H = &h->H;
     if (H->z != z) { set_error(me + (z ? "double handle: call sluamd_dUpdateValues" : "complex16 handle: call sluamd_zUpdateValues")); return SLUAMD_EINVAL; }
-    if (!H->d_apos || !H->d_aent || H->a_csr_nnz < 0) {
+    if (!H->d_apos.p || !H->d_aent.p || H->a_csr_nnz < 0) {
         set_error(me + "the handle was not created from the symbolic structure (sluamd_[dz]CreateLUHandleFromSymb[Grid]): a view-created handle takes new values in store form through sluamd_dSetValues / sluamd_zSetValues");
         return SLUAMD_EINVAL;
     }
-    const bool attached = H->d_rfs_rp != nullptr;
+    const bool attached = H->d_rfs_rp.p != nullptr;
     const bool scaled = H->eq_row || H->eq_col;
     if (attached && (H->rfs_z != z || H->rfs_nnz != H->a_csr_nnz)) { set_error(me + "the attached matrix is not the one the handle was created from (precision or number of entries)"); return SLUAMD_EINVAL; }
     if (out && !attached) { set_error(me + "anorm needs an attached matrix (sluamd_[dz]AttachMatrix or sluamd_[dz]Equilibrate): the handle keeps the CSR structure only with one; pass out = NULL"); return SLUAMD_EINVAL; }
-    if (scaled && !H->d_upd_ij && !attached) { set_error(me + "the equilibrated handle has lost its attached matrix: the rows and columns of its entries cannot be rebuilt"); return SLUAMD_EINVAL; }
+    if (scaled && !H->d_upd_ij.p && !attached) { set_error(me + "the equilibrated handle has lost its attached matrix: the rows and columns of its entries cannot be rebuilt"); return SLUAMD_EINVAL; }
     HIPCHK(hipSetDevice(H->device));
     hipStream_t s = H->stream;
     const int n = (int) H->hs.n;
     const size_t esz = z ? 16 : 8;
     // every allocation before anything is queued: a call that fails here has not touched the handle's values
-    if (host && H->a_csr_nnz > H->upd_stage_cap) {
-        if (H->d_upd_stage) { HIPCHK(hipStreamSynchronize(s)); hipFree(H->d_upd_stage); }
-        H->d_upd_stage = nullptr; H->upd_stage_cap = 0;
-        HIPCHK(hipMalloc((void **) &H->d_upd_stage, esz * (size_t) H->a_csr_nnz));
-        H->upd_stage_cap = H->a_csr_nnz;
-    }
+    if (host) if (int rc = H->d_upd_stage.reserve(H->a_csr_nnz * (z ? 2 : 1), H->device, "the staged new values")) return rc;
     if (host && !H->ev_upd) HIPCHK(hipEventCreateWithFlags(&H->ev_upd, hipEventDisableTiming));
-    const bool build_ij = scaled && !H->d_upd_ij && H->a_nnz > 0;
-    struct Ij { int2 *p = nullptr; ~Ij() { if (p) hipFree(p); } } ij;        // handed to the handle with the launch that fills it
-    if (build_ij) HIPCHK(hipMalloc((void **) &ij.p, sizeof(int2) * (size_t) H->a_nnz));
-    struct Red { unsigned long long *p = nullptr; ~Red() { if (p) hipFree(p); } } red;
-    if (out) HIPCHK(hipMalloc((void **) &red.p, 3 * sizeof(unsigned long long)));
+    const bool build_ij = scaled && !H->d_upd_ij.p && H->a_nnz > 0;
+    DevBuf<int2> ij;                                                         // handed to the handle with the launch that fills it
+    if (build_ij) if (int rc = ij.alloc(H->a_nnz, H->device, "the rows and columns of the owned entries")) return rc;
+    DevBuf<unsigned long long> red;
+    if (out) if (int rc = red.alloc(3, H->device, "the reduction words of the 1-norm")) return rc;
 
     const void *d_nz = nzval;
     if (host && H->a_csr_nnz > 0) {
-        HIPCHK(hipMemcpyAsync(H->d_upd_stage, nzval, esz * (size_t) H->a_csr_nnz, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(H->d_upd_stage.p, nzval, esz * (size_t) H->a_csr_nnz, hipMemcpyHostToDevice, s));
         HIPCHK(hipEventRecord(H->ev_upd, s));
-        d_nz = H->d_upd_stage;
+        d_nz = H->d_upd_stage.p;
     }
-    if (build_ij) { H->d_upd_ij = ij.p; ij.p = nullptr; eng::update_rowcol(s, H->a_nnz, n, H->d_rfs_rp, H->d_rfs_ci, H->d_aent, H->d_upd_ij); }
-    const double *R = H->eq_row ? H->d_eq_r : nullptr, *Cs = H->eq_col ? H->d_eq_c : nullptr;
+    if (build_ij) { H->d_upd_ij = std::move(ij); eng::update_rowcol(s, H->a_nnz, n, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_aent.p, H->d_upd_ij.p); }
+    const double *R = H->eq_row ? H->d_eq_r.p : nullptr, *Cs = H->eq_col ? H->d_eq_c.p : nullptr;
     if (int rc = reset_store(H, false)) return rc;
-    eng::update_values(s, z, H->a_nnz, H->d_aent, H->d_upd_ij, d_nz, R, Cs, H->d_aval, H->d_apos, H->d_val);
+    eng::update_values(s, z, H->a_nnz, H->d_aent.p, H->d_upd_ij.p, d_nz, R, Cs, H->d_aval.p, H->d_apos.p, H->d_val.p);
     if (attached) {
-        double *colsum = out ? H->d_rfs_work : nullptr;         // the refinement's work vector, as sluamd_[dz]Equilibrate
+        double *colsum = out ? H->d_rfs_work.p : nullptr;         // the refinement's work vector, as sluamd_[dz]Equilibrate
         if (colsum) HIPCHK(hipMemsetAsync(colsum, 0, sizeof(double) * (size_t) n, s));
-        eng::update_attached(s, z, n, H->rfs_nnz, H->d_rfs_rp, H->d_rfs_ci, d_nz, R, Cs, H->d_rfs_av, colsum);
+        eng::update_attached(s, z, n, H->rfs_nnz, H->d_rfs_rp.p, H->d_rfs_ci.p, d_nz, R, Cs, H->d_rfs_av.p, colsum);
     }
     HIPCHK(hipGetLastError());
     if (out) {
         unsigned long long bits[3] = {~0ull, 0ull, ~0ull};
         HIPCHK(hipMemcpyAsync(red.p, bits, sizeof bits, hipMemcpyHostToDevice, s));
-        eng::eq_reduce(s, n, H->d_rfs_work, red.p);
+        eng::eq_reduce(s, n, H->d_rfs_work.p, red.p);
         HIPCHK(hipMemcpyAsync(bits, red.p, sizeof bits, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(hipGetLastError());
