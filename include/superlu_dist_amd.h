@@ -511,7 +511,7 @@ int sluamd_zUpdateValues_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_nz
 /* ---- Fixed-size batches: `count` systems A_k X_k = B_k of order m that share ONE sparsity pattern and differ in values, with info, berr and refinement steps
  * per matrix (the role of the reference's pdgssvx3d_csc_batch, SRC/double/pdgssvx3d_csc_batch.c, reached through pddrive3d -b).  Time stepping and ensembles:
  * hundreds of small systems, each of which would pay its own symbolic factorisation, plan, tables and arena as a handle of its own, with kernels too small
- * to fill the device.  The batch is the block-diagonal matrix diag(A_0 .. A_{count-1}) on ONE ordinary 1 x 1 x 1 double handle, planned for the replicated
+ * to fill the device.  The batch is the block-diagonal matrix diag(A_0 .. A_{count-1}) on ONE ordinary 1 x 1 x 1 handle, planned for the replicated
  * structure (sluamd_symb_replicate): count copies of one elimination tree are count-wide DAG levels of the same kernels.
  *   s: the symbolic structure of ONE matrix (maxsup <= 256), rowptr / colind its CSR pattern, perm_c_final the perm_c_out of its symbolic factorisation;
  *   nzval: matrix k's values at nzval + k stride (stride >= nnz), in the order of the shared CSR;
@@ -524,7 +524,8 @@ int sluamd_zUpdateValues_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_nz
  * what sluamd_pdgstrf3d returns for A_k factored alone under SLUAMD_INFO_FIRST.  A singular A_k disturbs no other matrix: its inf / NaN stay inside its own
  * blocks, and so do its solutions'.
  * sluamd_dBatchSolve[_dev]: pack (xp[k m + perm_c[i], j] = B_k[i, j]), the handle's solve (trans = SLUAMD_NOTRANS / _TRANS / _CONJ), unpack: the only passes over
- * the right-hand sides when refine == 0.  refine != 0 (SLUAMD_NOTRANS only, as sluamd_pdgssvx3d_solve): the loop of sluamd_pdgsrfs3d with the stopping rule
+ * the right-hand sides when refine == 0.  refine != 0: the loop of sluamd_pdgsrfs3d -- of sluamd_pdgsrfs3d_trans for SLUAMD_TRANS / SLUAMD_CONJ: the residual
+ * of A_k^T x = b / A_k^H x = b over the transposed index of the attached matrix, the correction by the transposed sweeps -- with the stopping rule
  * per matrix -- berr[k nrhs + j], steps[k] (those of the last right-hand side), SAFE1 / SAFE2 formed from m so that a matrix sees the constants it would see
  * alone; one copy of count doubles to the host per sweep; a column ends when no matrix continues; a matrix that has stopped keeps the X and berr of its
  * stopping sweep while the others go on.  The loop refines against the matrix ATTACHED to the batch's handle, which is the batch's own block-diagonal
@@ -532,10 +533,10 @@ int sluamd_zUpdateValues_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_nz
  * must be block diagonal too (the residual of matrix k reads X_k only), and sluamd_dBatchUpdateValues refuses while it is attached.
  * berr and steps may be NULL when refine == 0 (steps is then all zero).  nrhs == 0 returns 0.
  * sluamd_BatchHandle: the handle, borrowed (sluamd_get_stats, sluamd_setup_times, sluamd_plan_table; it dies with the batch).
- * Not available on a batch: complex16 and process grids (no entry point takes either), RowPerm and the single-matrix sluamd_dEquilibrate made through the
+ * Not available on a batch: process grids (no entry point takes one), RowPerm and the single-matrix sluamd_[dz]Equilibrate made through the
  * borrowed handle (every later batch call returns SLUAMD_EINVAL), replace_tiny_pivot (it needs a threshold
  * eps anorm_k per matrix inside the diagonal LU kernels), supernodes wider than 256 columns.  Other errors (SLUAMD_EINVAL): count <= 0, stride < nnz,
- * ldb or ldx < m, strides smaller than a block, a solve of an unfactored batch, refine with a transposed system or without berr.
+ * ldb or ldx < m, strides smaller than a block, a solve of an unfactored batch, refine without berr.
  * sluamd_dBatchEquilibrate: pdgsequ + pdlaqgs PER MATRIX, once per batch, before the factorisation.  out[k] is what sluamd_dEquilibrate returns for A_k alone:
  * equed, rowcnd, colcnd, amax, R and C (sluamd_BatchGetScalings: count m values each, matrix-major, ones where a side is not scaled) bit for bit -- the maxima
  * are exact --, anorm with the summation caveat of sluamd_equil_t::anorm.  A matrix with an exactly zero row or column gets its own out[k].info (i + 1, or
@@ -544,7 +545,13 @@ int sluamd_zUpdateValues_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_nz
  * matrix, (a r[i]) c[j] in that order, as sluamd_dUpdateValues does.  sluamd_dBatchSolve takes B and returns X in the caller's scaling (B scaled by R, X by C;
  * the roles swapped for a transposed system); with refine the scaled system is refined and berr is that of the scaled system, as in the reference.
  * Errors (SLUAMD_EINVAL): a second call; a batch whose handle had another matrix attached, or was equilibrated / row-permuted through sluamd_BatchHandle
- * (every batch call refuses such a handle). */
+ * (every batch call refuses such a handle).
+ * complex16 (the role of pzgssvx3d_csc_batch): the sluamd_zBatch* calls are the twins of the sluamd_dBatch* calls with the same contract on a complex16 handle;
+ * values, B and X are sluamd_doublecomplex, strides and leading dimensions count values, R, C and berr are real.  SLUAMD_TRANS solves A_k^T x = b, SLUAMD_CONJ
+ * A_k^H x = b (on a double batch the two are the same).  sluamd_zBatchFactor: a U diagonal entry is zero when it is exactly 0 + 0i.  sluamd_zBatchEquilibrate:
+ * out[k] is what sluamd_zEquilibrate returns for A_k alone (maxima of |re| + |im|, anorm of the moduli).  Refinement: berr from the moduli |re| + |im| of
+ * sluamd_pzgsrfs3d.  sluamd_BatchGetScalings, sluamd_BatchHandle and sluamd_BatchDestroy serve both precisions.  A d call on a complex16 batch and a z call on
+ * a double batch return SLUAMD_EINVAL with a message that names the other call. */
 typedef struct sluamd_batch_s *sluamd_batch_t;
 int sluamd_dBatchCreate(sluamd_batch_t *b, sluamd_symb_t s, int32_t count, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const double *nzval,
                         int64_t stride, const sluamd_int_t *perm_c_final, const sluamd_options_t *opt);
@@ -557,6 +564,16 @@ int sluamd_dBatchSolve(sluamd_batch_t b, int trans, const double *B, int64_t ldb
                        int refine, double *berr /* [count * nrhs] */, int32_t *steps /* [count] */);
 int sluamd_dBatchSolve_dev(sluamd_batch_t b, int trans, const double *d_B, int64_t ldb, int64_t strideB, double *d_X, int64_t ldx, int64_t strideX, int32_t nrhs,
                            int refine, double *berr, int32_t *steps);
+int sluamd_zBatchCreate(sluamd_batch_t *b, sluamd_symb_t s, int32_t count, const sluamd_int_t *rowptr, const sluamd_int_t *colind,
+                        const sluamd_doublecomplex *nzval, int64_t stride, const sluamd_int_t *perm_c_final, const sluamd_options_t *opt);
+int sluamd_zBatchUpdateValues(sluamd_batch_t b, const sluamd_doublecomplex *nzval, int64_t stride);
+int sluamd_zBatchUpdateValues_dev(sluamd_batch_t b, const sluamd_doublecomplex *d_nzval, int64_t stride);
+int sluamd_zBatchEquilibrate(sluamd_batch_t b, sluamd_equil_t *out /* [count] */);
+int sluamd_zBatchFactor(sluamd_batch_t b, int32_t *info /* [count] */);
+int sluamd_zBatchSolve(sluamd_batch_t b, int trans, const sluamd_doublecomplex *B, int64_t ldb, int64_t strideB, sluamd_doublecomplex *X, int64_t ldx,
+                       int64_t strideX, int32_t nrhs, int refine, double *berr /* [count * nrhs] */, int32_t *steps /* [count] */);
+int sluamd_zBatchSolve_dev(sluamd_batch_t b, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, int64_t strideB, sluamd_doublecomplex *d_X, int64_t ldx,
+                           int64_t strideX, int32_t nrhs, int refine, double *berr, int32_t *steps);
 sluamd_handle_t sluamd_BatchHandle(sluamd_batch_t b);
 void sluamd_BatchDestroy(sluamd_batch_t b);
 

@@ -73,6 +73,8 @@ EXPORTS = [
     "sluamd_dUpdateValues", "sluamd_dUpdateValues_dev", "sluamd_zUpdateValues", "sluamd_zUpdateValues_dev",
     "sluamd_symb_replicate", "sluamd_dBatchCreate", "sluamd_dBatchUpdateValues", "sluamd_dBatchUpdateValues_dev", "sluamd_dBatchFactor", "sluamd_dBatchEquilibrate", "sluamd_BatchGetScalings",
     "sluamd_dBatchSolve", "sluamd_dBatchSolve_dev", "sluamd_BatchHandle", "sluamd_BatchDestroy",
+    "sluamd_zBatchCreate", "sluamd_zBatchUpdateValues", "sluamd_zBatchUpdateValues_dev", "sluamd_zBatchFactor", "sluamd_zBatchEquilibrate",
+    "sluamd_zBatchSolve", "sluamd_zBatchSolve_dev",
     "sluamd_comm_rccl_unique_id", "sluamd_comm_create_rccl", "sluamd_comm_create_callbacks", "sluamd_comm_create_local",
     "sluamd_comm_selftest", "sluamd_comm_rank", "sluamd_comm_size", "sluamd_comm_destroy", "sluamd_dCreateLUHandleGrid",
     "sluamd_dCreateLUHandleFromSymbGrid", "sluamd_zCreateLUHandleGrid", "sluamd_zCreateLUHandleFromSymbGrid",
@@ -198,6 +200,14 @@ def bind(L):
         L.sluamd_BatchHandle.restype = C.c_void_p
         L.sluamd_BatchDestroy.argtypes = [C.c_void_p]
         L.sluamd_BatchDestroy.restype = None
+    # complex16 batches: the same signatures, values as void pointers
+    if hasattr(L, "sluamd_zBatchCreate"):
+        L.sluamd_zBatchCreate.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, P_int, P_int, C.c_void_p, C.c_int64, P_int, C.POINTER(Options)]
+        L.sluamd_zBatchUpdateValues.argtypes = L.sluamd_dBatchUpdateValues.argtypes
+        L.sluamd_zBatchUpdateValues_dev.argtypes = L.sluamd_dBatchUpdateValues_dev.argtypes
+        L.sluamd_zBatchFactor.argtypes = L.sluamd_dBatchFactor.argtypes
+        L.sluamd_zBatchEquilibrate.argtypes = L.sluamd_dBatchEquilibrate.argtypes
+        L.sluamd_zBatchSolve.argtypes = L.sluamd_zBatchSolve_dev.argtypes = L.sluamd_dBatchSolve.argtypes
     L.sluamd_PlanTransposedSweeps.argtypes = [C.c_void_p]
     L.sluamd_plan_xlists.argtypes = [C.c_void_p, C.c_int, P_int, C.c_int64, C.POINTER(C.c_int64)]
     L.sluamd_comm_rccl_unique_id.argtypes = [C.c_void_p]

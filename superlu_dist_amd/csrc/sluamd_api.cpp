@@ -269,9 +269,9 @@ static int create_from_symb(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_
     return 0;
 }
 
-int create_symb_handle_empty(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_options_t *opt)
+int create_symb_handle_empty(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_options_t *opt, bool z)
 {
-    return create_from_symb(out, s, nullptr, nullptr, nullptr, nullptr, opt, Grid{}, nullptr, nullptr, false, true);
+    return create_from_symb(out, s, nullptr, nullptr, nullptr, nullptr, opt, Grid{}, nullptr, nullptr, z, true);
 }
 
 }  // namespace sluamd

@@ -579,9 +579,9 @@ void update_attached(hipStream_t s, bool z, int n, int64_t nnz, const int *rp, c
 // the flags, the zero-fill of the arena and (scatter) the re-distribution of d_aval that sluamd_dResetValues queues on the handle's stream (sluamd_api.cpp);
 // sluamd_[dz]UpdateValues passes scatter = false and queues its own kernel behind the zero-fill
 int reset_store(Handle *H, bool scatter);
-// a 1 x 1 x 1 double handle planned for the structure `s` whose value arena is zero-filled and that keeps no map of any matrix's entries (sluamd_api.cpp):
-// the batch object (sluamd_batch.cpp) distributes the values of its matrices itself, through the entry map of ONE of them
-int create_symb_handle_empty(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_options_t *opt);
+// a 1 x 1 x 1 handle (z: complex16) planned for the structure `s` whose value arena is zero-filled and that keeps no map of any matrix's entries
+// (sluamd_api.cpp): the batch object (sluamd_batch.cpp) distributes the values of its matrices itself, through the entry map of ONE of them
+int create_symb_handle_empty(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_options_t *opt, bool z);
 
 }  // namespace sluamd
 

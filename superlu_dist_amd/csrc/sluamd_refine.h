@@ -22,6 +22,8 @@ void free_rfs(Handle *H);   // sluamd_api.cpp
 // device copy of the ORIGINAL matrix (CSR, z: doublecomplex values) + perm_c; `who` names the entry point in messages
 int attach_rfs(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, const sluamd_int_t *colind, const void *nzval,
                const sluamd_int_t *perm_c, bool z, const char *who);
+// the transposed index of the attached matrix (Handle::d_rfs_tcp / d_rfs_tri / d_rfs_tpos), built on first use: sluamd_trefine.cpp, which describes it
+int ensure_tindex(Handle *H, const char *who);
 
 template <class K> int rfs_checks(const Handle *H)
 {

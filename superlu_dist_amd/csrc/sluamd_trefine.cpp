@@ -17,9 +17,7 @@
 
 using namespace sluamd;
 
-namespace {
-
-int ensure_tindex(Handle *H, const char *who)
+int sluamd::ensure_tindex(Handle *H, const char *who)
 {
     if (H->d_rfs_tcp.p) return 0;
     HIPCHK(hipSetDevice(H->device));
@@ -56,6 +54,8 @@ int ensure_tindex(Handle *H, const char *who)
     H->setup.lap("refine.transposed_index");
     return 0;
 }
+
+namespace {
 
 template <bool Z, bool CONJ> struct TRfs {
     static constexpr bool z = Z;

@@ -808,7 +808,13 @@ pzgssvx3d = pdgssvx3d   # complex16 input (nzval complex) takes the pzgstrf3d / 
 
 class BatchHandle:
     """sluamd_batch_t: `count` matrices of one sparsity pattern on one handle (block-diagonal factorisation), with info, berr and refinement steps per
-    matrix.  Values [count, nnz] in the order of the shared CSR; right-hand sides [count, n] or [count, n, nrhs]."""
+    matrix.  Values [count, nnz] in the order of the shared CSR; right-hand sides [count, n] or [count, n, nrhs].  float64 throughout; ZBatchHandle is the
+    complex16 twin (sluamd_zBatch*)."""
+    _p, _dt = "d", np.float64          # the precision letter of the entry points, the dtype of values, b and x
+
+    @classmethod
+    def _fn(cls, what):
+        return f"sluamd_{cls._p}Batch{what}"
 
     def __init__(self, b, n, nnz, count):
         self._b = b
@@ -817,36 +823,38 @@ class BatchHandle:
     @classmethod
     def create(cls, symb, nzvals, deterministic=False, device=-1, replace_tiny=False):
         """symb: the Symbolic of ONE matrix; nzvals: [count, >= nnz] (a row's first nnz values are the matrix)"""
-        if np.iscomplexobj(nzvals):
-            raise ValueError("BatchHandle.create: complex16 values are not available on a batch (double precision only)")
-        nz = np.ascontiguousarray(nzvals, dtype=np.float64)
+        if cls._p == "d" and np.iscomplexobj(nzvals):
+            raise ValueError("BatchHandle.create: complex16 values belong on a ZBatchHandle (BatchHandle holds double precision only)")
+        nz = np.ascontiguousarray(nzvals, dtype=cls._dt)
         if nz.ndim != 2:
             raise ValueError("nzvals must be [count, nnz]")
         o = LUHandle._opts(replace_tiny=replace_tiny, deterministic=deterministic, device=device)
         b = C.c_void_p()
-        _lib.check(_lib.entry("sluamd_dBatchCreate")(C.byref(b), symb._h, nz.shape[0], _pi(symb.rowptr), _pi(symb.colind), _pd(nz), nz.shape[1],
-                                                     _pi(symb.perm_c), C.byref(o)), "sluamd_dBatchCreate")
+        _lib.check(_lib.entry(cls._fn("Create"))(C.byref(b), symb._h, nz.shape[0], _pi(symb.rowptr), _pi(symb.colind),
+                                                 nz.ctypes.data_as(C.c_void_p if cls._p == "z" else _lib.P_dbl), nz.shape[1], _pi(symb.perm_c), C.byref(o)),
+                   cls._fn("Create"))
         return cls(b, symb.n, len(symb.colind), nz.shape[0])
 
     def update_values(self, nzvals):
         """new values of the same pattern: a numpy array [count, >= nnz] (host form) or a torch device tensor of that shape (_dev form); the batch is
         unfactored afterwards"""
         if isinstance(nzvals, np.ndarray) or not hasattr(nzvals, "data_ptr"):
-            nz = np.ascontiguousarray(nzvals, dtype=np.float64)
+            nz = np.ascontiguousarray(nzvals, dtype=self._dt)
             if nz.ndim != 2 or nz.shape[0] != self.count:
                 raise ValueError(f"nzvals must be [{self.count}, >= {self.nnz}]")
-            _lib.check(_lib.entry("sluamd_dBatchUpdateValues")(self._b, nz.ctypes.data_as(C.c_void_p), nz.shape[1]), "sluamd_dBatchUpdateValues")
+            _lib.check(_lib.entry(self._fn("UpdateValues"))(self._b, nz.ctypes.data_as(C.c_void_p), nz.shape[1]), self._fn("UpdateValues"))
             return
         import torch
-        if nzvals.dtype != torch.float64 or nzvals.dim() != 2 or nzvals.shape[0] != self.count or not nzvals.is_contiguous() or not nzvals.is_cuda:
-            raise ValueError(f"device values must be a contiguous float64 device tensor [{self.count}, >= {self.nnz}]")
+        want = torch.complex128 if self._p == "z" else torch.float64
+        if nzvals.dtype != want or nzvals.dim() != 2 or nzvals.shape[0] != self.count or not nzvals.is_contiguous() or not nzvals.is_cuda:
+            raise ValueError(f"device values must be a contiguous {np.dtype(self._dt).name} device tensor [{self.count}, >= {self.nnz}]")
         torch.cuda.current_stream(nzvals.device).synchronize()      # what produced the tensor must be complete (contract of the _dev form)
-        _lib.check(_lib.entry("sluamd_dBatchUpdateValues_dev")(self._b, C.c_void_p(nzvals.data_ptr()), int(nzvals.shape[1])), "sluamd_dBatchUpdateValues_dev")
+        _lib.check(_lib.entry(self._fn("UpdateValues_dev"))(self._b, C.c_void_p(nzvals.data_ptr()), int(nzvals.shape[1])), self._fn("UpdateValues_dev"))
 
     def equilibrate(self):
-        """pdgsequ + pdlaqgs per matrix (sluamd_dBatchEquilibrate): a list of count dicts like LUHandle.equilibrate's (equed as "N" / "R" / "C" / "B")"""
+        """pdgsequ + pdlaqgs per matrix (sluamd_[dz]BatchEquilibrate): a list of count dicts like LUHandle.equilibrate's (equed as "N" / "R" / "C" / "B")"""
         out = (_lib.Equil * self.count)()
-        _lib.check(_lib.entry("sluamd_dBatchEquilibrate")(self._b, out), "sluamd_dBatchEquilibrate")
+        _lib.check(_lib.entry(self._fn("Equilibrate"))(self._b, out), self._fn("Equilibrate"))
         return [{"equed": EQUED[e.equed], "info": e.info, "rowcnd": e.rowcnd, "colcnd": e.colcnd, "amax": e.amax, "anorm": e.anorm} for e in out]
 
     def scalings(self):
@@ -858,12 +866,13 @@ class BatchHandle:
     def factor(self):
         """info[count]: per matrix 0, or the 1-based column of its first exactly zero pivot"""
         info = np.zeros(self.count, dtype=np.int32)
-        _lib.check(_lib.entry("sluamd_dBatchFactor")(self._b, _pi(info)), "sluamd_dBatchFactor")
+        _lib.check(_lib.entry(self._fn("Factor"))(self._b, _pi(info)), self._fn("Factor"))
         return info
 
     def solve(self, b, trans="N", refine=False):
-        """b: [count, n] or [count, n, nrhs] -> (x of the same shape, berr [count, nrhs] or None, steps [count])"""
-        b = np.asarray(b, dtype=np.float64)
+        """b: [count, n] or [count, n, nrhs] -> (x of the same shape, berr [count, nrhs] or None, steps [count]); trans = "T" / "C": A_k^T x = b / A_k^H x = b
+        (the same system on a double batch), refined against the transposed system when refine is set"""
+        b = np.asarray(b, dtype=self._dt)
         one = b.ndim == 2
         b3 = b[:, :, None] if one else b
         if b3.ndim != 3 or b3.shape[0] != self.count or b3.shape[1] != self.n:
@@ -873,9 +882,9 @@ class BatchHandle:
         X = np.zeros_like(B)
         berr = np.zeros((self.count, max(nrhs, 1)))
         steps = np.zeros(self.count, dtype=np.int32)
-        _lib.check(_lib.entry("sluamd_dBatchSolve")(self._b, _trans_code(trans), B.ctypes.data_as(C.c_void_p), self.n, self.n * nrhs,
-                                                    X.ctypes.data_as(C.c_void_p), self.n, self.n * nrhs, nrhs, int(bool(refine)), _pd(berr), _pi(steps)),
-                   "sluamd_dBatchSolve")
+        _lib.check(_lib.entry(self._fn("Solve"))(self._b, _trans_code(trans), B.ctypes.data_as(C.c_void_p), self.n, self.n * nrhs,
+                                                 X.ctypes.data_as(C.c_void_p), self.n, self.n * nrhs, nrhs, int(bool(refine)), _pd(berr), _pi(steps)),
+                   self._fn("Solve"))
         x = X.transpose(0, 2, 1)
         return (np.ascontiguousarray(x[:, :, 0]) if one else np.ascontiguousarray(x)), (berr[:, :nrhs] if refine else None), steps
 
@@ -901,16 +910,33 @@ class BatchHandle:
             pass
 
 
+class ZBatchHandle(BatchHandle):
+    """the complex16 batch (sluamd_zBatch*): the interface of BatchHandle with complex128 values, b and x; device value updates take a contiguous complex128
+    device tensor; trans = "T" and "C" differ; R, C and berr stay real"""
+    _p, _dt = "z", np.complex128
+
+
 def pdgssvx3d_batch(n, rowptr, colind, nzvals, b, perm_c=None, relax=32, maxsup=256, equil=False, refine=False, trans="N", deterministic=False,
                     keep=False):
     """The batched expert driver on one rank: `count` systems of one pattern, nzvals [count, nnz], b [count, n] or [count, n, nrhs].  One symbolic
     factorisation (and, when perm_c is None, one nested-dissection ordering) of ONE matrix serves the batch.  Returns (x, info[count], stats); stats carries
     the per-matrix berr [count, nrhs] and refine_steps [count] when refine is set, and the BatchHandle under "handle" with keep=True.
-    equil: every matrix is equilibrated on its own; stats then holds equed [count] ("N" / "R" / "C" / "B"), rowcnd, colcnd, amax, anorm, equil_info [count]."""
+    equil: every matrix is equilibrated on its own; stats then holds equed [count] ("N" / "R" / "C" / "B"), rowcnd, colcnd, amax, anorm, equil_info [count].
+    trans = "T" / "C": the transposed / conjugate-transposed systems, refined as such when refine is set.  pzgssvx3d_batch: the same for complex128 values."""
+    return _gssvx3d_batch(BatchHandle, n, rowptr, colind, nzvals, b, perm_c, relax, maxsup, equil, refine, trans, deterministic, keep)
+
+
+def pzgssvx3d_batch(n, rowptr, colind, nzvals, b, perm_c=None, relax=32, maxsup=256, equil=False, refine=False, trans="N", deterministic=False,
+                    keep=False):
+    """pdgssvx3d_batch on complex16 systems (ZBatchHandle): nzvals, b and x complex128, berr real"""
+    return _gssvx3d_batch(ZBatchHandle, n, rowptr, colind, nzvals, b, perm_c, relax, maxsup, equil, refine, trans, deterministic, keep)
+
+
+def _gssvx3d_batch(cls, n, rowptr, colind, nzvals, b, perm_c, relax, maxsup, equil, refine, trans, deterministic, keep):
     if perm_c is None:
         perm_c = order_nd(n, rowptr, colind)
     symb = Symbolic(n, rowptr, colind, perm_c, relax=relax, maxsup=min(int(maxsup), 256))
-    bh = BatchHandle.create(symb, nzvals, deterministic=deterministic)
+    bh = cls.create(symb, nzvals, deterministic=deterministic)
     symb.free()
     try:
         eq = bh.equilibrate() if equil else None
