@@ -405,47 +405,20 @@ int sluamd_zCopyLU2Host(sluamd_handle_t h, const sluamd_zLUview_t *lu)
     return sluamd_dCopyLU2Host(h, reinterpret_cast<const sluamd_dLUview_t *>(lu));
 }
 
-// x: n x nrhs doublecomplex, column-major, host memory; overwritten by the solution of L U y = x
-int sluamd_pzgstrs3d(sluamd_handle_t h, sluamd_doublecomplex *x, int64_t ldx, int32_t nrhs)
+// The untransposed solves L U y = x in place in x (n x nrhs values of the handle's precision, column-major; host: staged through the handle's own vector).
+// The same driver for both precisions: level sweeps per Z level, Z exchanges / gather on grids (complex16: x seen as 2 n doubles there).  Their transposed
+// twins and the device form of the complex16 one: sluamd_tsolve.cpp
+static int solve_plain(sluamd_handle_t h, void *x, int64_t ldx, int32_t nrhs, bool z, bool host, const char *name)
 {
-    if (!h || !h->H.z || !x || nrhs < 0 || ldx < h->H.hs.n) { set_error("bad complex solve arguments"); return SLUAMD_EINVAL; }
-    if (nrhs == 0) return 0;
+    const int c = check_solve_args(h, SLUAMD_NOTRANS, x, ldx, x, ldx, nrhs, nullptr, false, z, name);
+    if (c) return c < 0 ? c : 0;
     Handle *H = &h->H;
-    HIPCHK(hipSetDevice(H->device));
-    const int64_t need = 2 * ldx * nrhs;   // in doubles
-    if (int rc = H->d_x.reserve(need, H->device, "the right-hand sides")) return rc;
-    HIPCHK(hipMemcpy(H->d_x.p, x, sizeof(double) * need, hipMemcpyHostToDevice));
-    hipStream_t s = H->stream;
-    HIPCHK(hipEventRecord(H->ev0, s));
-    {   // the same driver as the double path: level sweeps per Z level, Z exchanges / gather on grids (x seen as 2 n doubles there)
-        const int rc = run_solve_dev(H, H->d_x.p, ldx, nrhs);
-        if (rc) return rc;
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(H->ev1, s));
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev0, H->ev1));
-    H->st.t_solve_ms = ms;
-    HIPCHK(hipMemcpy(x, H->d_x.p, sizeof(double) * need, hipMemcpyDeviceToHost));
-    return 0;
+    return framed_solve(H, static_cast<double *>(x), ldx, nrhs, host, [&](double *d_x) { return run_solve_dev(H, d_x, ldx, nrhs); });
 }
 
-int sluamd_pdgstrs3d_dev(sluamd_handle_t h, double *d_x, int64_t ldx, int32_t nrhs)
-{
-    if (!h || !d_x || nrhs < 0 || ldx < h->H.hs.n) { set_error("bad solve arguments"); return SLUAMD_EINVAL; }
-    if (h->H.z) { set_error("complex16 handle: call sluamd_pzgstrs3d"); return SLUAMD_EINVAL; }
-    if (nrhs == 0) return 0;
-    Handle *H = &h->H;
-    HIPCHK(hipSetDevice(H->device));
-    HIPCHK(hipEventRecord(H->ev0, H->stream));
-    int rc = run_solve_dev(H, d_x, ldx, nrhs);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(H->ev1, H->stream));
-    HIPCHK(hipStreamSynchronize(H->stream));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev0, H->ev1));
-    H->st.t_solve_ms = ms;
-    return 0;
-}
+int sluamd_pzgstrs3d(sluamd_handle_t h, sluamd_doublecomplex *x, int64_t ldx, int32_t nrhs) { return solve_plain(h, x, ldx, nrhs, true, true, "sluamd_pzgstrs3d"); }
+
+int sluamd_pdgstrs3d_dev(sluamd_handle_t h, double *d_x, int64_t ldx, int32_t nrhs) { return solve_plain(h, d_x, ldx, nrhs, false, false, "sluamd_pdgstrs3d_dev"); }
 
 // B: host, this rank's m_loc rows (vs doubles per value), leading dimension ldb in values
 static int solve_dist_host(sluamd_handle_t h, double *B, int64_t ldb, int32_t nrhs, int64_t m_loc, int64_t fst_row, const sluamd_int_t *perm_in,
@@ -461,13 +434,7 @@ static int solve_dist_host(sluamd_handle_t h, double *B, int64_t ldb, int32_t nr
     const int64_t need = ldd * nrhs * vs;
     if (int rc = H->d_bloc.reserve(need, H->device, "the local rows of B")) return rc;
     for (int q = 0; q < nrhs && m_loc; ++q) HIPCHK(hipMemcpy(H->d_bloc.p + (size_t) q * ldd * vs, B + (size_t) q * ldb * vs, sizeof(double) * (size_t) m_loc * vs, hipMemcpyHostToDevice));
-    HIPCHK(hipEventRecord(H->ev0, H->stream));
-    int rc = run_solve_dist(H, H->d_bloc.p, ldd, nrhs, m_loc, fst_row, perm_in, perm_out);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(H->ev1, H->stream));
-    HIPCHK(hipStreamSynchronize(H->stream));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev0, H->ev1));
-    H->st.t_solve_ms = ms;
+    if (int rc = timed_scope(H, H->st.t_solve_ms, [&] { return run_solve_dist(H, H->d_bloc.p, ldd, nrhs, m_loc, fst_row, perm_in, perm_out); })) return rc;
     for (int q = 0; q < nrhs && m_loc; ++q) HIPCHK(hipMemcpy(B + (size_t) q * ldb * vs, H->d_bloc.p + (size_t) q * ldd * vs, sizeof(double) * (size_t) m_loc * vs, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -484,20 +451,7 @@ int sluamd_pzgstrs3d_dist(sluamd_handle_t h, sluamd_doublecomplex *B, int64_t ld
     return solve_dist_host(h, reinterpret_cast<double *>(B), ldb, nrhs, m_loc, fst_row, perm_in, perm_out, true);
 }
 
-int sluamd_pdgstrs3d(sluamd_handle_t h, double *x, int64_t ldx, int32_t nrhs)
-{
-    if (!h || !x || nrhs < 0 || ldx < h->H.hs.n) { set_error("bad solve arguments"); return SLUAMD_EINVAL; }
-    if (nrhs == 0) return 0;
-    Handle *H = &h->H;
-    HIPCHK(hipSetDevice(H->device));
-    const int64_t need = ldx * nrhs;
-    if (int rc = H->d_x.reserve(need, H->device, "the right-hand sides")) return rc;
-    HIPCHK(hipMemcpy(H->d_x.p, x, sizeof(double) * need, hipMemcpyHostToDevice));
-    int rc = sluamd_pdgstrs3d_dev(h, H->d_x.p, ldx, nrhs);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(x, H->d_x.p, sizeof(double) * need, hipMemcpyDeviceToHost));
-    return 0;
-}
+int sluamd_pdgstrs3d(sluamd_handle_t h, double *x, int64_t ldx, int32_t nrhs) { return solve_plain(h, x, ldx, nrhs, false, true, "sluamd_pdgstrs3d"); }
 
 }  // extern "C"
 
@@ -558,7 +512,7 @@ extern "C" int sluamd_dAttachMatrix(sluamd_handle_t h, sluamd_int_t n, const slu
 namespace {
 struct DRfs {   // the double kernels of the refinement driver (sluamd_refine.h)
     static constexpr bool z = false;
-    static constexpr const char *attach = "sluamd_dAttachMatrix", *other = "sluamd_pzgsrfs3d";
+    static constexpr const char *attach = "sluamd_dAttachMatrix";
     static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
     {
         eng::rfs_residual(s, (int) H->hs.n, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
@@ -572,12 +526,12 @@ extern "C" {
 
 int sluamd_pdgsrfs3d_dev(sluamd_handle_t h, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    return rfs_dev<DRfs>(h, d_B, ldb, d_X, ldx, nrhs, berr, steps);
+    return rfs_entry<DRfs>(h, d_B, ldb, d_X, ldx, nrhs, berr, steps, false, "sluamd_pdgsrfs3d_dev");
 }
 
 int sluamd_pdgsrfs3d(sluamd_handle_t h, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    return rfs_host<DRfs>(h, B, ldb, X, ldx, nrhs, berr, steps);
+    return rfs_entry<DRfs>(h, B, ldb, X, ldx, nrhs, berr, steps, true, "sluamd_pdgsrfs3d");
 }
 
 void sluamd_dDestroyLUHandle(sluamd_handle_t h)

@@ -114,20 +114,17 @@ int equilibrate(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, c
     return 0;
 }
 
-// the checks every entry point shares; 1: nothing to do (nrhs == 0)
+// the shared checks of the solves (check_solve_args), then what this call adds; 1: nothing to do (nrhs == 0)
 int check_solve(sluamd_handle_t h, int trans, const void *B, int64_t ldb, const void *X, int64_t ldx, int32_t nrhs, int refine, const double *berr,
                 int32_t *steps, bool z, const char *name)
 {
+    const int c = check_solve_args(h, trans, B, ldb, X, ldx, nrhs, berr, refine != 0, z, name);
+    if (c < 0) return c;
     const std::string me = std::string(name) + ": ";
-    if (!h || !B || !X || nrhs < 0 || ldb < h->H.hs.n || ldx < h->H.hs.n || (refine && !berr)) { set_error(me + "bad solve arguments"); return SLUAMD_EINVAL; }
-    if (trans != SLUAMD_NOTRANS && trans != SLUAMD_TRANS && trans != SLUAMD_CONJ) { set_error(me + "trans must be SLUAMD_NOTRANS, SLUAMD_TRANS or SLUAMD_CONJ"); return SLUAMD_EINVAL; }
-    const Handle *H = &h->H;
-    if (H->z != z) { set_error(me + (z ? "double handle: call sluamd_pdgssvx3d_solve" : "complex16 handle: call sluamd_pzgssvx3d_solve")); return SLUAMD_EINVAL; }
-    if (!H->d_rfs_pc.p || H->rfs_z != z) { set_error(me + "no matrix attached (perm_c): call sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix first"); return SLUAMD_EINVAL; }
+    if (!h->H.d_rfs_pc.p) { set_error(me + "no matrix attached (perm_c): call sluamd_[dz]Equilibrate or sluamd_[dz]AttachMatrix first"); return SLUAMD_EINVAL; }
     if (refine && trans != SLUAMD_NOTRANS) { set_error(me + "refine with a transposed system is not part of this call: solve with refine = 0, then refine the attached (scaled) system with sluamd_p[dz]gsrfs3d_trans"); return SLUAMD_EINVAL; }
-    if (trans != SLUAMD_NOTRANS && H->grid.size() > 1 && !H->xt_ready) { set_error(me + "transposed solves need a 1 x 1 x 1 handle, or a grid handle after sluamd_PlanTransposedSweeps"); return SLUAMD_EINVAL; }
     if (steps) *steps = 0;
-    return nrhs == 0 ? 1 : 0;
+    return c;
 }
 
 // d_B, d_X: device, original ordering and scaling; xp: n x nrhs values of work space (ld n)

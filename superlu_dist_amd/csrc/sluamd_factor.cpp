@@ -4,7 +4,7 @@
 #include <algorithm>
 #include <cstring>
 #include "sluamd_comm.h"
-#include "sluamd_plan.h"
+#include "sluamd_sweep.h"
 
 namespace sluamd {
 
@@ -481,28 +481,24 @@ int run_factor(Handle *H, double thresh, int *info)
     H->schur_rec.clear();
     H->ev_pool_used = 0;
     H->red_pool_used = 0; H->red_events.clear();
-    HIPCHK(hipEventRecord(H->ev0, H->stream));
     // Z levels in order (pdgstrf3d.c:333-385): factor my forest of the level, then the ancestor reduction
-    int rc = 0;
-    for (size_t zl = 0; zl < H->sched.size(); ++zl) {
-        if (H->z_active[zl]) {
-            rc = run_factor_sched(H, H->sched[zl], thresh);     // double and complex16 alike: the look-ahead schedule is type-independent
-            if (rc) return rc;
+    int rc = timed_scope(H, H->st.t_factor_ms, [&]() -> int {
+        for (size_t zl = 0; zl < H->sched.size(); ++zl) {
+            if (H->z_active[zl])
+                if (int e = run_factor_sched(H, H->sched[zl], thresh)) return e;     // double and complex16 alike: the look-ahead schedule is type-independent
+            if (g.Pz > 1) {
+                ev_begin(H, H->ev_red, H->ev_red_used, H->stream);
+                const int e = reduce_ancestors(H, (int) zl);
+                ev_end(H, H->ev_red, H->ev_red_used, H->stream);
+                if (e) return e;
+            }
         }
-        if (g.Pz > 1) {
-            ev_begin(H, H->ev_red, H->ev_red_used, H->stream);
-            rc = reduce_ancestors(H, (int) zl);
-            ev_end(H, H->ev_red, H->ev_red_used, H->stream);
-            if (rc) return rc;
-        }
-    }
-    if (H->red_all) { HIPCHK(hipStreamWaitEvent(H->stream, H->red_all, 0)); H->red_events.clear(); }   // the last reduction's additions belong to the factorisation
-    HIPCHK(hipEventRecord(H->ev1, H->stream));
+        if (H->red_all) { HIPCHK(hipStreamWaitEvent(H->stream, H->red_all, 0)); H->red_events.clear(); }   // the last reduction's additions belong to the factorisation
+        return 0;
+    });
+    if (rc) return rc;
     int res[8];
-    HIPCHK(hipMemcpyAsync(res, H->d_info.p, sizeof(res), hipMemcpyDeviceToHost, H->stream));
-    HIPCHK(hipStreamSynchronize(H->stream));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev0, H->ev1));
-    H->st.t_factor_ms = ms;
+    HIPCHK(hipMemcpy(res, H->d_info.p, sizeof(res), hipMemcpyDeviceToHost));
     H->dinv_ready = true; H->inv_ready = !H->env.trsm_panels && !H->z; H->factored = true;
     if (H->profile && H->env.profile_dump && H->schur_rec.size() == H->ev_schur_used)
         for (size_t i = 0; i < H->ev_schur_used; ++i) {
@@ -818,10 +814,25 @@ static inline bool groups_fit(const Handle *H, int nrhs)
     for (const Handle::SolveGroup &G : H->groups) w = std::max(w, G.nG);
     return (size_t) w * nrhs * sizeof(double) <= 48 * 1024;
 }
+
+// The plain in-place sweeps (sluamd_sweep.h) of XY layers, of complex16 handles and of profiled double handles: the level kernels of the two precisions.
+// (d_x of a complex16 handle holds doublecomplex, ldx in complex values.)
+static void d_level_diag(hipStream_t s, bool fwd, const DevTables &T, const int *nodes, int nn, double *x, int64_t ldx, int nr, int mx, void *) { eng::solve_diag(s, fwd, T, nodes, nn, x, ldx, nr, mx); }
+static void d_level_update(hipStream_t s, bool fwd, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, double *x, int64_t ldx, int nr, int mx, void *)
+{
+    if (fwd) eng::fwd_update(s, T, nodes, prefix, nn, nwork, x, x, ldx, nr, mx);
+    else eng::bwd_update(s, T, nodes, prefix, nn, nwork, x, x, ldx, nr, mx);
+}
+static void z_level_diag(hipStream_t s, bool fwd, const DevTables &T, const int *nodes, int nn, double *x, int64_t ldx, int nr, int mx, void *) { eng::zsolve_diag(s, fwd, T, nodes, nn, x, ldx, nr, mx); }
+static void z_level_update(hipStream_t s, bool fwd, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, double *x, int64_t ldx, int nr, int mx, void *)
+{
+    if (fwd) eng::zfwd_update(s, T, nodes, prefix, nn, nwork, x, ldx, nr, mx);
+    else eng::zbwd_update(s, T, nodes, prefix, nn, nwork, x, ldx, nr);
+}
+static const LevelKernels plain_d = {d_level_diag, d_level_update, UNITS_FWD, UNITS_BWD, false}, plain_z = {z_level_diag, z_level_update, UNITS_ZFWD, UNITS_BWD, false};
+
 static int solve_fwd_z(Handle *H, int z, double *d_x, int64_t ldx, int nrhs)
 {
-    const DevTables &T = H->T;
-    hipStream_t s = H->stream;
     LevelSched &S = H->sched[z];
     const bool xy = H->grid.Pr * H->grid.Pc > 1;
     if (!xy && !H->z && !H->profile) {
@@ -831,27 +842,11 @@ static int solve_fwd_z(Handle *H, int z, double *d_x, int64_t ldx, int nrhs)
         if (!rc && S.join) return solve_fwd_join(H, S, d_x, ldx, nrhs);
         return rc ? rc : solve_fwd_links(H, S, d_x, ldx, nrhs);
     }
-    for (int l = 0; l < S.nlevels; ++l) {
-        const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
-        int rc;
-        if (H->z) {   // complex16: d_x holds doublecomplex, ldx in complex values; the exchanges see 2 ldx doubles (run lists in doubles)
-            if (xy && (rc = xseg_exchange(H, d_x, 2 * ldx, nrhs, S.xs_red_send[l], 3, S.xs_red_recv[l], 2, s))) return rc;
-            eng::zsolve_diag(s, true, T, S.d_nodes + n0, nn, d_x, ldx, nrhs, S.max_nsupc[l]);
-            if (xy && (rc = xseg_exchange(H, d_x, 2 * ldx, nrhs, S.xs_bc_send[l], 0, S.xs_bc_recv[l], 1, s))) return rc;
-            eng::zfwd_update(s, T, S.d_nodes + n0, S.d_zfwd_prefix + po, nn, S.zfwd_prefix[po + nn], d_x, ldx, nrhs, S.max_nsupc[l]);
-            continue;
-        }
-        if (xy && (rc = xseg_exchange(H, d_x, ldx, nrhs, S.xs_red_send[l], 3, S.xs_red_recv[l], 2, s))) return rc;
-        eng::solve_diag(s, true, T, S.d_nodes + n0, nn, d_x, ldx, nrhs, S.max_nsupc[l]);
-        if (xy && (rc = xseg_exchange(H, d_x, ldx, nrhs, S.xs_bc_send[l], 0, S.xs_bc_recv[l], 1, s))) return rc;
-        eng::fwd_update(s, T, S.d_nodes + n0, S.d_fwd_prefix + po, nn, S.fwd_prefix[po + nn], d_x, d_x, ldx, nrhs, S.max_nsupc[l]);
-    }
-    return 0;
+    const int n = sweep_forest(H, S, true, d_x, ldx, nrhs, H->z ? plain_z : plain_d);      // (counts no launches: Handle::st)
+    return n < 0 ? n : 0;
 }
 static int solve_bwd_z(Handle *H, int z, double *d_x, int64_t ldx, int nrhs)
 {
-    const DevTables &T = H->T;
-    hipStream_t s = H->stream;
     LevelSched &S = H->sched[z];
     const bool xy = H->grid.Pr * H->grid.Pc > 1;
     if (!xy && !H->z && !H->profile) {
@@ -861,22 +856,8 @@ static int solve_bwd_z(Handle *H, int z, double *d_x, int64_t ldx, int nrhs)
         if (!rc && S.join) return solve_bwd_join(H, S, d_x, ldx, nrhs);
         return rc ? rc : solve_bwd_links(H, S, d_x, ldx, nrhs);
     }
-    for (int l = S.nlevels - 1; l >= 0; --l) {
-        const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
-        int rc;
-        if (H->z) {
-            eng::zbwd_update(s, T, S.d_nodes + n0, S.d_bwd_prefix + po, nn, S.bwd_prefix[po + nn], d_x, ldx, nrhs);
-            if (xy && (rc = xseg_exchange(H, d_x, 2 * ldx, nrhs, S.xs_red_send[l], 3, S.xs_red_recv[l], 2, s))) return rc;
-            eng::zsolve_diag(s, false, T, S.d_nodes + n0, nn, d_x, ldx, nrhs, S.max_nsupc[l]);
-            if (xy && (rc = xseg_exchange(H, d_x, 2 * ldx, nrhs, S.xs_bc_send[l], 0, S.xs_bc_recv[l], 1, s))) return rc;
-            continue;
-        }
-        eng::bwd_update(s, T, S.d_nodes + n0, S.d_bwd_prefix + po, nn, S.bwd_prefix[po + nn], d_x, d_x, ldx, nrhs, S.max_nsupc[l]);
-        if (xy && (rc = xseg_exchange(H, d_x, ldx, nrhs, S.xs_red_send[l], 3, S.xs_red_recv[l], 2, s))) return rc;
-        eng::solve_diag(s, false, T, S.d_nodes + n0, nn, d_x, ldx, nrhs, S.max_nsupc[l]);
-        if (xy && (rc = xseg_exchange(H, d_x, ldx, nrhs, S.xs_bc_send[l], 0, S.xs_bc_recv[l], 1, s))) return rc;
-    }
-    return 0;
+    const int n = sweep_forest(H, S, false, d_x, ldx, nrhs, H->z ? plain_z : plain_d);
+    return n < 0 ? n : 0;
 }
 
 int max_rhs_chunk(const Handle *H)
@@ -904,11 +885,7 @@ static int zsolve_fused(Handle *H, double *x, int64_t ldx, int nr)
             if (fused(S, l)) {
                 eng::zsweep_fused(s, true, T, S.d_nodes + n0, S.d_zffu_prefix + po, nn, S.zffu_prefix[po + nn], x, H->d_w.p, ldx, nr, S.max_nsupc[l], nullptr);
                 H->st.solve_launches += 1;
-            } else {
-                eng::zsolve_diag(s, true, T, S.d_nodes + n0, nn, x, ldx, nr, S.max_nsupc[l]);
-                eng::zfwd_update(s, T, S.d_nodes + n0, S.d_zfwd_prefix + po, nn, S.zfwd_prefix[po + nn], x, ldx, nr, S.max_nsupc[l]);
-                H->st.solve_launches += 2;
-            }
+            } else H->st.solve_launches += sweep_level(H, S, l, true, x, ldx, nr, plain_z);      // (one rank: no exchange, no error)
         }
     for (int z = (int) H->sched.size() - 1; z >= 0; --z) {
         LevelSched &S = H->sched[z];
@@ -917,11 +894,7 @@ static int zsolve_fused(Handle *H, double *x, int64_t ldx, int nr)
             if (fused(S, l)) {
                 eng::zsweep_fused(s, false, T, S.d_nodes + n0, S.d_zbfu_prefix + po, nn, S.zbfu_prefix[po + nn], x, H->d_w.p, ldx, nr, S.max_nsupc[l], H->d_ztickets.p);
                 H->st.solve_launches += 1;
-            } else {
-                eng::zbwd_update(s, T, S.d_nodes + n0, S.d_bwd_prefix + po, nn, S.bwd_prefix[po + nn], x, ldx, nr);
-                eng::zsolve_diag(s, false, T, S.d_nodes + n0, nn, x, ldx, nr, S.max_nsupc[l]);
-                H->st.solve_launches += 2;
-            }
+            } else H->st.solve_launches += sweep_level(H, S, l, false, x, ldx, nr, plain_z);
         }
     }
     return 0;
@@ -1085,11 +1058,10 @@ static int allgather_solution(Handle *H, double *x, int64_t ldxd, int nr, hipStr
 // forward and backward sweeps of one right-hand-side chunk on the grid.  On entry x holds b at the rows this rank consumes (diagonal
 // owner on the factoring layer) and zeros elsewhere; on return x_k is final at those rows.  Z sweeps as pdgsTrForwardSolve3d /
 // pdgsTrBackSolve3d (pdgstrs3d.c:7312, :7564): forward reduction of the ancestor rows to the partner layer (dfsolveReduceLsum3d
-// :1646), backward hand-down of the solved ancestors (dp2pSolvedX3d :1596).  `ops` supplies the two per-forest bodies and the forest_runs roles of the
+// :1646), backward hand-down of the solved ancestors (dp2pSolvedX3d :1596).  `ops` supplies the per-forest body (either direction) and the forest_runs roles of the
 // rows that hold partial sums / solved entries (untransposed: process row / process column; the transposed sweeps of sluamd_tsolve.cpp: the other way round).
-static int fwd_z_op(Handle *H, int z, double *x, int64_t ldx, int nr, void *) { return solve_fwd_z(H, z, x, ldx, nr); }
-static int bwd_z_op(Handle *H, int z, double *x, int64_t ldx, int nr, void *) { return solve_bwd_z(H, z, x, ldx, nr); }
-static const GridSweepOps plain_ops = {fwd_z_op, bwd_z_op, nullptr, 0, 1};
+static int plain_z_op(Handle *H, int z, bool fwd, double *x, int64_t ldx, int nr, void *) { return fwd ? solve_fwd_z(H, z, x, ldx, nr) : solve_bwd_z(H, z, x, ldx, nr); }
+static const GridSweepOps plain_ops = {plain_z_op, nullptr, 0, 1};
 static int grid_sweeps(Handle *H, double *x, int64_t ldx, int nr, const GridSweepOps &ops = plain_ops)
 {
     const Grid &g = H->grid;
@@ -1102,7 +1074,7 @@ static int grid_sweeps(Handle *H, double *x, int64_t ldx, int nr, const GridSwee
     for (int zl = 0; zl < nzl; ++zl) {
         const int step = 1 << zl;
         if (g.z % step) break;
-        if (H->z_active[zl] && (rc = ops.fwd(H, zl, x, ldx, nr, ops.ctx))) return rc;
+        if (H->z_active[zl] && (rc = ops.sweep(H, zl, true, x, ldx, nr, ops.ctx))) return rc;
         if (zl + 1 < nzl) {
             const bool receiver = (g.z % (2 * step)) == 0;
             if (receiver && g.z + step >= g.Pz) continue;
@@ -1125,7 +1097,7 @@ static int grid_sweeps(Handle *H, double *x, int64_t ldx, int nr, const GridSwee
                 if (seg.total && (rc = sender ? xseg_exchange(H, x, ldxd, nr, one, 0, none, 0, s) : xseg_exchange(H, x, ldxd, nr, none, 0, one, 1, s))) return rc;
             }
         }
-        if (H->z_active[zl] && (rc = ops.bwd(H, zl, x, ldx, nr, ops.ctx))) return rc;
+        if (H->z_active[zl] && (rc = ops.sweep(H, zl, false, x, ldx, nr, ops.ctx))) return rc;
     }
     return 0;
 }

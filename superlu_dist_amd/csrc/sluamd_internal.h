@@ -398,6 +398,10 @@ struct Handle {
     std::vector<uint8_t> ev_schur_big;     // parallel to ev_schur: the launch ran the 128 x 128 tile configuration
     struct SchurRec { int level, pass, big, ntiles, mx; };
     std::vector<SchurRec> schur_rec;   // SLUAMD_PROFILE_DUMP: one record per profiled Schur launch (parallel to ev_schur)
+    // st.solve_launches: set to 0 by every solve driver, then added to by the schedules that count -- the joined, two-launch, serial and grouped links of a
+    // 1 x 1 x 1 double handle, the complex16 fused driver (its in-place levels included) and the transposed sweeps (two per level and sweep, on grids
+    // too).  The plain in-place sweeps of solve_fwd_z / solve_bwd_z (XY layers, complex16 beyond the fused driver, profiled handles) count nothing:
+    // sweep_forest (sluamd_sweep.h) returns its launches and the caller adds them or does not
     sluamd_stats_t st{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // host tables kept for stats / planning

@@ -98,10 +98,9 @@ int run_tsolve(Handle *H, bool conj, double *d_x, int64_t ldx, int nrhs);   // s
 // The replicated solve of a multi-rank handle around two per-forest sweeps (sluamd_factor.cpp; run_solve_dev and run_tsolve are its two callers): per chunk of
 // right-hand sides b is kept at the rows that consume it, fwd runs on the forests leaves to root with the ancestors' partial sums (forest_runs role acc_role:
 // 0 = rows of my process row, 1 = of my process column) added into the partner layer, bwd root to leaves after the solved ancestors (role x_role) came down,
-// then the all-gather.  The bodies get the chunk's vector (ldx in values of the handle's precision) and ctx.
+// then the all-gather.  The body (fwd / bwd = `sweep` with fwd true / false) gets the chunk's vector (ldx in values of the handle's precision) and ctx.
 struct GridSweepOps {
-    int (*fwd)(Handle *H, int z, double *x, int64_t ldx, int nr, void *ctx);
-    int (*bwd)(Handle *H, int z, double *x, int64_t ldx, int nr, void *ctx);
+    int (*sweep)(Handle *H, int z, bool fwd, double *x, int64_t ldx, int nr, void *ctx);
     void *ctx;
     int acc_role, x_role;
 };
@@ -109,6 +108,57 @@ int run_grid_solve(Handle *H, double *d_x, int64_t ldx, int nrhs, const GridSwee
 // exchange of x segments with a set of peers on stream s (run lists and ldx in doubles): pack_mode 0 = pack, 3 = pack and clear; unpack_mode 1 = overwrite, 2 = accumulate
 int xseg_exchange(Handle *H, double *d_x, int64_t ldx, int nrhs, const std::vector<LevelSched::XSeg> &snd, int pack_mode,
                   const std::vector<LevelSched::XSeg> &rcv, int unpack_mode, hipStream_t s);
+// The argument checks of the solve, refinement and expert-solve entry points, in this order: the handle, the blocks B and X (an in-place
+// call passes its one block as both), nrhs, the leading dimensions, berr where the call returns one (need_berr), trans, the precision z the call serves --
+// the message names the same call for the other one, `name` (sluamd_p[dz]g...) with its precision letter swapped -- and, for trans != SLUAMD_NOTRANS on more
+// than one rank, that the transposed sweeps are planned.  Every message starts with `name`; `what`: "solve" / "refinement".
+// < 0: refused, nothing was touched; 1: nothing to do (nrhs == 0); 0: go on
+static inline int check_solve_args(sluamd_handle_t h, int trans, const void *B, int64_t ldb, const void *X, int64_t ldx, int32_t nrhs, const double *berr, bool need_berr,
+                                   bool z, const char *name, const char *what = "solve")
+{
+    const std::string me = std::string(name) + ": ";
+    if (!h || !B || !X || nrhs < 0 || ldb < h->H.hs.n || ldx < h->H.hs.n || (need_berr && !berr)) { set_error(me + "bad " + what + " arguments"); return SLUAMD_EINVAL; }
+    if (trans != SLUAMD_NOTRANS && trans != SLUAMD_TRANS && trans != SLUAMD_CONJ) { set_error(me + "trans must be SLUAMD_NOTRANS, SLUAMD_TRANS or SLUAMD_CONJ"); return SLUAMD_EINVAL; }
+    const Handle *H = &h->H;
+    if (H->z != z) {
+        std::string twin(name);
+        twin[8] = z ? 'd' : 'z';
+        set_error(me + (z ? "double" : "complex16") + " handle: call " + twin);
+        return SLUAMD_EINVAL;
+    }
+    if (trans != SLUAMD_NOTRANS && H->grid.size() > 1 && !H->xt_ready) { set_error(me + "a transposed " + what + " needs a 1 x 1 x 1 handle, or a grid handle after sluamd_PlanTransposedSweeps (the transposed sweeps of a grid need exchange plans of their own)"); return SLUAMD_EINVAL; }
+    return nrhs == 0 ? 1 : 0;
+}
+// Timed scope on the handle's stream: ev0, `run()` (0 or an error code), the launch check, ev1, synchronise; `out` = the milliseconds between the events
+template <class F> int timed_scope(Handle *H, double &out, F &&run)
+{
+    HIPCHK(hipSetDevice(H->device));
+    HIPCHK(hipEventRecord(H->ev0, H->stream));
+    if (int rc = run()) return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(H->ev1, H->stream));
+    HIPCHK(hipStreamSynchronize(H->stream));
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, H->ev0, H->ev1));
+    out = ms;
+    return 0;
+}
+// Staged scope of the host-pointer solves: the caller's ldx x nrhs block of values goes through Handle::d_x, `run(d_x)` works on the copy
+template <class F> int staged_scope(Handle *H, double *x, int64_t ldx, int nrhs, F &&run)
+{
+    HIPCHK(hipSetDevice(H->device));
+    const int64_t need = ldx * nrhs * (H->z ? 2 : 1);   // in doubles
+    if (int rc = H->d_x.reserve(need, H->device, "the right-hand sides")) return rc;
+    HIPCHK(hipMemcpy(H->d_x.p, x, sizeof(double) * need, hipMemcpyHostToDevice));
+    if (int rc = run(H->d_x.p)) return rc;
+    HIPCHK(hipMemcpy(x, H->d_x.p, sizeof(double) * need, hipMemcpyDeviceToHost));
+    return 0;
+}
+// An in-place solve of nrhs right-hand sides, x on the host (staged) or on the device: `run(d_x)` queues it, stats.t_solve_ms times it
+template <class F> int framed_solve(Handle *H, double *x, int64_t ldx, int nrhs, bool host, F &&run)
+{
+    auto timed = [&](double *d_x) { return timed_scope(H, H->st.t_solve_ms, [&] { return run(d_x); }); };
+    return host ? staged_scope(H, x, ldx, nrhs, timed) : timed(x);
+}
 int run_solve_local(Handle *H, double *d_x, int64_t ldx, int nrhs);   // single-rank sweep over every schedule (refinement)
 int ensure_dinv(Handle *H);
 int ensure_inv(Handle *H);

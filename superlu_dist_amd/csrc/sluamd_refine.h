@@ -3,7 +3,7 @@
 // resident work vectors and the collective continue / stop decision on grids live here; a precision supplies its two kernels as
 // a policy K:
 //   K::z                 complex16 (values, x, b, r_perm of two doubles)
-//   K::attach, K::other  names for the error messages: this precision's attach call, the other precision's refinement call
+//   K::attach            name for the error messages: this precision's attach call
 //   K::residual(s, H, x, b, r_perm, safe1, safe2)   r_perm = Pc (b - A x), *H->d_rfs_s.p = max(*H->d_rfs_s.p, berr bits)
 //   K::update(s, H, dx_perm, x)                     x += Pc^T dx_perm
 //   K::solve(H, r_perm, n)                          the correction, in place in r_perm: run_solve_dev for A x = b; the transposed policies run the
@@ -25,11 +25,11 @@ int attach_rfs(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, co
 // the transposed index of the attached matrix (Handle::d_rfs_tcp / d_rfs_tri / d_rfs_tpos), built on first use: sluamd_trefine.cpp, which describes it
 int ensure_tindex(Handle *H, const char *who);
 
+// what the driver needs beyond the arguments its entry points check (check_solve_args, sluamd_plan.h: handle, blocks, nrhs, leading dimensions, berr, trans,
+// precision, planned transposed sweeps): a matrix attached to the handle -- always of the handle's precision, attach_rfs refuses any other
 template <class K> int rfs_checks(const Handle *H)
 {
-    if (H->z != K::z) { set_error(std::string(H->z ? "complex16" : "double") + " handle: call " + K::other); return SLUAMD_EINVAL; }
     if (!H->d_rfs_rp.p) { set_error(std::string("no matrix attached: call ") + K::attach + " first"); return SLUAMD_EINVAL; }
-    if (H->rfs_z != K::z) { set_error(std::string("the attached matrix is ") + (H->rfs_z ? "complex16" : "double") + ": call " + K::other); return SLUAMD_EINVAL; }
     return 0;
 }
 
@@ -37,7 +37,6 @@ template <class K> int rfs_checks(const Handle *H)
 // On a grid handle (replicated form, like sluamd_pdgstrs3d) every rank passes the complete B and X and the call is collective.
 template <class K> int rfs_dev(sluamd_handle_t h, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    if (!h || !d_B || !d_X || !berr || nrhs < 0 || ldb < h->H.hs.n || ldx < h->H.hs.n) { set_error("bad refinement arguments"); return SLUAMD_EINVAL; }
     Handle *H = &h->H;
     if (int rc = rfs_checks<K>(H)) return rc;
     const bool grid = H->grid.size() > 1;
@@ -83,7 +82,6 @@ template <class K> int rfs_dev(sluamd_handle_t h, const double *d_B, int64_t ldb
 // B, X: host memory, column-major; one column at a time through the two resident work vectors (r_perm | b | x)
 template <class K> int rfs_host(sluamd_handle_t h, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    if (!h || !B || !X || !berr || nrhs < 0 || ldb < h->H.hs.n || ldx < h->H.hs.n) { set_error("bad refinement arguments"); return SLUAMD_EINVAL; }
     if (nrhs == 0) { if (steps) *steps = 0; return 0; }
     Handle *H = &h->H;
     if (int rc = rfs_checks<K>(H)) return rc;
@@ -101,6 +99,16 @@ template <class K> int rfs_host(sluamd_handle_t h, const double *B, int64_t ldb,
     }
     if (steps) *steps = last;
     return 0;
+}
+
+// An untransposed refinement entry point of the precision of K: the shared argument checks, then the driver on host or device blocks
+template <class K> int rfs_entry(sluamd_handle_t h, const void *B, int64_t ldb, void *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps, bool host, const char *name)
+{
+    const int c = check_solve_args(h, SLUAMD_NOTRANS, B, ldb, X, ldx, nrhs, berr, true, K::z, name, "refinement");
+    if (c < 0) return c;
+    const double *b = static_cast<const double *>(B);
+    double *x = static_cast<double *>(X);
+    return host ? rfs_host<K>(h, b, ldb, x, ldx, nrhs, berr, steps) : rfs_dev<K>(h, b, ldb, x, ldx, nrhs, berr, steps);
 }
 
 }  // namespace sluamd

@@ -59,7 +59,7 @@ namespace {
 
 template <bool Z, bool CONJ> struct TRfs {
     static constexpr bool z = Z;
-    static constexpr const char *attach = Z ? "sluamd_zAttachMatrix" : "sluamd_dAttachMatrix", *other = Z ? "sluamd_pdgsrfs3d_trans" : "sluamd_pzgsrfs3d_trans";
+    static constexpr const char *attach = Z ? "sluamd_zAttachMatrix" : "sluamd_dAttachMatrix";
     static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
     {
         if (Z) eng::zrfs_residual_t(s, CONJ, (int) H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
@@ -73,26 +73,25 @@ template <bool Z, bool CONJ> struct TRfs {
     static int solve(Handle *H, double *r_perm, int n) { return run_tsolve(H, Z && CONJ, r_perm, n, 1); }
 };
 
-// trans != SLUAMD_NOTRANS.  The checks in the order of the transposed solves, then the index, then the shared driver
-template <bool Z> int trefine(sluamd_handle_t h, int trans, bool dev, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps,
-                              const char *name)
+// One entry for the four calls below.  trans == SLUAMD_NOTRANS: the untransposed call of the precision.  Else the checks in the order of the transposed
+// solves, then the index, then the shared driver.  B, X: n x nrhs values of precision z, on the host or on the device
+int refine_entry(sluamd_handle_t h, int trans, const void *Bv, int64_t ldb, void *Xv, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps, bool z, bool host, const char *name)
 {
+    const int c = check_solve_args(h, trans, Bv, ldb, Xv, ldx, nrhs, berr, true, z, name, "refinement");
+    if (c < 0) return c;
+    const double *B = static_cast<const double *>(Bv);
+    double *X = static_cast<double *>(Xv);
+    if (trans == SLUAMD_NOTRANS) {
+        auto zB = static_cast<const sluamd_doublecomplex *>(Bv); auto zX = static_cast<sluamd_doublecomplex *>(Xv);
+        if (z) return host ? sluamd_pzgsrfs3d(h, zB, ldb, zX, ldx, nrhs, berr, steps) : sluamd_pzgsrfs3d_dev(h, zB, ldb, zX, ldx, nrhs, berr, steps);
+        return host ? sluamd_pdgsrfs3d(h, B, ldb, X, ldx, nrhs, berr, steps) : sluamd_pdgsrfs3d_dev(h, B, ldb, X, ldx, nrhs, berr, steps);
+    }
     Handle *H = &h->H;
-    if (int rc = rfs_checks<TRfs<Z, false>>(H)) return rc;
-    if (H->grid.size() > 1 && !H->xt_ready) { set_error(std::string(name) + ": transposed refinement needs a 1 x 1 x 1 handle, or a grid handle after sluamd_PlanTransposedSweeps (the transposed sweeps of a grid need exchange plans of their own)"); return SLUAMD_EINVAL; }
+    if (int rc = z ? rfs_checks<TRfs<true, false>>(H) : rfs_checks<TRfs<false, false>>(H)) return rc;
     if (nrhs == 0) { if (steps) *steps = 0; return 0; }
     if (int rc = ensure_tindex(H, name)) return rc;
-    if (Z && trans == SLUAMD_CONJ) return dev ? rfs_dev<TRfs<Z, true>>(h, B, ldb, X, ldx, nrhs, berr, steps) : rfs_host<TRfs<Z, true>>(h, B, ldb, X, ldx, nrhs, berr, steps);
-    return dev ? rfs_dev<TRfs<Z, false>>(h, B, ldb, X, ldx, nrhs, berr, steps) : rfs_host<TRfs<Z, false>>(h, B, ldb, X, ldx, nrhs, berr, steps);
-}
-
-// 0: go on; the arguments every entry point checks before it looks at the matrix
-int check_args(sluamd_handle_t h, int trans, const void *B, int64_t ldb, const void *X, int64_t ldx, int32_t nrhs, const double *berr, bool z, const char *name)
-{
-    if (!h || !B || !X || !berr || nrhs < 0 || ldb < h->H.hs.n || ldx < h->H.hs.n) { set_error(std::string(name) + ": bad refinement arguments"); return SLUAMD_EINVAL; }
-    if (trans != SLUAMD_NOTRANS && trans != SLUAMD_TRANS && trans != SLUAMD_CONJ) { set_error(std::string(name) + ": trans must be SLUAMD_NOTRANS, SLUAMD_TRANS or SLUAMD_CONJ"); return SLUAMD_EINVAL; }
-    if (h->H.z != z) { set_error(std::string(name) + (z ? ": double handle: call sluamd_pdgsrfs3d_trans" : ": complex16 handle: call sluamd_pzgsrfs3d_trans")); return SLUAMD_EINVAL; }
-    return 0;
+    auto run = [&](auto K) { return host ? rfs_host<decltype(K)>(h, B, ldb, X, ldx, nrhs, berr, steps) : rfs_dev<decltype(K)>(h, B, ldb, X, ldx, nrhs, berr, steps); };
+    return !z ? run(TRfs<false, false>()) : trans == SLUAMD_CONJ ? run(TRfs<true, true>()) : run(TRfs<true, false>());
 }
 
 }  // namespace
@@ -101,32 +100,24 @@ extern "C" {
 
 int sluamd_pdgsrfs3d_trans(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    if (int rc = check_args(h, trans, B, ldb, X, ldx, nrhs, berr, false, "sluamd_pdgsrfs3d_trans")) return rc;
-    if (trans == SLUAMD_NOTRANS) return sluamd_pdgsrfs3d(h, B, ldb, X, ldx, nrhs, berr, steps);
-    return trefine<false>(h, trans, false, B, ldb, X, ldx, nrhs, berr, steps, "sluamd_pdgsrfs3d_trans");
+    return refine_entry(h, trans, B, ldb, X, ldx, nrhs, berr, steps, false, true, "sluamd_pdgsrfs3d_trans");
 }
 
 int sluamd_pdgsrfs3d_trans_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    if (int rc = check_args(h, trans, d_B, ldb, d_X, ldx, nrhs, berr, false, "sluamd_pdgsrfs3d_trans_dev")) return rc;
-    if (trans == SLUAMD_NOTRANS) return sluamd_pdgsrfs3d_dev(h, d_B, ldb, d_X, ldx, nrhs, berr, steps);
-    return trefine<false>(h, trans, true, d_B, ldb, d_X, ldx, nrhs, berr, steps, "sluamd_pdgsrfs3d_trans_dev");
+    return refine_entry(h, trans, d_B, ldb, d_X, ldx, nrhs, berr, steps, false, false, "sluamd_pdgsrfs3d_trans_dev");
 }
 
 int sluamd_pzgsrfs3d_trans(sluamd_handle_t h, int trans, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X, int64_t ldx, int32_t nrhs, double *berr,
                            int32_t *steps)
 {
-    if (int rc = check_args(h, trans, B, ldb, X, ldx, nrhs, berr, true, "sluamd_pzgsrfs3d_trans")) return rc;
-    if (trans == SLUAMD_NOTRANS) return sluamd_pzgsrfs3d(h, B, ldb, X, ldx, nrhs, berr, steps);
-    return trefine<true>(h, trans, false, reinterpret_cast<const double *>(B), ldb, reinterpret_cast<double *>(X), ldx, nrhs, berr, steps, "sluamd_pzgsrfs3d_trans");
+    return refine_entry(h, trans, B, ldb, X, ldx, nrhs, berr, steps, true, true, "sluamd_pzgsrfs3d_trans");
 }
 
 int sluamd_pzgsrfs3d_trans_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X, int64_t ldx, int32_t nrhs,
                                double *berr, int32_t *steps)
 {
-    if (int rc = check_args(h, trans, d_B, ldb, d_X, ldx, nrhs, berr, true, "sluamd_pzgsrfs3d_trans_dev")) return rc;
-    if (trans == SLUAMD_NOTRANS) return sluamd_pzgsrfs3d_dev(h, d_B, ldb, d_X, ldx, nrhs, berr, steps);
-    return trefine<true>(h, trans, true, reinterpret_cast<const double *>(d_B), ldb, reinterpret_cast<double *>(d_X), ldx, nrhs, berr, steps, "sluamd_pzgsrfs3d_trans_dev");
+    return refine_entry(h, trans, d_B, ldb, d_X, ldx, nrhs, berr, steps, true, false, "sluamd_pzgsrfs3d_trans_dev");
 }
 
 }  // extern "C"

@@ -9,7 +9,7 @@ using namespace sluamd;
 namespace {
 struct ZRfs {
     static constexpr bool z = true;
-    static constexpr const char *attach = "sluamd_zAttachMatrix", *other = "sluamd_pdgsrfs3d";
+    static constexpr const char *attach = "sluamd_zAttachMatrix";
     static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
     {
         eng::zrfs_residual(s, (int) H->hs.n, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
@@ -30,13 +30,13 @@ int sluamd_zAttachMatrix(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *
 int sluamd_pzgsrfs3d_dev(sluamd_handle_t h, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X, int64_t ldx, int32_t nrhs, double *berr,
                          int32_t *steps)
 {
-    return rfs_dev<ZRfs>(h, reinterpret_cast<const double *>(d_B), ldb, reinterpret_cast<double *>(d_X), ldx, nrhs, berr, steps);
+    return rfs_entry<ZRfs>(h, d_B, ldb, d_X, ldx, nrhs, berr, steps, false, "sluamd_pzgsrfs3d_dev");
 }
 
 int sluamd_pzgsrfs3d(sluamd_handle_t h, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X, int64_t ldx, int32_t nrhs, double *berr,
                      int32_t *steps)
 {
-    return rfs_host<ZRfs>(h, reinterpret_cast<const double *>(B), ldb, reinterpret_cast<double *>(X), ldx, nrhs, berr, steps);
+    return rfs_entry<ZRfs>(h, B, ldb, X, ldx, nrhs, berr, steps, true, "sluamd_pzgsrfs3d");
 }
 
 }  // extern "C"

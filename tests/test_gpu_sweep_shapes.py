@@ -38,11 +38,13 @@ def _copy(fs):
                             fs.Unzval.copy())
 
 
-def _factored(name):
-    """a handle holding the exact factors of case `name` (asserted)"""
+def _factored(name, profile=False):
+    """a handle holding the exact factors of case `name` (asserted); profile: factored under sluamd_set_profile(h, 1), which the solves then follow"""
     c, fs0, expL, expU = _prepared(name)[:4]
     fs = _copy(fs0)
     h = driver.LUHandle.from_store(fs)
+    if profile:
+        h.set_profile(True)
     assert h.pdgstrf3d(0.0) == 0
     h.copy_to_host()
     for which, got, exp in (("L", fs.Lnzval, expL), ("U", fs.Unzval, expU)):
@@ -92,6 +94,30 @@ def test_chunks_of_right_hand_sides_are_exact():
     h.destroy()
     h = _factored("narrow")
     _solve_exact("narrow", h, (300,))
+    h.destroy()
+
+
+@pytest.mark.parametrize("name", ["widths", "z_wide"])
+def test_profiled_in_place_sweeps_are_the_unprofiled_ones_bitwise(name):
+    """a handle factored under sluamd_set_profile(h, 1) solves with the plain in-place level loop (diagonal, then update, per level; no second vector) until
+    the profile is switched off: on one handle the profiled and the unprofiled solutions are the same bits, and both are the integer x.  1 and 3
+    right-hand sides, and one more than a chunk (48 at 256 columns, 30 at 200 complex16 columns): two chunks.  The in-place loop counts no launches."""
+    c = _prepared(name)[0]
+    chunk = (96 * 1024) // (max(c.widths) * (16 if c.z else 8))
+    assert chunk == (30 if c.z else 48)
+    h = _factored(name, profile=True)
+    rhs = [c.rhs(nrhs) for nrhs in (1, 3, chunk + 1)]
+    prof = []
+    for x, b in rhs:
+        prof.append(h.pdgstrs3d(b.copy(order="F")))
+        assert h.stats()["solve_launches"] == 0, (name, x.shape[1])
+    h.set_profile(False)                                                                    # takes effect at once; switching it on again would need a factorisation
+    for (x, b), p in zip(rhs, prof):
+        plain = h.pdgstrs3d(b.copy(order="F"))
+        if not c.z:
+            assert h.stats()["solve_launches"] > 0, (name, x.shape[1])                      # the links with the second vector ran
+        assert np.array_equal(np.ascontiguousarray(p).view(np.uint64), np.ascontiguousarray(plain).view(np.uint64)), (name, x.shape[1])
+        assert np.array_equal(p, x), (name, x.shape[1])
     h.destroy()
 
 
