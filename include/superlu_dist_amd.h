@@ -356,6 +356,40 @@ int sluamd_pzgsrfs3d_trans(sluamd_handle_t h, int trans, const sluamd_doublecomp
 int sluamd_pzgsrfs3d_trans_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
                                int64_t ldx, int32_t nrhs, double *berr, int32_t *steps);
 
+/* GMRES refinement preconditioned by the resident factors (GMRES-IR: Carson & Higham; the fallback Li & Demmel name for static pivoting): for systems on
+ * which the stationary loop above stalls or diverges because the spectral radius of I - (L U)^-1 A reaches one -- replaced tiny pivots, factors of an
+ * earlier matrix kept as a lagged preconditioner (sluamd_[dz]UpdateValues / sluamd_[dz]AttachMatrix with another matrix), growth.  The outer loop is that of
+ * sluamd_p[dz]gsrfs3d[_trans]: the same residual and berr kernels, the same stopping rule (berr > eps, 2 berr <= previous, < 20 outer steps), the same
+ * update; the correction of a step is one cycle of right-preconditioned GMRES on A1 d = r, A1 = Pc op(A) Pc^T, M = L U, d_0 = 0, instead of one
+ * application of (L U)^-1: classical Gram-Schmidt with one reorthogonalisation on the device, Hessenberg matrix and Givens rotations on the host.  A cycle
+ * ends when the residual estimate is <= inner_tol ||r||_2, on a breakdown, after `restart` iterations, or when the budget leaves one application of the
+ * factors; its correction d = M^-1 V y costs that last application.  The accuracy reported is computed by the refinement's own kernels from the true
+ * residual; GMRES only proposes corrections.  Reductions use no floating-point atomics: on a deterministic handle two calls return the same bits.
+ * trans, B, X, ldb, ldx, nrhs, berr, the ordering, equilibrated handles (the attached, scaled system is refined) and nrhs == 0: the contract of
+ * sluamd_p[dz]gsrfs3d_trans[_dev].  *steps = OUTER steps (cycles) of the last right-hand side; solves[j] (may be NULL) = applications of the factors spent
+ * on right-hand side j: iterations + 1 per cycle.  When max_solves is reached the cycle in hand is finished into X, the true berr is computed and the call
+ * returns 0 with solves[j] == max_solves (a single remaining application is spent on one plain refinement step: a cycle needs two).
+ * A residual whose 2-norm is not a positive finite double (its square under- or overflows) gets the plain step instead of a cycle; a residual that
+ * op(A) (L U)^-1 maps to zero ends the refinement of that right-hand side with X untouched and the berr reached so far (one application spent), return 0.
+ * opt == NULL: the defaults.  Device memory: restart + 5 vectors of n values and 1 MiB of partial sums, allocated on the first call of a handle, regrown
+ * when restart grows, released with the attached matrix.
+ * Errors beyond those of sluamd_p[dz]gsrfs3d_trans, all SLUAMD_EINVAL with a message: restart outside [1, 64], max_solves < 1, inner_tol outside (0, 1);
+ * a handle of a multi-rank grid; the handle of a batch (sluamd_BatchHandle). */
+typedef struct sluamd_gmres {
+    int32_t restart;      /* basis vectors per cycle, 1..64; default 20 (the limit of the outer loop) */
+    int32_t max_solves;   /* cap on applications of the factors per right-hand side, >= 1; default 100 */
+    double  inner_tol;    /* cycle ends at estimate <= inner_tol * ||r||_2, in (0,1); default 2^-30: two outer steps reach eps */
+} sluamd_gmres_t;
+void sluamd_default_gmres(sluamd_gmres_t *opt);
+int sluamd_pdgsrfs3d_gmres(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs,
+                           const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves);
+int sluamd_pdgsrfs3d_gmres_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs,
+                               const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves);
+int sluamd_pzgsrfs3d_gmres(sluamd_handle_t h, int trans, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X,
+                           int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves);
+int sluamd_pzgsrfs3d_gmres_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
+                               int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves);
+
 /* ---- Equil = YES: row / column equilibration on the device and the solve phase of the expert driver in the caller's ordering and
  * scaling (pdgsequ + pdlaqgs at the head of pdgssvx3d, SRC/double/pdgssvx3d.c:673-729; B scaled by R before the solve, :1450-1465;
  * X scaled by C after it, :1806-1821, the roles swapped for a transposed system).  For handles made by

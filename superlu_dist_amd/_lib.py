@@ -52,6 +52,11 @@ class Update(C.Structure):
     _fields_ = [("anorm", C.c_double), ("equed", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Gmres(C.Structure):
+    """sluamd_gmres_t"""
+    _fields_ = [("restart", C.c_int32), ("max_solves", C.c_int32), ("inner_tol", C.c_double)]
+
+
 class RowPerm(C.Structure):
     """sluamd_rowperm_t"""
     _fields_ = [("info", C.c_int32), ("rounds", C.c_int32), ("matched_device", C.c_int64), ("augmentations", C.c_int64)]
@@ -67,6 +72,7 @@ EXPORTS = [
     "sluamd_zAttachMatrix", "sluamd_pzgsrfs3d", "sluamd_pzgsrfs3d_dev",
     "sluamd_pdgstrs3d_trans", "sluamd_pdgstrs3d_trans_dev", "sluamd_pzgstrs3d_trans", "sluamd_pzgstrs3d_trans_dev",
     "sluamd_pdgsrfs3d_trans", "sluamd_pdgsrfs3d_trans_dev", "sluamd_pzgsrfs3d_trans", "sluamd_pzgsrfs3d_trans_dev",
+    "sluamd_default_gmres", "sluamd_pdgsrfs3d_gmres", "sluamd_pdgsrfs3d_gmres_dev", "sluamd_pzgsrfs3d_gmres", "sluamd_pzgsrfs3d_gmres_dev",
     "sluamd_dEquilibrate", "sluamd_zEquilibrate", "sluamd_GetScalings",
     "sluamd_dEquilibrateWith", "sluamd_zEquilibrateWith", "sluamd_dLargeDiag", "sluamd_zLargeDiag", "sluamd_SetRowPerm",
     "sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev",
@@ -162,6 +168,13 @@ def bind(L):
     for name in ("sluamd_pdgsrfs3d_trans", "sluamd_pdgsrfs3d_trans_dev", "sluamd_pzgsrfs3d_trans", "sluamd_pzgsrfs3d_trans_dev"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, P_dbl, P_int]
+    # GMRES refinement: only in the product library (its Krylov kernels have no CPU restatement)
+    if hasattr(L, "sluamd_default_gmres"):
+        L.sluamd_default_gmres.argtypes = [C.POINTER(Gmres)]
+        L.sluamd_default_gmres.restype = None
+    for name in ("sluamd_pdgsrfs3d_gmres", "sluamd_pdgsrfs3d_gmres_dev", "sluamd_pzgsrfs3d_gmres", "sluamd_pzgsrfs3d_gmres_dev"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Gmres), P_dbl, P_int, P_int]
     # equilibration and the expert driver's solve phase: only in the product library (the CPU test build has no equilibration kernels)
     for name in ("sluamd_dEquilibrate", "sluamd_zEquilibrate"):
         if hasattr(L, name):

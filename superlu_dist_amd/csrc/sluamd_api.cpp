@@ -473,6 +473,7 @@ void free_rfs(Handle *H)
     H->d_rfs_rp.reset(); H->d_rfs_ci.reset(); H->d_rfs_pc.reset(); H->d_rfs_av.reset(); H->d_rfs_work.reset(); H->d_rfs_s.reset();
     H->d_rfs_tcp.reset(); H->d_rfs_tri.reset(); H->d_rfs_tpos.reset();       // (the transposed index belongs to the pattern that goes)
     H->d_rp_pr.reset(); H->d_rp_pcpr.reset(); H->d_rp_rs.reset();            // (and so does the row permutation of sluamd_SetRowPerm)
+    H->d_gm_work.reset(); H->d_gm_part.reset(); H->gm_restart = 0;            // (and the Krylov workspace of sluamd_p[dz]gsrfs3d_gmres)
     H->rfs_nnz = 0;
     H->rfs_z = false;
 }
@@ -509,18 +510,13 @@ extern "C" int sluamd_dAttachMatrix(sluamd_handle_t h, sluamd_int_t n, const slu
     return attach_rfs(h, n, rowptr, colind, nzval, perm_c, false, "sluamd_dAttachMatrix");
 }
 
-namespace {
-struct DRfs {   // the double kernels of the refinement driver (sluamd_refine.h)
-    static constexpr bool z = false;
-    static constexpr const char *attach = "sluamd_dAttachMatrix";
-    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
-    {
-        eng::rfs_residual(s, (int) H->hs.n, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
-    }
-    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x) { eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x); }
-    static int solve(Handle *H, double *r_perm, int n) { return run_solve_dev(H, r_perm, n, 1); }
-};
-}  // namespace
+// the double kernels of the refinement driver (DRfs: sluamd_refine.h)
+void DRfs::residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
+{
+    eng::rfs_residual(s, (int) H->hs.n, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
+}
+void DRfs::update(hipStream_t s, const Handle *H, const double *dx_perm, double *x) { eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x); }
+int DRfs::solve(Handle *H, double *r_perm, int n) { return run_solve_dev(H, r_perm, n, 1); }
 
 extern "C" {
 

@@ -260,6 +260,7 @@ int create(sluamd_batch_t *out, bool z, sluamd_symb_t s, int32_t count, const sl
     sluamd_symb_free(big);
     if (rc) { batch_free(b); return rc; }
     Handle *H = &b->h->H;
+    H->batch_owned = true;
     auto fail = [&](int code, const char *what) { if (what) set_error(me + what); batch_free(b); return code; };
     if (H->split.active) return fail(SLUAMD_EINVAL, "the handle refined a wide supernode");
     {   // the block-diagonal CSR with its values, attached as sluamd_[dz]AttachMatrix would (the refinement and the equilibration read it): the one upload of the values

@@ -1,0 +1,273 @@
+// sluamd_gmres.cpp -- GMRES refinement preconditioned by the resident factors: sluamd_p[dz]gsrfs3d_gmres[_dev] (contract: include/superlu_dist_amd.h;
+// the algorithm, CGS2, the reduction order and the storage: DESIGN.md "GMRES refinement").  The outer loop is rfs_dev's (sluamd_refine.h) with the same policies
+// K -- the true residual and berr by K::residual, the same stop rule, K::update -- and the correction K::solve(r) replaced by one cycle of right-preconditioned
+// GMRES on A1 d = r in the permuted space, A1 = Pc op(A) Pc^T, M = L U, d_0 = 0.  K::solve is the only way into the sweeps.
+//   A1 z from the policy kernels: x0 = 0; K::update(x0 += Pc^T z); K::residual(x0, b = 0) = Pc (0 - op(A) x0) = -A1 z.  The sign is not undone by a pass of
+//   its own: CGS2 runs on w' = -w (every coefficient comes out negated, the norm does not), the host negates the Hessenberg column and v_{j+1} = w' / (-h).
+//   K::residual also leaves a backward error of that product in the handle's berr word; the outer loop clears the word before every true residual and reads
+//   it right after, so nothing of it reaches the caller.
+// A file of its own: the CPU test build (oracle/Makefile) links a fixed list of the host sources, none of which may reference a symbol of this file.
+#include <algorithm>
+#include <cmath>
+#include <complex>
+#include <vector>
+#include "sluamd_refine.h"
+#include "sluamd_gkernels.inc"
+
+using namespace sluamd;
+
+namespace {
+
+typedef std::complex<double> cplx;
+const int GM_MAX_RESTART = 64;
+// slots of the partials slab: the dots of up to GM_MAX_RESTART basis vectors (two doubles each for complex16), ||w||^2 from k_gm_dots, ||w||^2 from k_gm_axpys
+const int GM_SLOT_NDOT = 2 * GM_MAX_RESTART, GM_SLOT_NAXPY = GM_SLOT_NDOT + 1, GM_SLOTS = GM_SLOT_NAXPY + 1;
+const int GM_RES = 2 * 2 * GM_MAX_RESTART + 2;      // results behind the slab: [h of pass 1 | h of pass 2 | ||w||^2], doubles
+
+struct Work {                                       // the Krylov workspace of one call
+    int64_t ns = 0, nu = 0;                         // doubles / 16-byte units per vector
+    double *V = nullptr, *z = nullptr, *w = nullptr, *x0 = nullptr, *zero = nullptr, *slab = nullptr, *res = nullptr;
+};
+
+// [v_0 .. v_restart | z | w | x0 | 0]: allocated on the first call, regrown when restart grows; zero-filled, and the pad of a double vector of odd order is
+// cleared again on every call (a NaN met once must not stay in it)
+int ensure_work(Handle *H, int restart, bool z, Work &W)
+{
+    const int64_t n = H->hs.n;
+    W.ns = z ? 2 * n : ((n + 1) & ~(int64_t) 1);
+    W.nu = W.ns / 2;
+    const int64_t nvec = (int64_t) restart + 5;
+    if (!H->d_gm_work.p || H->gm_restart < restart) {
+        if (int rc = H->d_gm_work.alloc(nvec * W.ns, H->device, "the Krylov basis of the GMRES refinement")) { H->gm_restart = 0; return rc; }
+        H->gm_restart = restart;
+        HIPCHK(hipMemsetAsync(H->d_gm_work.p, 0, sizeof(double) * (size_t) (nvec * W.ns), H->stream));
+    }
+    if (!H->d_gm_part.p) {
+        if (int rc = H->d_gm_part.alloc((int64_t) GM_SLOTS * GM_GRID + GM_RES, H->device, "the partial sums of the GMRES refinement")) return rc;
+    }
+    const int64_t have = (int64_t) H->gm_restart + 5;
+    if (!z && W.ns != n) HIPCHK(hipMemset2DAsync(H->d_gm_work.p + n, sizeof(double) * (size_t) W.ns, 0, sizeof(double), (size_t) have, H->stream));
+    double *p = H->d_gm_work.p;
+    W.V = p; W.z = p + (have - 4) * W.ns; W.w = p + (have - 3) * W.ns; W.x0 = p + (have - 2) * W.ns; W.zero = p + (have - 1) * W.ns;
+    W.slab = H->d_gm_part.p; W.res = H->d_gm_part.p + (int64_t) GM_SLOTS * GM_GRID;
+    return 0;
+}
+
+// One cycle on the residual in W.w (overwritten): the correction u = M^-1 V y ends up in W.z and is added to x.  `solves`: applications of the factors so far
+// for this right-hand side, at least two short of the budget on entry.  Returns 1, with the residual untouched, when its 2-norm is not a positive finite
+// double: the caller then takes the plain step.  Returns 2, with X untouched and one application spent, when the first Krylov vector maps to zero: the
+// caller ends the refinement of this right-hand side with the berr it has
+template <class K> int gmres_cycle(Handle *H, const Work &W, const sluamd_gmres_t &o, double *Xc, double safe1, double safe2, int &solves)
+{
+    const bool z = K::z;
+    const int vs = z ? 2 : 1, n = (int) H->hs.n, m = o.restart;
+    hipStream_t s = H->stream;
+    const size_t vbytes = sizeof(double) * (size_t) W.ns;
+    double hres[GM_RES];
+    // beta = ||r||_2, v_0 = r / beta
+    geng::dots(s, z, W.nu, W.V, W.ns, 0, W.w, W.slab, 0, GM_SLOT_NDOT);
+    geng::sum(s, W.nu, W.slab, GM_SLOT_NDOT, 1, W.res);
+    HIPCHK(hipMemcpyAsync(hres, W.res, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const double beta = std::sqrt(hres[0]);
+    if (!(beta > 0.0) || !std::isfinite(beta)) return 1;       // ||r||^2 under- or overflowed: no Krylov space to build, W.w still holds r
+    geng::scale(s, W.nu, W.V, W.w, beta);
+    std::vector<cplx> R((size_t) m * m, cplx(0.0)), g((size_t) m + 1, cplx(0.0)), sn((size_t) m, cplx(0.0)), col((size_t) m + 1);
+    std::vector<double> cs((size_t) m, 0.0);
+    g[0] = beta;
+    int kdim = 0;
+    for (int j = 0; j < m; ++j) {
+        const int nb = j + 1;                                   // basis vectors so far
+        // z = M^-1 v_j;  w' = -A1 z
+        HIPCHK(hipMemcpyAsync(W.z, W.V + (int64_t) j * W.ns, vbytes, hipMemcpyDeviceToDevice, s));
+        if (int rc = K::solve(H, W.z, n)) return rc;
+        ++solves;
+        HIPCHK(hipMemsetAsync(W.x0, 0, vbytes, s));
+        K::update(s, H, W.z, W.x0);
+        K::residual(s, H, W.x0, W.zero, W.w, safe1, safe2);
+        // CGS2: h = V^H w', w' -= V h, twice, the coefficients staying on the device between the two launches of a pass
+        for (int pass = 0; pass < 2; ++pass) {
+            double *h = W.res + (int64_t) pass * nb * vs;
+            for (int c0 = 0; c0 < nb; c0 += GM_CHUNK)
+                geng::dots(s, z, W.nu, W.V + (int64_t) c0 * W.ns, W.ns, std::min(GM_CHUNK, nb - c0), W.w, W.slab, c0 * vs, -1);   // (the norm CGS2 uses is k_gm_axpys')
+            geng::sum(s, W.nu, W.slab, 0, nb * vs, h);
+            for (int c0 = 0; c0 < nb; c0 += GM_CHUNK)
+                geng::axpys(s, z, W.nu, W.V + (int64_t) c0 * W.ns, W.ns, std::min(GM_CHUNK, nb - c0), W.w, h + (int64_t) c0 * vs, W.slab, GM_SLOT_NAXPY);
+        }
+        geng::sum(s, W.nu, W.slab, GM_SLOT_NAXPY, 1, W.res + 2 * (int64_t) nb * vs);
+        HIPCHK(hipMemcpyAsync(hres, W.res, sizeof(double) * (size_t) (2 * nb * vs + 1), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const double hn = std::sqrt(hres[2 * nb * vs]);
+        for (int i = 0; i < nb; ++i) {
+            const double *a = hres + i * vs, *b = hres + (nb + i) * vs;
+            col[i] = -(cplx(a[0], z ? a[1] : 0.0) + cplx(b[0], z ? b[1] : 0.0));
+        }
+        // the rotations so far, then the one that removes h_{j+1,j}
+        for (int i = 0; i < j; ++i) {
+            const cplx t = cs[i] * col[i] + sn[i] * col[i + 1];
+            col[i + 1] = -std::conj(sn[i]) * col[i] + cs[i] * col[i + 1];
+            col[i] = t;
+        }
+        const double aa = std::abs(col[j]), den = std::hypot(aa, hn);
+        if (!(den > 0.0) || !std::isfinite(den)) break;         // a column of zeros (or worse): the cycle ends with the columns before it
+        const cplx ph = aa > 0.0 ? col[j] / aa : cplx(1.0);
+        cs[j] = aa / den; sn[j] = ph * (hn / den);
+        col[j] = ph * den;
+        for (int i = 0; i <= j; ++i) R[(size_t) i * m + j] = col[i];
+        g[j + 1] = -std::conj(sn[j]) * g[j];
+        g[j] = cs[j] * g[j];
+        kdim = j + 1;
+        // before v_{j+1} is formed: a happy breakdown never divides
+        if (std::abs(g[j + 1]) <= o.inner_tol * beta || hn == 0.0 || j + 1 == m || solves + 2 > o.max_solves) break;
+        geng::scale(s, W.nu, W.V + (int64_t) (j + 1) * W.ns, W.w, -hn);
+    }
+    if (kdim == 0) return 2;                                    // op(A) M^-1 r = 0 (or not finite): no correction to propose, X untouched
+    // R y = g on the host, u = V y, d = M^-1 u, x += Pc^T d
+    std::vector<cplx> y((size_t) kdim);
+    for (int i = kdim - 1; i >= 0; --i) {
+        cplx t = g[i];
+        for (int k = i + 1; k < kdim; ++k) t -= R[(size_t) i * m + k] * y[k];
+        y[i] = t / R[(size_t) i * m + i];
+    }
+    for (int c0 = 0; c0 < kdim; c0 += GM_CHUNK) {
+        double yc[2 * GM_CHUNK];
+        const int nv = std::min(GM_CHUNK, kdim - c0);
+        for (int k = 0; k < nv; ++k) { yc[2 * k] = y[c0 + k].real(); yc[2 * k + 1] = y[c0 + k].imag(); }
+        geng::combine(s, z, W.nu, W.V + (int64_t) c0 * W.ns, W.ns, nv, W.z, yc, c0 > 0);
+    }
+    if (int rc = K::solve(H, W.z, n)) return rc;
+    ++solves;
+    K::update(s, H, W.z, Xc);
+    return 0;
+}
+
+// d_B, d_X: device-resident, original ordering, column-major (ld in values); the loop of rfs_dev with the correction of a step replaced
+template <class K> int gmres_dev(sluamd_handle_t h, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, const sluamd_gmres_t &o, double *berr, int32_t *steps,
+                                 int32_t *solves_out)
+{
+    Handle *H = &h->H;
+    HIPCHK(hipSetDevice(H->device));
+    Work W;
+    if (int rc = ensure_work(H, o.restart, K::z, W)) return rc;
+    const int vs = K::z ? 2 : 1;
+    const int n = (int) H->hs.n;
+    const int ITMAX = 20;
+    const double eps = 0x1p-53, safmin = 2.2250738585072014e-308;
+    const double safe1 = (double) (n + 1) * safmin, safe2 = safe1 / eps;
+    hipStream_t s = H->stream;
+    int count = 0;
+    for (int j = 0; j < nrhs; ++j) {
+        const double *Bc = d_B + (size_t) j * ldb * vs;
+        double *Xc = d_X + (size_t) j * ldx * vs;
+        double lstres = 3.0;
+        int solves = 0;
+        count = 0;
+        for (;;) {
+            HIPCHK(hipMemsetAsync(H->d_rfs_s.p, 0, sizeof(unsigned long long), s));
+            K::residual(s, H, Xc, Bc, W.w, safe1, safe2);
+            double sv = 0.0;
+            HIPCHK(hipMemcpyAsync(&sv, H->d_rfs_s.p, sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            berr[j] = sv;
+            if (!(sv > eps && sv * 2 <= lstres && count < ITMAX && solves < o.max_solves)) break;
+            // one application left: a cycle needs two (an iteration and the end of the cycle), so the step is the plain one
+            const int rc = o.max_solves - solves < 2 ? 1 : gmres_cycle<K>(H, W, o, Xc, safe1, safe2, solves);
+            if (rc < 0) return rc;
+            if (rc == 2) break;
+            if (rc == 1) {
+                if (int rs = K::solve(H, W.w, n)) return rs;
+                ++solves;
+                K::update(s, H, W.w, Xc);
+            }
+            lstres = sv;
+            ++count;
+        }
+        if (solves_out) solves_out[j] = solves;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (steps) *steps = count;
+    return 0;
+}
+
+// B, X: host memory; one column at a time through the resident work vectors of the plain refinement (r_perm | b | x), as rfs_host
+template <class K> int gmres_host(sluamd_handle_t h, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, const sluamd_gmres_t &o, double *berr, int32_t *steps,
+                                  int32_t *solves)
+{
+    Handle *H = &h->H;
+    HIPCHK(hipSetDevice(H->device));
+    const int vs = K::z ? 2 : 1;
+    const int64_t n = H->hs.n;
+    const size_t col = sizeof(double) * (size_t) n * vs;
+    double *d_b = H->d_rfs_work.p + (size_t) n * vs, *d_x = H->d_rfs_work.p + 2 * (size_t) n * vs;
+    int last = 0;
+    for (int j = 0; j < nrhs; ++j) {
+        HIPCHK(hipMemcpy(d_b, B + (size_t) j * ldb * vs, col, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_x, X + (size_t) j * ldx * vs, col, hipMemcpyHostToDevice));
+        if (int rc = gmres_dev<K>(h, d_b, n, d_x, n, 1, o, berr + j, &last, solves ? solves + j : nullptr)) return rc;
+        HIPCHK(hipMemcpy(X + (size_t) j * ldx * vs, d_x, col, hipMemcpyDeviceToHost));
+    }
+    if (steps) *steps = last;
+    return 0;
+}
+
+int gmres_entry(sluamd_handle_t h, int trans, const void *Bv, int64_t ldb, void *Xv, int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr, int32_t *steps,
+                int32_t *solves, bool z, bool host, const char *name)
+{
+    const int c = check_solve_args(h, trans, Bv, ldb, Xv, ldx, nrhs, berr, true, z, name, "refinement");
+    if (c < 0) return c;
+    const std::string me = std::string(name) + ": ";
+    sluamd_gmres_t o;
+    sluamd_default_gmres(&o);
+    if (opt) o = *opt;
+    if (o.restart < 1 || o.restart > GM_MAX_RESTART) { set_error(me + "restart must lie in [1, 64]"); return SLUAMD_EINVAL; }
+    if (o.max_solves < 1) { set_error(me + "max_solves must be at least 1"); return SLUAMD_EINVAL; }
+    if (!(o.inner_tol > 0.0 && o.inner_tol < 1.0)) { set_error(me + "inner_tol must lie in (0, 1)"); return SLUAMD_EINVAL; }
+    Handle *H = &h->H;
+    if (H->grid.size() > 1) { set_error(me + "the GMRES refinement needs a 1 x 1 x 1 handle (grid handles refine with sluamd_p[dz]gsrfs3d[_trans])"); return SLUAMD_EINVAL; }
+    if (H->batch_owned) { set_error(me + "the handle belongs to a batch (sluamd_BatchHandle): the GMRES refinement does not run on batches"); return SLUAMD_EINVAL; }
+    if (int rc = z ? rfs_checks<ZRfs>(H) : rfs_checks<DRfs>(H)) return rc;
+    if (nrhs == 0) { if (steps) *steps = 0; return 0; }
+    if (trans != SLUAMD_NOTRANS) { if (int rc = ensure_tindex(H, name)) return rc; }
+    const double *B = static_cast<const double *>(Bv);
+    double *X = static_cast<double *>(Xv);
+    auto run = [&](auto K) { return host ? gmres_host<decltype(K)>(h, B, ldb, X, ldx, nrhs, o, berr, steps, solves) : gmres_dev<decltype(K)>(h, B, ldb, X, ldx, nrhs, o, berr, steps, solves); };
+    if (trans == SLUAMD_NOTRANS) return z ? run(ZRfs()) : run(DRfs());
+    return !z ? run(TRfs<false, false>()) : trans == SLUAMD_CONJ ? run(TRfs<true, true>()) : run(TRfs<true, false>());
+}
+
+}  // namespace
+
+extern "C" {
+
+void sluamd_default_gmres(sluamd_gmres_t *o)
+{
+    if (!o) return;
+    o->restart = 20; o->max_solves = 100; o->inner_tol = 0x1p-30;
+}
+
+int sluamd_pdgsrfs3d_gmres(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr,
+                           int32_t *steps, int32_t *solves)
+{
+    return gmres_entry(h, trans, B, ldb, X, ldx, nrhs, opt, berr, steps, solves, false, true, "sluamd_pdgsrfs3d_gmres");
+}
+
+int sluamd_pdgsrfs3d_gmres_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr,
+                               int32_t *steps, int32_t *solves)
+{
+    return gmres_entry(h, trans, d_B, ldb, d_X, ldx, nrhs, opt, berr, steps, solves, false, false, "sluamd_pdgsrfs3d_gmres_dev");
+}
+
+int sluamd_pzgsrfs3d_gmres(sluamd_handle_t h, int trans, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X, int64_t ldx, int32_t nrhs,
+                           const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves)
+{
+    return gmres_entry(h, trans, B, ldb, X, ldx, nrhs, opt, berr, steps, solves, true, true, "sluamd_pzgsrfs3d_gmres");
+}
+
+int sluamd_pzgsrfs3d_gmres_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X, int64_t ldx, int32_t nrhs,
+                               const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves)
+{
+    return gmres_entry(h, trans, d_B, ldb, d_X, ldx, nrhs, opt, berr, steps, solves, true, false, "sluamd_pzgsrfs3d_gmres_dev");
+}
+
+}  // extern "C"

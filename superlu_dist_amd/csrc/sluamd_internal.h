@@ -386,6 +386,10 @@ struct Handle {
     // transposed index of the attached matrix (sluamd_trefine.cpp), built on the first transposed refinement: column pointers, and per entry in
     // column order (rows ascending inside a column) its row and its position in d_rfs_av.  No values: the kernels read d_rfs_av[d_rfs_tpos[e]]
     DevBuf<int> d_rfs_tcp, d_rfs_tri, d_rfs_tpos;
+    // GMRES refinement (sluamd_gmres.cpp), allocated on the first such call: [v_0 .. v_gm_restart | z | w | x0 | 0] of n values each (a double vector padded to an
+    // even count) and the reductions' partials slab + results.  They go with the attached matrix (free_rfs)
+    DevBuf<double> d_gm_work, d_gm_part; int gm_restart = 0;
+    bool batch_owned = false;                               // the handle of a batch object (sluamd_BatchHandle lends it out)
     void *h_pinned = nullptr; size_t pinned_bytes = 0;      // bounded pinned staging buffer (value upload / download)
     bool z = false;                                         // complex16 (doublecomplex) values: 16-byte elements
     bool dinv_ready = false;                                // T.dinv holds the inverses for the current factors

@@ -9,9 +9,10 @@
 //   K::solve(H, r_perm, n)                          the correction, in place in r_perm: run_solve_dev for A x = b; the transposed policies run the
 //                                                   transposed sweeps (A^T d = r is A1^T (Pc d) = Pc r for the factors of A1 = Pc A Pc^T: the same
 //                                                   permutation on both sides, so r_perm and K::update are used exactly alike)
-// sluamd_api.cpp instantiates it for double (eng::rfs_*), sluamd_zrefine.cpp for complex16 (eng::zrfs_*), sluamd_trefine.cpp for the transposed and
-// conjugate-transposed systems of both (eng::rfs_residual_t / eng::zrfs_residual_t).  Keep those instantiations out of sluamd_api.cpp: the CPU test build
-// links the host sources without the complex and the transposed kernels.
+// The policies are declared below and DEFINED beside their entry points: DRfs in sluamd_api.cpp (eng::rfs_*), ZRfs in sluamd_zrefine.cpp (eng::zrfs_*),
+// TRfs<Z, CONJ> in sluamd_trefine.cpp for the transposed and conjugate-transposed systems of both (eng::rfs_residual_t / eng::zrfs_residual_t).  Keep the
+// complex and transposed definitions out of sluamd_api.cpp: the CPU test build links the host sources without the complex and the transposed kernels.
+// The GMRES refinement (sluamd_gmres.cpp) runs the same three calls of the same policies around its Krylov kernels.
 #pragma once
 #include "sluamd_comm.h"
 #include "sluamd_plan.h"
@@ -24,6 +25,31 @@ int attach_rfs(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, co
                const sluamd_int_t *perm_c, bool z, const char *who);
 // the transposed index of the attached matrix (Handle::d_rfs_tcp / d_rfs_tri / d_rfs_tpos), built on first use: sluamd_trefine.cpp, which describes it
 int ensure_tindex(Handle *H, const char *who);
+
+struct DRfs {   // double, A x = b: sluamd_api.cpp
+    static constexpr bool z = false;
+    static constexpr const char *attach = "sluamd_dAttachMatrix";
+    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2);
+    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x);
+    static int solve(Handle *H, double *r_perm, int n);
+};
+struct ZRfs {   // complex16, A x = b: sluamd_zrefine.cpp
+    static constexpr bool z = true;
+    static constexpr const char *attach = "sluamd_zAttachMatrix";
+    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2);
+    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x);
+    static int solve(Handle *H, double *r_perm, int n);
+};
+template <bool Z, bool CONJ> struct TRfs {   // A^T x = b / A^H x = b of either precision: sluamd_trefine.cpp, which instantiates <false, false>, <true, false>, <true, true>
+    static constexpr bool z = Z;
+    static constexpr const char *attach = Z ? "sluamd_zAttachMatrix" : "sluamd_dAttachMatrix";
+    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2);
+    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x);
+    static int solve(Handle *H, double *r_perm, int n);
+};
+extern template struct TRfs<false, false>;
+extern template struct TRfs<true, false>;
+extern template struct TRfs<true, true>;
 
 // what the driver needs beyond the arguments its entry points check (check_solve_args, sluamd_plan.h: handle, blocks, nrhs, leading dimensions, berr, trans,
 // precision, planned transposed sweeps): a matrix attached to the handle -- always of the handle's precision, attach_rfs refuses any other

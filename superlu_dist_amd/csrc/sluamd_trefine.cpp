@@ -55,23 +55,24 @@ int sluamd::ensure_tindex(Handle *H, const char *who)
     return 0;
 }
 
-namespace {
+template <bool Z, bool CONJ> void TRfs<Z, CONJ>::residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
+{
+    if (Z) eng::zrfs_residual_t(s, CONJ, (int) H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
+    else eng::rfs_residual_t(s, (int) H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
+}
+template <bool Z, bool CONJ> void TRfs<Z, CONJ>::update(hipStream_t s, const Handle *H, const double *dx_perm, double *x)
+{
+    if (Z) eng::zrfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
+    else eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
+}
+template <bool Z, bool CONJ> int TRfs<Z, CONJ>::solve(Handle *H, double *r_perm, int n) { return run_tsolve(H, Z && CONJ, r_perm, n, 1); }
+namespace sluamd {
+template struct TRfs<false, false>;
+template struct TRfs<true, false>;
+template struct TRfs<true, true>;
+}
 
-template <bool Z, bool CONJ> struct TRfs {
-    static constexpr bool z = Z;
-    static constexpr const char *attach = Z ? "sluamd_zAttachMatrix" : "sluamd_dAttachMatrix";
-    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
-    {
-        if (Z) eng::zrfs_residual_t(s, CONJ, (int) H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
-        else eng::rfs_residual_t(s, (int) H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
-    }
-    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x)
-    {
-        if (Z) eng::zrfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
-        else eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
-    }
-    static int solve(Handle *H, double *r_perm, int n) { return run_tsolve(H, Z && CONJ, r_perm, n, 1); }
-};
+namespace {
 
 // One entry for the four calls below.  trans == SLUAMD_NOTRANS: the untransposed call of the precision.  Else the checks in the order of the transposed
 // solves, then the index, then the shared driver.  B, X: n x nrhs values of precision z, on the host or on the device

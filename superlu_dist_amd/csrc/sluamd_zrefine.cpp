@@ -6,18 +6,12 @@
 
 using namespace sluamd;
 
-namespace {
-struct ZRfs {
-    static constexpr bool z = true;
-    static constexpr const char *attach = "sluamd_zAttachMatrix";
-    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
-    {
-        eng::zrfs_residual(s, (int) H->hs.n, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
-    }
-    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x) { eng::zrfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x); }
-    static int solve(Handle *H, double *r_perm, int n) { return run_solve_dev(H, r_perm, n, 1); }
-};
-}  // namespace
+void ZRfs::residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
+{
+    eng::zrfs_residual(s, (int) H->hs.n, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
+}
+void ZRfs::update(hipStream_t s, const Handle *H, const double *dx_perm, double *x) { eng::zrfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x); }
+int ZRfs::solve(Handle *H, double *r_perm, int n) { return run_solve_dev(H, r_perm, n, 1); }
 
 extern "C" {
 

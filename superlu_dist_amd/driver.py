@@ -373,18 +373,27 @@ class LUHandle:
         """Device copy of the ORIGINAL matrix (CSR) + perm_c for pdgsrfs3d (sluamd_dAttachMatrix, or sluamd_zAttachMatrix on a complex16 handle)."""
         _attach_matrix(self._h, self.z, n, rowptr, colind, nzval, perm_c)
 
-    def pdgsrfs3d(self, b, x, trans="N"):
+    def pdgsrfs3d(self, b, x, trans="N", method="plain", restart=None, inner_tol=None, max_solves=None):
         """Iterative refinement of x (original ordering) for the attached matrix; returns (x, berr[nrhs], steps).
+        method="gmres": the correction of every step is a cycle of GMRES preconditioned by the factors (sluamd_p[dz]gsrfs3d_gmres; restart, inner_tol,
+        max_solves: sluamd_gmres_t, None = the library's default); returns (x, berr[nrhs], steps, solves[nrhs]), steps counting the outer steps.  b and x
+        are checked as for trans = "T" / "C"; ValueError also for another method, or for restart / inner_tol / max_solves with method="plain".
         pzgsrfs3d on a complex16 handle (complex b and x).  trans = "T" / "C": the transposed / conjugate-transposed system A^T x = b, A^H x = b of
         the attached matrix (sluamd_p[dz]gsrfs3d_trans), x e.g. from pdgstrs3d(trans=...).  ValueError, before any library call:
         a trans other than "N", "T", "C"; b or x of another dtype than the handle's; shapes that differ or are not (n,) / (n, nrhs)."""
+        opt = _gmres_opt(method, restart, inner_tol, max_solves)
+        if opt is not None:
+            return _gsrfs3d_gmres(self._h, self.z, b, x, trans, self.n, opt)
         return _gsrfs3d(self._h, self.z, b, x, trans, self.n)
 
     pzgsrfs3d = pdgsrfs3d
 
-    def pdgsrfs3d_dev(self, d_b, ldb, d_x, ldx, nrhs, trans="N"):
+    def pdgsrfs3d_dev(self, d_b, ldb, d_x, ldx, nrhs, trans="N", method="plain", restart=None, inner_tol=None, max_solves=None):
         """sluamd_p[dz]gsrfs3d_dev: b, x device pointers (column-major, ld in values); x refined in place.  Returns (berr[nrhs], steps).
-        trans = "T" / "C": sluamd_p[dz]gsrfs3d_trans_dev."""
+        trans = "T" / "C": sluamd_p[dz]gsrfs3d_trans_dev.  method="gmres": sluamd_p[dz]gsrfs3d_gmres_dev, returns (berr[nrhs], steps, solves[nrhs])."""
+        opt = _gmres_opt(method, restart, inner_tol, max_solves)
+        if opt is not None:
+            return _gsrfs3d_gmres_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans, opt)
         return _gsrfs3d_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans)
 
     pzgsrfs3d_dev = pdgsrfs3d_dev
@@ -520,6 +529,54 @@ def _gsrfs3d_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans="N"):
     name = "sluamd_pzgsrfs3d_dev" if z else "sluamd_pdgsrfs3d_dev"
     _lib.check(_lib.entry(name)(h, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), _pd(berr), C.byref(steps)), name)
     return berr[:int(nrhs)], steps.value
+
+
+def _gmres_opt(method, restart, inner_tol, max_solves):
+    """None for method="plain"; else sluamd_gmres_t with the library's defaults where an argument is None.  ValueError: another method, options without
+    method="gmres".  (The ranges are the library's to check: SLUAMD_EINVAL -> RuntimeError.)"""
+    if method == "plain":
+        if restart is not None or inner_tol is not None or max_solves is not None:
+            raise ValueError("restart, inner_tol and max_solves belong to method='gmres'")
+        return None
+    if method != "gmres":
+        raise ValueError(f"method must be 'plain' or 'gmres', not {method!r}")
+    from ._lib import Gmres
+    o = Gmres()
+    _lib.entry("sluamd_default_gmres")(C.byref(o))
+    if restart is not None:
+        o.restart = int(restart)
+    if inner_tol is not None:
+        o.inner_tol = float(inner_tol)
+    if max_solves is not None:
+        o.max_solves = int(max_solves)
+    return o
+
+
+def _gsrfs3d_gmres(h, z, b, x, trans, n, opt):
+    t = _trans_code(trans)
+    dt = np.complex128 if z else np.float64
+    for what, a in (("b", b), ("x", x)):
+        if np.asarray(a).dtype != np.dtype(dt):
+            raise ValueError(f"pdgsrfs3d(method='gmres'): the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
+    if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
+        raise ValueError(f"pdgsrfs3d(method='gmres'): b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
+    b = np.asfortranarray(np.array(b, dtype=dt)); x = np.asfortranarray(np.array(x, dtype=dt))
+    if b.ndim == 1:
+        b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
+    nrhs = b.shape[1]
+    berr = np.zeros(max(nrhs, 1)); steps = C.c_int32(0); solves = np.zeros(max(nrhs, 1), dtype=np.int32)
+    name = "sluamd_pzgsrfs3d_gmres" if z else "sluamd_pdgsrfs3d_gmres"
+    _lib.check(_lib.entry(name)(h, t, b.ctypes.data_as(C.c_void_p), max(b.shape[0], 1), x.ctypes.data_as(C.c_void_p), max(x.shape[0], 1), nrhs, C.byref(opt), _pd(berr),
+                                C.byref(steps), _pi(solves)), name)
+    return x, berr[:nrhs], steps.value, solves[:nrhs]
+
+
+def _gsrfs3d_gmres_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans, opt):
+    t = _trans_code(trans)
+    berr = np.zeros(max(int(nrhs), 1)); steps = C.c_int32(0); solves = np.zeros(max(int(nrhs), 1), dtype=np.int32)
+    name = "sluamd_pzgsrfs3d_gmres_dev" if z else "sluamd_pdgsrfs3d_gmres_dev"
+    _lib.check(_lib.entry(name)(h, t, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), C.byref(opt), _pd(berr), C.byref(steps), _pi(solves)), name)
+    return berr[:int(nrhs)], steps.value, solves[:int(nrhs)]
 
 
 EQUED = "NRCB"      # SLUAMD_EQUED_N / _R / _C / _B
@@ -665,7 +722,15 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
     grid=(Pr, Pc, Pz): the same on a process grid whose ranks are threads of this process over the in-process transport (grid3d.local_comms) -- every
     rank holds the complete matrix and b, the calls are collective (replicated forms), rank 0's x, info and stats are returned; trans, equil and refine
     as above; keep and rowperm are not part of this form (ValueError).
+    refine="gmres": the refinement is the GMRES one (LUHandle.pdgsrfs3d(method="gmres")); `refine_solves` joins `berr` and `refine_steps` in the stats.
+    With equil=True the solve runs with refine=0 and the SCALED system is refined: b' = R o b, x' = x / C, then x = C o x'.  Not with grid or rowperm
+    (ValueError).
     Returns (x, info, stats[, handle, symb])."""
+    gmres = isinstance(refine, str)
+    if gmres and refine != "gmres":
+        raise ValueError(f"refine must be False, True or 'gmres', not {refine!r}")
+    if gmres and ((grid is not None and tuple(grid) != (1, 1, 1)) or rowperm is not None):
+        raise ValueError("refine='gmres' is not part of the grid and rowperm forms of this driver -- keep the handle and call LUHandle.pdgsrfs3d(method='gmres')")
     if refine and _trans_code(trans):
         raise ValueError("refine=True with trans != 'N': not in this driver -- solve with refine=False and keep=True, then refine with "
                          "LUHandle.pdgsrfs3d(b, x, trans=...) on the attached matrix")
@@ -693,8 +758,11 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
     st = h.stats()
     if refine:
         h.attach_matrix(n, rowptr, colind, nzval, symb.perm_c)
-        x, berr, steps = h.pdgsrfs3d(b, x)
-        st["berr"] = berr; st["refine_steps"] = steps
+        if gmres:
+            x, st["berr"], st["refine_steps"], st["refine_solves"] = h.pdgsrfs3d(b, x, method="gmres")
+        else:
+            x, berr, steps = h.pdgsrfs3d(b, x)
+            st["berr"] = berr; st["refine_steps"] = steps
     if keep:
         return x, info, st, h, symb
     h.destroy(); symb.free()
@@ -789,13 +857,19 @@ def _gssvx3d_equil(h, symb, n, rowptr, colind, nzval, b, keep, refine, trans):
     """the Equil = YES path of pdgssvx3d: equilibrate on the device, thresh from the scaled matrix's 1-norm, factor, expert solve"""
     eq = h.equilibrate(n, rowptr, colind, nzval, symb.perm_c)
     info = h.pdgstrf3d(0.5 * float(np.finfo(np.float32).eps) * eq["anorm"])
-    out = h.gssvx_solve(b, trans=trans, refine=refine)
+    gmres = refine == "gmres"
+    out = h.gssvx_solve(b, trans=trans, refine=refine and not gmres)
     st = h.stats()
     st.update(equed=eq["equed"], rowcnd=eq["rowcnd"], colcnd=eq["colcnd"], amax=eq["amax"])
     if eq["info"] > 0:
         st["equil_info"] = eq["info"]
     x = out
-    if refine:
+    if gmres:                                                   # the attached matrix is the scaled one, R A C: refine (R A C) x' = R o b, x = C o x'
+        r, c = h.scalings()
+        bs = np.asfortranarray(np.array(b, dtype=x.dtype).reshape(x.shape) * r[:, None])
+        xs, st["berr"], st["refine_steps"], st["refine_solves"] = h.pdgsrfs3d(bs, np.asfortranarray(x / c[:, None]), method="gmres")
+        x = np.asfortranarray(xs * c[:, None])
+    elif refine:
         x, st["berr"], st["refine_steps"] = out
     if keep:
         return x, info, st, h, symb
