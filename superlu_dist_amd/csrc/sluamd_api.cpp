@@ -510,24 +510,16 @@ extern "C" int sluamd_dAttachMatrix(sluamd_handle_t h, sluamd_int_t n, const slu
     return attach_rfs(h, n, rowptr, colind, nzval, perm_c, false, "sluamd_dAttachMatrix");
 }
 
-// the double kernels of the refinement driver (DRfs: sluamd_refine.h)
-void DRfs::residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
-{
-    eng::rfs_residual(s, (int) H->hs.n, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
-}
-void DRfs::update(hipStream_t s, const Handle *H, const double *dx_perm, double *x) { eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x); }
-int DRfs::solve(Handle *H, double *r_perm, int n) { return run_solve_dev(H, r_perm, n, 1); }
-
 extern "C" {
 
 int sluamd_pdgsrfs3d_dev(sluamd_handle_t h, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    return rfs_entry<DRfs>(h, d_B, ldb, d_X, ldx, nrhs, berr, steps, false, "sluamd_pdgsrfs3d_dev");
+    return rfs_entry<Rfs<false, 0>>(h, d_B, ldb, d_X, ldx, nrhs, berr, steps, false, "sluamd_pdgsrfs3d_dev");
 }
 
 int sluamd_pdgsrfs3d(sluamd_handle_t h, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    return rfs_entry<DRfs>(h, B, ldb, X, ldx, nrhs, berr, steps, true, "sluamd_pdgsrfs3d");
+    return rfs_entry<Rfs<false, 0>>(h, B, ldb, X, ldx, nrhs, berr, steps, true, "sluamd_pdgsrfs3d");
 }
 
 void sluamd_dDestroyLUHandle(sluamd_handle_t h)

@@ -152,9 +152,8 @@ int solve_dev(sluamd_batch_t b, int trans, const double *B, int64_t ldb, int64_t
     // a foreign block-diagonal one), the correction by the transposed sweeps on r_perm, the same permutation on both sides
     const bool tr = trans != SLUAMD_NOTRANS, conj = z && trans == SLUAMD_CONJ;
     if (tr) { if (int rc = ensure_tindex(H, z ? "sluamd_zBatchSolve" : "sluamd_dBatchSolve")) return rc; }
-    const int ITMAX = 20;
-    const double eps = 0x1p-53, safmin = 2.2250738585072014e-308;
-    const double safe1 = (double) (m + 1) * safmin, safe2 = safe1 / eps;
+    const RfsGuards g = rfs_guards(m);
+    const RfsMat A = rfs_mat(H, tr);
     double *r_perm = H->d_rfs_work.p;
     std::vector<double> sv(count), lstres(count);
     std::vector<int> cnt(count), go(count), live(count);
@@ -164,8 +163,7 @@ int solve_dev(sluamd_batch_t b, int trans, const double *B, int64_t ldb, int64_t
         std::fill(lstres.begin(), lstres.end(), 3.0); std::fill(cnt.begin(), cnt.end(), 0); std::fill(live.begin(), live.end(), 1);
         for (;;) {
             HIPCHK(hipMemsetAsync(b->d_s.p, 0, sizeof(unsigned long long) * count, s));
-            if (tr) beng::batch_residual_t(s, z, conj, n, m, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, Xc, strideX, Bc, sB, H->d_rfs_pc.p, r_perm, b->d_s.p, safe1, safe2);
-            else beng::batch_residual(s, z, n, m, H->d_rfs_rp.p, H->d_rfs_ci.p, H->d_rfs_av.p, Xc, strideX, Bc, sB, H->d_rfs_pc.p, r_perm, b->d_s.p, safe1, safe2);
+            beng::batch_residual(s, z, conj, A, m, Xc, strideX, Bc, sB, r_perm, b->d_s.p, g.safe1, g.safe2);
             HIPCHK(hipMemcpyAsync(sv.data(), b->d_s.p, sizeof(double) * count, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             int any = 0;
@@ -173,7 +171,7 @@ int solve_dev(sluamd_batch_t b, int trans, const double *B, int64_t ldb, int64_t
                 go[k] = 0;
                 if (!live[k]) continue;
                 berr[(size_t) k * nrhs + j] = sv[k];
-                go[k] = (sv[k] > eps && sv[k] * 2 <= lstres[k] && cnt[k] < ITMAX) ? 1 : 0;
+                go[k] = rfs_continue(sv[k], lstres[k], cnt[k]) ? 1 : 0;
                 if (!go[k]) live[k] = 0;
                 any |= go[k];
             }

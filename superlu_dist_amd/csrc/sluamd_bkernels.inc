@@ -8,6 +8,8 @@
 // R and C and the backward errors are real.  The complex moduli are those of the single-matrix kernels: abs1(z) = |re| + |im| wherever the reference uses
 // slud_z_abs1 (refinement; the equilibration's maxima come from eng::eq_rowmax / eq_colmax themselves), hypot for the 1-norm (k_eq_scale_norm).
 
+#include "sluamd_rkernels.inc"   // rfs_row, rfs_add: the refinement arithmetic of the single-matrix kernels
+
 typedef double2 bzc;
 template <bool Z> struct BVal { typedef double T; };
 template <> struct BVal<true> { typedef bzc T; };
@@ -161,108 +163,32 @@ __device__ __forceinline__ void bk_berr_max(int k, double q, unsigned long long 
     }
 }
 
-// The twin of k_rfs_residual / k_zrfs_residual on the attached block-diagonal CSR: r_perm[pc[g]] = b - A x for global row g = k m + i, x and b read from
-// matrix k's own block (x = X_k[:, j] at xs + k stridex, b likewise), the backward error of the row maximised into s_out[k].  The arithmetic per row is the
-// expression and order of the single-matrix kernels: a batch is bitwise one matrix alone.
-template <bool Z>
-__global__ __launch_bounds__(256) void k_batch_residual(int64_t n, int m, const int *__restrict__ rp, const int *__restrict__ ci,
+// k_rfs_residual<V, TRANS, CONJ> on the attached block-diagonal matrix: one thread per global row g = k m + i of op(A), (ptr, idx, pos) its CSR or (TRANS) its
+// transposed index over GLOBAL rows and columns, x and b read from matrix k's own block (x = X_k[:, j] at xs + k stridex, b likewise),
+// r_perm[pc[g]] = b_i - sum_e op(a_e) x_k[idx[e] - k m], the backward error of the row maximised into s_out[k].  The row is rfs_row (sluamd_rkernels.inc), the
+// text the single-matrix kernels run: a batch is bitwise one matrix alone.
+template <bool Z, bool TRANS, bool CONJ>
+__global__ __launch_bounds__(256) void k_batch_residual(int64_t n, int m, const int *__restrict__ ptr, const int *__restrict__ idx, const int *__restrict__ pos,
                                                         const typename BVal<Z>::T *__restrict__ av, const typename BVal<Z>::T *__restrict__ xs, int64_t stridex,
                                                         const typename BVal<Z>::T *__restrict__ bs, int64_t strideb, const int *__restrict__ pc,
                                                         typename BVal<Z>::T *__restrict__ r_perm, unsigned long long *__restrict__ s_out, double safe1, double safe2)
 {
+    typedef typename BVal<Z>::T V;
     const int64_t g = (int64_t) blockIdx.x * 256 + threadIdx.x;
     double q = 0.0;
     int k = -1;
     if (g < n) {
         k = (int) (g / m);
         const int i = (int) (g - (int64_t) k * m);
-        const auto *x = xs + (int64_t) k * stridex - (int64_t) k * m;     // indexed by the global column
-        const auto bi = bs[(int64_t) k * strideb + i];
-        if constexpr (Z) {
-            double axr = 0.0, axi = 0.0, t = 0.0;
-            for (int e = rp[g]; e < rp[g + 1]; ++e) {
-                const bzc a = av[e], xv = x[ci[e]];
-                axr += a.x * xv.x - a.y * xv.y;
-                axi += a.x * xv.y + a.y * xv.x;
-                t += (fabs(a.x) + fabs(a.y)) * (fabs(xv.x) + fabs(xv.y));
-            }
-            const bzc r = make_double2(bi.x - axr, bi.y - axi);
-            t += fabs(bi.x) + fabs(bi.y);
-            r_perm[pc[g]] = r;
-            const double ar = fabs(r.x) + fabs(r.y);
-            if (t > safe2) q = ar / t;
-            else if (t != 0.0) q = (safe1 + ar) / t;
-        } else {
-            double ax = 0.0, t = 0.0;
-            for (int e = rp[g]; e < rp[g + 1]; ++e) {
-                const double a = av[e], xv = x[ci[e]];
-                ax += a * xv;
-                t += fabs(a) * fabs(xv);
-            }
-            const double r = bi - ax;
-            t += fabs(bi);
-            r_perm[pc[g]] = r;
-            if (t > safe2) q = fabs(r) / t;
-            else if (t != 0.0) q = (safe1 + fabs(r)) / t;
-        }
+        const V *x = xs + (int64_t) k * stridex - (int64_t) k * m;     // indexed by the global column (TRANS: row)
+        V r;
+        q = rfs_row<V, CONJ, TRANS>(ptr[g], ptr[g + 1], idx, pos, av, x, bs[(int64_t) k * strideb + i], safe1, safe2, r);
+        r_perm[pc[g]] = r;
     }
     bk_berr_max(k, q, s_out);
 }
 
-// The twin of k_rfs_residual_t / kz_rfs_residual_t<CONJ> over the transposed index of the attached block-diagonal matrix (tcp[n + 1] column pointers, per entry
-// in column order -- rows ascending inside a column, so every sum has a fixed order -- tri[e] its global row and tpos[e] its position in the CSR value array;
-// the values are not copied).  One thread per global column g = k m + j = row j of op(A_k):
-//   r_perm[pc[g]] = b_j - sum_e op(av[tpos[e]]) x[tri[e]],      op = identity, or the conjugate (CONJ, complex16 only: A^H x = b)
-// with x and b read from matrix k's own block and the backward error maximised into s_out[k] as above.  The expressions and their order are those of the
-// single-matrix kernels.  One more dependent gather than the CSR pass (8 B of index + a scattered value per entry); a step reads the factors beside it.
-template <bool Z, bool CONJ>
-__global__ __launch_bounds__(256) void k_batch_residual_t(int64_t n, int m, const int *__restrict__ tcp, const int *__restrict__ tri, const int *__restrict__ tpos,
-                                                          const typename BVal<Z>::T *__restrict__ av, const typename BVal<Z>::T *__restrict__ xs, int64_t stridex,
-                                                          const typename BVal<Z>::T *__restrict__ bs, int64_t strideb, const int *__restrict__ pc,
-                                                          typename BVal<Z>::T *__restrict__ r_perm, unsigned long long *__restrict__ s_out, double safe1, double safe2)
-{
-    const int64_t g = (int64_t) blockIdx.x * 256 + threadIdx.x;
-    double q = 0.0;
-    int k = -1;
-    if (g < n) {
-        k = (int) (g / m);
-        const int j = (int) (g - (int64_t) k * m);
-        const auto *x = xs + (int64_t) k * stridex - (int64_t) k * m;     // indexed by the global row
-        const auto bj = bs[(int64_t) k * strideb + j];
-        if constexpr (Z) {
-            double axr = 0.0, axi = 0.0, t = 0.0;
-            for (int e = tcp[g]; e < tcp[g + 1]; ++e) {
-                bzc a = av[tpos[e]];
-                const bzc xv = x[tri[e]];
-                if (CONJ) a.y = -a.y;
-                axr += a.x * xv.x - a.y * xv.y;
-                axi += a.x * xv.y + a.y * xv.x;
-                t += (fabs(a.x) + fabs(a.y)) * (fabs(xv.x) + fabs(xv.y));
-            }
-            const bzc r = make_double2(bj.x - axr, bj.y - axi);
-            t += fabs(bj.x) + fabs(bj.y);
-            r_perm[pc[g]] = r;
-            const double ar = fabs(r.x) + fabs(r.y);
-            if (t > safe2) q = ar / t;
-            else if (t != 0.0) q = (safe1 + ar) / t;
-        } else {
-            double ax = 0.0, t = 0.0;
-            for (int e = tcp[g]; e < tcp[g + 1]; ++e) {
-                const double a = av[tpos[e]], xv = x[tri[e]];
-                ax += a * xv;
-                t += fabs(a) * fabs(xv);
-            }
-            const double r = bj - ax;
-            t += fabs(bj);
-            r_perm[pc[g]] = r;
-            if (t > safe2) q = fabs(r) / t;
-            else if (t != 0.0) q = (safe1 + fabs(r)) / t;
-        }
-    }
-    bk_berr_max(k, q, s_out);
-}
-
-// masked twin of k_rfs_update / k_zrfs_update: X_k[i] += dx_perm[pc[k m + i]] for the matrices that continue (go[k] != 0)
+// masked k_rfs_update: X_k[i] += dx_perm[pc[k m + i]] for the matrices that continue (go[k] != 0)
 template <bool Z>
 __global__ __launch_bounds__(256) void k_batch_update(int64_t n, int m, const int *__restrict__ pc, const int *__restrict__ go,
                                                       const typename BVal<Z>::T *__restrict__ dx_perm, typename BVal<Z>::T *__restrict__ xs, int64_t stridex)
@@ -272,14 +198,9 @@ __global__ __launch_bounds__(256) void k_batch_update(int64_t n, int m, const in
     const int k = (int) (g / m);
     if (!go[k]) return;
     auto *p = xs + (int64_t) k * stridex + (g - (int64_t) k * m);
-    if constexpr (Z) {
-        const bzc d = dx_perm[pc[g]];
-        bzc v = *p;
-        v.x += d.x; v.y += d.y;
-        *p = v;
-    } else {
-        *p += dx_perm[pc[g]];
-    }
+    auto v = *p;
+    rfs_add(v, dx_perm[pc[g]]);
+    *p = v;
 }
 
 namespace sluamd { namespace beng {
@@ -349,22 +270,20 @@ void batch_info(hipStream_t s, bool z, int64_t ncol, int m, const int64_t *dpos,
     else hipLaunchKernelGGL(k_batch_info<double>, batch_rows(ncol), dim3(256), 0, s, ncol, m, dpos, BDC(val), info);
 }
 
-void batch_residual(hipStream_t s, bool z, int64_t n, int m, const int *rp, const int *ci, const void *av, const void *xs, int64_t stridex, const void *bs,
-                    int64_t strideb, const int *pc, void *r_perm, unsigned long long *s_out, double safe1, double safe2)
+// A: rfs_mat() of the batch's handle (A.pos: the transposed index); conj is read on that complex16 form only: the conjugate of a real matrix is itself
+void batch_residual(hipStream_t s, bool z, bool conj, const RfsMat &A, int m, const void *xs, int64_t stridex, const void *bs, int64_t strideb, void *r_perm,
+                    unsigned long long *s_out, double safe1, double safe2)
 {
-    if (n <= 0) return;
-    if (z) hipLaunchKernelGGL(k_batch_residual<true>, batch_rows(n), dim3(256), 0, s, n, m, rp, ci, BZC(av), BZC(xs), stridex, BZC(bs), strideb, pc, BZ(r_perm), s_out, safe1, safe2);
-    else hipLaunchKernelGGL(k_batch_residual<false>, batch_rows(n), dim3(256), 0, s, n, m, rp, ci, BDC(av), BDC(xs), stridex, BDC(bs), strideb, pc, BD(r_perm), s_out, safe1, safe2);
-}
-
-// conj is read on complex16 only: the conjugate of a real matrix is itself
-void batch_residual_t(hipStream_t s, bool z, bool conj, int64_t n, int m, const int *tcp, const int *tri, const int *tpos, const void *av, const void *xs,
-                      int64_t stridex, const void *bs, int64_t strideb, const int *pc, void *r_perm, unsigned long long *s_out, double safe1, double safe2)
-{
-    if (n <= 0) return;
-    if (z && conj) hipLaunchKernelGGL((k_batch_residual_t<true, true>), batch_rows(n), dim3(256), 0, s, n, m, tcp, tri, tpos, BZC(av), BZC(xs), stridex, BZC(bs), strideb, pc, BZ(r_perm), s_out, safe1, safe2);
-    else if (z) hipLaunchKernelGGL((k_batch_residual_t<true, false>), batch_rows(n), dim3(256), 0, s, n, m, tcp, tri, tpos, BZC(av), BZC(xs), stridex, BZC(bs), strideb, pc, BZ(r_perm), s_out, safe1, safe2);
-    else hipLaunchKernelGGL((k_batch_residual_t<false, false>), batch_rows(n), dim3(256), 0, s, n, m, tcp, tri, tpos, BDC(av), BDC(xs), stridex, BDC(bs), strideb, pc, BD(r_perm), s_out, safe1, safe2);
+    if (A.n <= 0) return;
+#define BATCH_RESIDUAL(Z, TRANS, CONJ)                                                                                                                  \
+    hipLaunchKernelGGL((k_batch_residual<Z, TRANS, CONJ>), batch_rows(A.n), dim3(256), 0, s, A.n, m, A.ptr, A.idx, A.pos,                               \
+                       reinterpret_cast<const typename BVal<Z>::T *>(A.av), reinterpret_cast<const typename BVal<Z>::T *>(xs), stridex,                 \
+                       reinterpret_cast<const typename BVal<Z>::T *>(bs), strideb, A.pc, reinterpret_cast<typename BVal<Z>::T *>(r_perm), s_out, safe1, safe2)
+    if (!z) { if (A.pos) BATCH_RESIDUAL(false, true, false); else BATCH_RESIDUAL(false, false, false); }
+    else if (!A.pos) BATCH_RESIDUAL(true, false, false);
+    else if (conj) BATCH_RESIDUAL(true, true, true);
+    else BATCH_RESIDUAL(true, true, false);
+#undef BATCH_RESIDUAL
 }
 
 void batch_update(hipStream_t s, bool z, int64_t n, int m, const int *pc, const int *go, const void *dx_perm, void *xs, int64_t stridex)

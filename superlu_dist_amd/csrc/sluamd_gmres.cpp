@@ -151,9 +151,7 @@ template <class K> int gmres_dev(sluamd_handle_t h, const double *d_B, int64_t l
     if (int rc = ensure_work(H, o.restart, K::z, W)) return rc;
     const int vs = K::z ? 2 : 1;
     const int n = (int) H->hs.n;
-    const int ITMAX = 20;
-    const double eps = 0x1p-53, safmin = 2.2250738585072014e-308;
-    const double safe1 = (double) (n + 1) * safmin, safe2 = safe1 / eps;
+    const RfsGuards g = rfs_guards(n);
     hipStream_t s = H->stream;
     int count = 0;
     for (int j = 0; j < nrhs; ++j) {
@@ -164,14 +162,14 @@ template <class K> int gmres_dev(sluamd_handle_t h, const double *d_B, int64_t l
         count = 0;
         for (;;) {
             HIPCHK(hipMemsetAsync(H->d_rfs_s.p, 0, sizeof(unsigned long long), s));
-            K::residual(s, H, Xc, Bc, W.w, safe1, safe2);
+            K::residual(s, H, Xc, Bc, W.w, g.safe1, g.safe2);
             double sv = 0.0;
             HIPCHK(hipMemcpyAsync(&sv, H->d_rfs_s.p, sizeof(double), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             berr[j] = sv;
-            if (!(sv > eps && sv * 2 <= lstres && count < ITMAX && solves < o.max_solves)) break;
+            if (!(rfs_continue(sv, lstres, count) && solves < o.max_solves)) break;
             // one application left: a cycle needs two (an iteration and the end of the cycle), so the step is the plain one
-            const int rc = o.max_solves - solves < 2 ? 1 : gmres_cycle<K>(H, W, o, Xc, safe1, safe2, solves);
+            const int rc = o.max_solves - solves < 2 ? 1 : gmres_cycle<K>(H, W, o, Xc, g.safe1, g.safe2, solves);
             if (rc < 0) return rc;
             if (rc == 2) break;
             if (rc == 1) {
@@ -226,14 +224,12 @@ int gmres_entry(sluamd_handle_t h, int trans, const void *Bv, int64_t ldb, void 
     Handle *H = &h->H;
     if (H->grid.size() > 1) { set_error(me + "the GMRES refinement needs a 1 x 1 x 1 handle (grid handles refine with sluamd_p[dz]gsrfs3d[_trans])"); return SLUAMD_EINVAL; }
     if (H->batch_owned) { set_error(me + "the handle belongs to a batch (sluamd_BatchHandle): the GMRES refinement does not run on batches"); return SLUAMD_EINVAL; }
-    if (int rc = z ? rfs_checks<ZRfs>(H) : rfs_checks<DRfs>(H)) return rc;
+    if (int rc = z ? rfs_checks<Rfs<true, 0>>(H) : rfs_checks<Rfs<false, 0>>(H)) return rc;
     if (nrhs == 0) { if (steps) *steps = 0; return 0; }
     if (trans != SLUAMD_NOTRANS) { if (int rc = ensure_tindex(H, name)) return rc; }
     const double *B = static_cast<const double *>(Bv);
     double *X = static_cast<double *>(Xv);
-    auto run = [&](auto K) { return host ? gmres_host<decltype(K)>(h, B, ldb, X, ldx, nrhs, o, berr, steps, solves) : gmres_dev<decltype(K)>(h, B, ldb, X, ldx, nrhs, o, berr, steps, solves); };
-    if (trans == SLUAMD_NOTRANS) return z ? run(ZRfs()) : run(DRfs());
-    return !z ? run(TRfs<false, false>()) : trans == SLUAMD_CONJ ? run(TRfs<true, true>()) : run(TRfs<true, false>());
+    return rfs_dispatch(z, trans, [&](auto K) { return host ? gmres_host<decltype(K)>(h, B, ldb, X, ldx, nrhs, o, berr, steps, solves) : gmres_dev<decltype(K)>(h, B, ldb, X, ldx, nrhs, o, berr, steps, solves); });
 }
 
 }  // namespace

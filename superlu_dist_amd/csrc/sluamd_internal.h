@@ -7,6 +7,7 @@
 // orchestration (Z forests, XY block-cyclic panel exchange) is covered by `-m "not gpu"` tests; the product library has
 // no CPU path.
 #pragma once
+#include <cassert>
 #include <cstdint>
 #include <map>
 #include <string>
@@ -438,6 +439,17 @@ struct Handle {
     DevBuf<double> d_bloc;                            // the caller's local rows of B on the device
 };
 
+// The matrix of a refinement residual as its kernels read it: row i of op(A) is the entries [ptr[i], ptr[i + 1]), entry e multiplies x[idx[e]] and its value
+// is av[e] (pos null: the attached CSR itself) or av[pos[e]] (the transposed index of ensure_tindex: no second copy of the values).  av in doubles, two per
+// value on a complex16 handle
+struct RfsMat { int64_t n; const int *ptr, *idx, *pos; const double *av; const int *pc; };
+inline RfsMat rfs_mat(const Handle *H, bool trans)
+{
+    assert(!trans || H->d_rfs_tpos.p);      // ensure_tindex first: without the index the entries would take the descriptor for the CSR and compute A x, not op(A) x
+    if (trans) return {H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, H->d_rfs_pc.p};
+    return {H->hs.n, H->d_rfs_rp.p, H->d_rfs_ci.p, nullptr, H->d_rfs_av.p, H->d_rfs_pc.p};
+}
+
 // ------------------------------------------------------------------------------------------------
 // Engine: every device operation of the hot path.  sluamd_kernels.hip implements these as gfx950 kernel launches on
 // `s`; all pointer arguments are device pointers.
@@ -497,6 +509,13 @@ void sweep_join(hipStream_t s, bool lower, const DevTables &T, const int4 *jrecs
 // x[rows of the supernodes `nodes`] = 0 (all right-hand sides)
 void zero_nodes(hipStream_t s, const DevTables &T, const int *nodes, int nn, double *x, int64_t ldx, int nrhs);
 void scatter_values(hipStream_t s, double *val, const int64_t *pos, const double *a, int64_t nnz);
+// iterative refinement (sluamd_rkernels.inc), every form behind two entries.  z: interleaved doublecomplex values, x, b, r_perm, dx_perm (the double pointers
+// count two doubles per value then); A: rfs_mat() of the handle -- the attached CSR, or its transposed index for op(A) = A^T, and with conj (read on that
+// complex16 form only) A^H.  r_perm[pc[i]] = b_i - sum over row i of op(A) of a x, *s_out = max(*s_out, berr bits); x[i] += dx_perm[pc[i]].
+void rfs_residual(hipStream_t s, bool z, bool conj, const RfsMat &A, const double *x, const double *b, double *r_perm, unsigned long long *s_out, double safe1, double safe2);
+void rfs_update(hipStream_t s, bool z, int n, const int *pc, const double *dx_perm, double *x);
+// The double A x = b form under the flat signature that the CPU test build restates (oracle/emul/engine_cpu.cpp knows this pair and no other): the policy
+// Rfs<false, 0> calls it, so the host sources link against that engine unchanged; here it forwards to the two entries above
 void rfs_residual(hipStream_t s, int n, const int *rp, const int *ci, const double *av, const double *x, const double *b, const int *pc,
                   double *r_perm, unsigned long long *s_out, double safe1, double safe2);
 void rfs_update(hipStream_t s, int n, const int *pc, const double *dx_perm, double *x);
@@ -527,11 +546,6 @@ void zbwd_update(hipStream_t s, const DevTables &T, const int *nodes, const int 
 void zsweep_fused(hipStream_t s, bool lower, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, void *w, int64_t ldx, int nrhs,
                   int max_nsupc, int *tickets);
 void zscatter_values(hipStream_t s, void *val, const int64_t *pos, const void *a, int64_t nnz);
-// iterative refinement (pzgsrfs3d): the twins of rfs_residual / rfs_update on interleaved doublecomplex values, x, b, r_perm, dx_perm.
-// Referenced only by sluamd_zrefine.cpp (the CPU test build of the host sources has no restatement of them)
-void zrfs_residual(hipStream_t s, int n, const int *rp, const int *ci, const void *av, const void *x, const void *b, const int *pc,
-                   void *r_perm, unsigned long long *s_out, double safe1, double safe2);
-void zrfs_update(hipStream_t s, int n, const int *pc, const void *dx_perm, void *x);
 // transposed / conjugate-transposed sweeps on a 1 x 1 x 1 handle, in place in ONE vector (sluamd_tkernels.inc).  Referenced only by sluamd_tsolve.cpp (the CPU
 // test build of the host sources has no restatement of them).  `upper`: the U^T step (forward sweep) -- y_k = Uinv_k^T x_k, complex16: substitution on U_kk^T
 // (conj: its conjugate) -- else the L^T step (backward sweep).  fwd_update_t: x[gc] -= U_k[:, c]^T y_k, units = (supernode, chunk of 64 non-empty columns) of
@@ -543,13 +557,6 @@ void bwd_update_t(hipStream_t s, const DevTables &T, const int *nodes, const int
 void zsolve_diag_t(hipStream_t s, bool upper, bool conj, const DevTables &T, const int *nodes, int nn, void *x, int64_t ldx, int nrhs, int max_nsupc);
 void zfwd_update_t(hipStream_t s, bool conj, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, int64_t ldx, int nrhs, int max_nsupc);
 void zbwd_update_t(hipStream_t s, bool conj, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, void *x, int64_t ldx, int nrhs);
-// residual + backward error of the transposed (conj: conjugate-transposed) refinement over the transposed index of the attached matrix (sluamd_rkernels.inc):
-// r_perm[pc[j]] = b_j - sum over column j of op(av[tpos[e]]) x[tri[e]].  Referenced only by sluamd_trefine.cpp (the CPU test build of the host sources has no
-// restatement of them).  The updates are rfs_update / zrfs_update
-void rfs_residual_t(hipStream_t s, int n, const int *tcp, const int *tri, const int *tpos, const double *av, const double *x, const double *b, const int *pc,
-                    double *r_perm, unsigned long long *s_out, double safe1, double safe2);
-void zrfs_residual_t(hipStream_t s, bool conj, int n, const int *tcp, const int *tri, const int *tpos, const void *av, const void *x, const void *b, const int *pc,
-                     void *r_perm, unsigned long long *s_out, double safe1, double safe2);
 // equilibration on the attached CSR copy of A (sluamd_ekernels.inc; z: doublecomplex values).  Referenced only by sluamd_equil.cpp (the CPU test build of the
 // host sources has no restatement of them).  red: three 64-bit words {min bits, max bits, first index whose value is exactly 0}, set to {~0, 0, ~0} before
 // eq_rowmax / eq_reduce; eq_colmax needs c zero-filled, eq_scale_norm colsum zero-filled; mode bit 0: scale by r[i], bit 1: by c[j] (in that order)

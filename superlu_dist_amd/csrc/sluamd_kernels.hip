@@ -1312,51 +1312,6 @@ __global__ __launch_bounds__(256) void k_full_inv64(DevTables T, const int *__re
         }
 }
 
-// ---- iterative refinement (pdgsrfs3d, SRC/double/pdgsrfs.c:345-510) --------------------------------
-// One pass over the CSR matrix does both of the reference's pdgsmv calls (abs = 0 and abs = 1, pdgsmv.c): residual
-// r = b - A x (stored permuted, r_perm[perm_c[i]] = r_i: the right-hand side of the triangular solves on Pc A Pc^T),
-// temp = |A||x| + |b|, and the componentwise backward error max_i |r_i| / temp_i with the SAFE1/SAFE2 guards
-// (:463-469), reduced per workgroup and combined with an integer atomicMax (non-negative doubles order like
-// their bit patterns).  HBM-bound: 12 B per nonzero + 32 B per row.
-__global__ __launch_bounds__(256) void k_rfs_residual(int n, const int *__restrict__ rp, const int *__restrict__ ci,
-                                                      const double *__restrict__ av, const double *__restrict__ x,
-                                                      const double *__restrict__ b, const int *__restrict__ pc,
-                                                      double *__restrict__ r_perm, unsigned long long *__restrict__ s_out,
-                                                      double safe1, double safe2)
-{
-    __shared__ double red[4];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    double q = 0.0;
-    if (i < n) {
-        double ax = 0.0, t = 0.0;
-        for (int e = rp[i]; e < rp[i + 1]; ++e) {
-            const double a = av[e], xv = x[ci[e]];
-            ax += a * xv;
-            t += fabs(a) * fabs(xv);
-        }
-        const double r = b[i] - ax;
-        t += fabs(b[i]);
-        r_perm[pc[i]] = r;
-        if (t > safe2) q = fabs(r) / t;
-        else if (t != 0.0) q = (safe1 + fabs(r)) / t;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q = fmax(q, __shfl_xor(q, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = q;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        q = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-        atomicMax(s_out, (unsigned long long) __double_as_longlong(q));
-    }
-}
-
-__global__ __launch_bounds__(256) void k_rfs_update(int n, const int *__restrict__ pc, const double *__restrict__ dx_perm,
-                                                    double *__restrict__ x)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) x[i] += dx_perm[pc[i]];
-}
-
 // ---- Schur complement update: fused gather -> MFMA fp64 GEMM -> scatter ---------------------------
 // One workgroup (4 waves) per 64x64 tile of one (L block, U block) pair of one supernode of the level.
 // MFMA v_mfma_f64_16x16x4_f64 computes D[i][j] = sum_k A[i][k] B[k][j] with lane l holding
@@ -2921,7 +2876,7 @@ __global__ void k_mfma_selftest(const double *A, const double *B, double *D)
 #include "sluamd_ekernels.inc"   // equilibration, 1-norm, permute-and-scale of right-hand sides (sluamd_equil.cpp)
 #include "sluamd_pkernels.inc"   // RowPerm = LargeDiag_MC64: costs, duals, proposal rounds (sluamd_rowperm.cpp)
 #include "sluamd_ukernels.inc"   // same-pattern value updates (sluamd_update.cpp)
-#include "sluamd_rkernels.inc"   // residual / backward error of the transposed refinement (sluamd_trefine.cpp)
+#include "sluamd_rkernels.inc"   // iterative refinement: residual / backward error and update, every form (sluamd_refine.h)
 
 // ---- exchange helpers (XY block-cyclic layers, Z ancestor reduction, distributed solve) ---------------------------
 // y += a x : the daxpy of dzRecvLPanel / dzRecvUPanel (pd3dcomm.c:189-331) on a whole forest slice; HBM-bound, 24 B/element
@@ -3415,16 +3370,37 @@ void scatter_values(hipStream_t s, double *val, const int64_t *pos, const double
     if (nnz > 0) hipLaunchKernelGGL(k_scatter_values, dim3((unsigned) ((nnz + 255) / 256)), dim3(256), 0, s, val, pos, a, nnz);
 }
 
+// the twelve forms of the refinement kernels (sluamd_rkernels.inc) behind two entries: z picks the precision, A.pos the transposed index, conj (read on the
+// transposed complex16 form only) the conjugate
+void rfs_residual(hipStream_t s, bool z, bool conj, const RfsMat &A, const double *x, const double *b, double *r_perm, unsigned long long *s_out, double safe1, double safe2)
+{
+    if (A.n <= 0) return;
+    const int n = (int) A.n;
+    const dim3 grid((n + 255) / 256), block(256);
+#define RFS_RESIDUAL(V, TRANS, CONJ)                                                                                                                  \
+    hipLaunchKernelGGL((k_rfs_residual<V, TRANS, CONJ>), grid, block, 0, s, n, A.ptr, A.idx, A.pos, reinterpret_cast<const V *>(A.av),                \
+                       reinterpret_cast<const V *>(x), reinterpret_cast<const V *>(b), A.pc, reinterpret_cast<V *>(r_perm), s_out, safe1, safe2)
+    if (!z) { if (A.pos) RFS_RESIDUAL(double, true, false); else RFS_RESIDUAL(double, false, false); }
+    else if (!A.pos) RFS_RESIDUAL(zc, false, false);
+    else if (conj) RFS_RESIDUAL(zc, true, true);
+    else RFS_RESIDUAL(zc, true, false);
+#undef RFS_RESIDUAL
+}
+
+void rfs_update(hipStream_t s, bool z, int n, const int *pc, const double *dx_perm, double *x)
+{
+    if (n <= 0) return;
+    if (z) hipLaunchKernelGGL(k_rfs_update<zc>, dim3((n + 255) / 256), dim3(256), 0, s, n, pc, reinterpret_cast<const zc *>(dx_perm), reinterpret_cast<zc *>(x));
+    else hipLaunchKernelGGL(k_rfs_update<double>, dim3((n + 255) / 256), dim3(256), 0, s, n, pc, dx_perm, x);
+}
+
+// the flat double form of the CPU test build's engine
 void rfs_residual(hipStream_t s, int n, const int *rp, const int *ci, const double *av, const double *x, const double *b, const int *pc,
                   double *r_perm, unsigned long long *s_out, double safe1, double safe2)
 {
-    hipLaunchKernelGGL(k_rfs_residual, dim3((n + 255) / 256), dim3(256), 0, s, n, rp, ci, av, x, b, pc, r_perm, s_out, safe1, safe2);
+    rfs_residual(s, false, false, RfsMat{n, rp, ci, nullptr, av, pc}, x, b, r_perm, s_out, safe1, safe2);
 }
-
-void rfs_update(hipStream_t s, int n, const int *pc, const double *dx_perm, double *x)
-{
-    hipLaunchKernelGGL(k_rfs_update, dim3((n + 255) / 256), dim3(256), 0, s, n, pc, dx_perm, x);
-}
+void rfs_update(hipStream_t s, int n, const int *pc, const double *dx_perm, double *x) { rfs_update(s, false, n, pc, dx_perm, x); }
 
 void add_atomic(hipStream_t s, int64_t n, const double *x, double *y)
 {
@@ -3538,33 +3514,6 @@ void zbwd_update(hipStream_t s, const DevTables &T, const int *nodes, const int 
 void zscatter_values(hipStream_t s, void *val, const int64_t *pos, const void *a, int64_t nnz)
 {
     if (nnz > 0) hipLaunchKernelGGL(kz_scatter_values, dim3((unsigned) ((nnz + 255) / 256)), dim3(256), 0, s, reinterpret_cast<zc *>(val), pos, reinterpret_cast<const zc *>(a), nnz);
-}
-void zrfs_residual(hipStream_t s, int n, const int *rp, const int *ci, const void *av, const void *x, const void *b, const int *pc,
-                   void *r_perm, unsigned long long *s_out, double safe1, double safe2)
-{
-    if (n > 0)
-        hipLaunchKernelGGL(k_zrfs_residual, dim3((n + 255) / 256), dim3(256), 0, s, n, rp, ci, reinterpret_cast<const zc *>(av), reinterpret_cast<const zc *>(x),
-                           reinterpret_cast<const zc *>(b), pc, reinterpret_cast<zc *>(r_perm), s_out, safe1, safe2);
-}
-void zrfs_update(hipStream_t s, int n, const int *pc, const void *dx_perm, void *x)
-{
-    if (n > 0) hipLaunchKernelGGL(k_zrfs_update, dim3((n + 255) / 256), dim3(256), 0, s, n, pc, reinterpret_cast<const zc *>(dx_perm), reinterpret_cast<zc *>(x));
-}
-void rfs_residual_t(hipStream_t s, int n, const int *tcp, const int *tri, const int *tpos, const double *av, const double *x, const double *b, const int *pc,
-                    double *r_perm, unsigned long long *s_out, double safe1, double safe2)
-{
-    if (n > 0) hipLaunchKernelGGL(k_rfs_residual_t, dim3((n + 255) / 256), dim3(256), 0, s, n, tcp, tri, tpos, av, x, b, pc, r_perm, s_out, safe1, safe2);
-}
-void zrfs_residual_t(hipStream_t s, bool conj, int n, const int *tcp, const int *tri, const int *tpos, const void *av, const void *x, const void *b, const int *pc,
-                     void *r_perm, unsigned long long *s_out, double safe1, double safe2)
-{
-    if (n <= 0) return;
-    if (conj)
-        hipLaunchKernelGGL(kz_rfs_residual_t<true>, dim3((n + 255) / 256), dim3(256), 0, s, n, tcp, tri, tpos, reinterpret_cast<const zc *>(av),
-                           reinterpret_cast<const zc *>(x), reinterpret_cast<const zc *>(b), pc, reinterpret_cast<zc *>(r_perm), s_out, safe1, safe2);
-    else
-        hipLaunchKernelGGL(kz_rfs_residual_t<false>, dim3((n + 255) / 256), dim3(256), 0, s, n, tcp, tri, tpos, reinterpret_cast<const zc *>(av),
-                           reinterpret_cast<const zc *>(x), reinterpret_cast<const zc *>(b), pc, reinterpret_cast<zc *>(r_perm), s_out, safe1, safe2);
 }
 
 }  // namespace eng

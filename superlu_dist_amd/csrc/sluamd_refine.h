@@ -1,18 +1,18 @@
 // sluamd_refine.h -- internal: the iterative refinement driver of pdgsrfs3d (SRC/double/pdgsrfs.c:345-510) and pzgsrfs3d
-// (SRC/complex16/pzgsrfs.c:365-514), written once for both precisions.  The stopping rule, the per-column work through the
-// resident work vectors and the collective continue / stop decision on grids live here; a precision supplies its two kernels as
-// a policy K:
+// (SRC/complex16/pzgsrfs.c:365-514), written once for both precisions and for A x = b, A^T x = b and A^H x = b.  The stopping rule and its constants
+// (rfs_guards, rfs_continue), the per-column work through the resident work vectors and the collective continue / stop decision on grids live here.
+// A form is the policy K = Rfs<Z, TRANS> below:
 //   K::z                 complex16 (values, x, b, r_perm of two doubles)
 //   K::attach            name for the error messages: this precision's attach call
-//   K::residual(s, H, x, b, r_perm, safe1, safe2)   r_perm = Pc (b - A x), *H->d_rfs_s.p = max(*H->d_rfs_s.p, berr bits)
+//   K::residual(s, H, x, b, r_perm, safe1, safe2)   r_perm = Pc (b - op(A) x), *H->d_rfs_s.p = max(*H->d_rfs_s.p, berr bits)
 //   K::update(s, H, dx_perm, x)                     x += Pc^T dx_perm
-//   K::solve(H, r_perm, n)                          the correction, in place in r_perm: run_solve_dev for A x = b; the transposed policies run the
-//                                                   transposed sweeps (A^T d = r is A1^T (Pc d) = Pc r for the factors of A1 = Pc A Pc^T: the same
-//                                                   permutation on both sides, so r_perm and K::update are used exactly alike)
-// The policies are declared below and DEFINED beside their entry points: DRfs in sluamd_api.cpp (eng::rfs_*), ZRfs in sluamd_zrefine.cpp (eng::zrfs_*),
-// TRfs<Z, CONJ> in sluamd_trefine.cpp for the transposed and conjugate-transposed systems of both (eng::rfs_residual_t / eng::zrfs_residual_t).  Keep the
-// complex and transposed definitions out of sluamd_api.cpp: the CPU test build links the host sources without the complex and the transposed kernels.
-// The GMRES refinement (sluamd_gmres.cpp) runs the same three calls of the same policies around its Krylov kernels.
+//   K::solve(H, r_perm, n)                          the correction, in place in r_perm: run_solve_dev for A x = b, the transposed sweeps otherwise
+//                                                   (A^T d = r is A1^T (Pc d) = Pc r for the factors of A1 = Pc A Pc^T: the same permutation on both
+//                                                   sides, so r_perm and K::update are used exactly alike)
+// A template, so a file instantiates the forms it names and no others: sluamd_api.cpp names Rfs<false, 0> only, and the CPU test build, which links the host
+// sources without sluamd_tsolve.cpp, never sees run_tsolve.  That build's engine (oracle/emul/engine_cpu.cpp) restates the double A x = b kernels under their
+// flat signature and nothing else, so Rfs<false, 0> calls that pair; every other form calls the general entries.  The batch loop (sluamd_batch.cpp) and the GMRES refinement (sluamd_gmres.cpp) share the
+// stopping rule, and the latter runs the same three calls of the same policies around its Krylov kernels.
 #pragma once
 #include "sluamd_comm.h"
 #include "sluamd_plan.h"
@@ -26,30 +26,47 @@ int attach_rfs(sluamd_handle_t h, sluamd_int_t n, const sluamd_int_t *rowptr, co
 // the transposed index of the attached matrix (Handle::d_rfs_tcp / d_rfs_tri / d_rfs_tpos), built on first use: sluamd_trefine.cpp, which describes it
 int ensure_tindex(Handle *H, const char *who);
 
-struct DRfs {   // double, A x = b: sluamd_api.cpp
-    static constexpr bool z = false;
-    static constexpr const char *attach = "sluamd_dAttachMatrix";
-    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2);
-    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x);
-    static int solve(Handle *H, double *r_perm, int n);
-};
-struct ZRfs {   // complex16, A x = b: sluamd_zrefine.cpp
-    static constexpr bool z = true;
-    static constexpr const char *attach = "sluamd_zAttachMatrix";
-    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2);
-    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x);
-    static int solve(Handle *H, double *r_perm, int n);
-};
-template <bool Z, bool CONJ> struct TRfs {   // A^T x = b / A^H x = b of either precision: sluamd_trefine.cpp, which instantiates <false, false>, <true, false>, <true, true>
+template <bool Z, int TRANS> struct Rfs {   // TRANS: 0 = A x = b, 1 = A^T x = b, 2 = A^H x = b (complex16; needs ensure_tindex first, like 1)
     static constexpr bool z = Z;
     static constexpr const char *attach = Z ? "sluamd_zAttachMatrix" : "sluamd_dAttachMatrix";
-    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2);
-    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x);
-    static int solve(Handle *H, double *r_perm, int n);
+    static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
+    {
+        const RfsMat A = rfs_mat(H, TRANS != 0);
+        if constexpr (!Z && TRANS == 0) eng::rfs_residual(s, (int) A.n, A.ptr, A.idx, A.av, x, b, A.pc, r_perm, H->d_rfs_s.p, safe1, safe2);   // the form the CPU test build restates
+        else eng::rfs_residual(s, Z, TRANS == 2, A, x, b, r_perm, H->d_rfs_s.p, safe1, safe2);
+    }
+    static void update(hipStream_t s, const Handle *H, const double *dx_perm, double *x)
+    {
+        if constexpr (!Z && TRANS == 0) eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
+        else eng::rfs_update(s, Z, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
+    }
+    static int solve(Handle *H, double *r_perm, int n)
+    {
+        if constexpr (TRANS != 0) return run_tsolve(H, Z && TRANS == 2, r_perm, n, 1);
+        else return run_solve_dev(H, r_perm, n, 1);
+    }
 };
-extern template struct TRfs<false, false>;
-extern template struct TRfs<true, false>;
-extern template struct TRfs<true, true>;
+// the policy of a (precision, trans) pair known at run time: f(Rfs<..>()) of the form that SLUAMD_NOTRANS / SLUAMD_TRANS / SLUAMD_CONJ names (the conjugate
+// of a real matrix is itself)
+template <class F> auto rfs_dispatch(bool z, int trans, F f)
+{
+    if (trans == SLUAMD_NOTRANS) return z ? f(Rfs<true, 0>()) : f(Rfs<false, 0>());
+    return !z ? f(Rfs<false, 1>()) : trans == SLUAMD_CONJ ? f(Rfs<true, 2>()) : f(Rfs<true, 1>());
+}
+
+// The stopping rule (pdgsrfs.c:371, :463-469, :477): the guards of a matrix of order n, and whether a step follows a backward error sv
+constexpr double RFS_EPS = 0x1p-53, RFS_SAFMIN = 2.2250738585072014e-308;      // dmach_dist("Epsilon"), ("Safe minimum")
+struct RfsGuards { double eps, safe1, safe2; };
+inline RfsGuards rfs_guards(int64_t n)
+{
+    const double safe1 = (double) (n + 1) * RFS_SAFMIN;
+    return {RFS_EPS, safe1, safe1 / RFS_EPS};
+}
+inline bool rfs_continue(double sv, double lstres, int count)
+{
+    constexpr int ITMAX = 20;                                   // pdgsrfs.c:371
+    return sv > RFS_EPS && sv * 2 <= lstres && count < ITMAX;
+}
 
 // what the driver needs beyond the arguments its entry points check (check_solve_args, sluamd_plan.h: handle, blocks, nrhs, leading dimensions, berr, trans,
 // precision, planned transposed sweeps): a matrix attached to the handle -- always of the handle's precision, attach_rfs refuses any other
@@ -70,9 +87,7 @@ template <class K> int rfs_dev(sluamd_handle_t h, const double *d_B, int64_t ldb
     HIPCHK(hipSetDevice(H->device));
     const int vs = K::z ? 2 : 1;
     const int n = (int) H->hs.n;
-    const int ITMAX = 20;                                   // pdgsrfs.c:371
-    const double eps = 0x1p-53, safmin = 2.2250738585072014e-308;
-    const double safe1 = (double) (n + 1) * safmin, safe2 = safe1 / eps;
+    const RfsGuards g = rfs_guards(n);
     double *r_perm = H->d_rfs_work.p;
     hipStream_t s = H->stream;
     int count = 0;
@@ -83,12 +98,12 @@ template <class K> int rfs_dev(sluamd_handle_t h, const double *d_B, int64_t ldb
         count = 0;
         for (;;) {
             HIPCHK(hipMemsetAsync(H->d_rfs_s.p, 0, sizeof(unsigned long long), s));
-            K::residual(s, H, Xc, Bc, r_perm, safe1, safe2);
+            K::residual(s, H, Xc, Bc, r_perm, g.safe1, g.safe2);
             double sv = 0.0;
             HIPCHK(hipMemcpyAsync(&sv, H->d_rfs_s.p, sizeof(double), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             berr[j] = sv;
-            int go = (sv > eps && sv * 2 <= lstres && count < ITMAX) ? 1 : 0;
+            int go = rfs_continue(sv, lstres, count) ? 1 : 0;
             // every rank computed sv from the same all-gathered x, but the step's solve is collective: decide it together, so that the
             // ranks can never split into unmatched solves
             if (grid) { if (int rc = H->comm->allreduce_min(&go, 1, s)) return rc; }

@@ -1,11 +1,12 @@
 // sluamd_trefine.cpp -- iterative refinement of the TRANSPOSED and CONJUGATE-TRANSPOSED systems A^T x = b / A^H x = b of the attached matrix
-// (xGERFS with trans; the reference's pdgsrfs3d / pzgsrfs3d know A x = b only): sluamd_p[dz]gsrfs3d_trans[_dev].  The driver is sluamd_refine.h's, with
-//   residual   eng::rfs_residual_t / eng::zrfs_residual_t over the transposed index of the attached CSR matrix (below),
+// (xGERFS with trans; the reference's pdgsrfs3d / pzgsrfs3d know A x = b only): sluamd_p[dz]gsrfs3d_trans[_dev].  The driver and the policies
+// Rfs<Z, 1> / Rfs<true, 2> are sluamd_refine.h's:
+//   residual   eng::rfs_residual over the transposed index of the attached CSR matrix (below),
 //   solve      the transposed sweeps of sluamd_tsolve.cpp on r_perm: with the factors of A1 = Pc A Pc^T, A^T d = r is A1^T (Pc d) = Pc r -- the same
-//              permutation on both sides, so r_perm and the update kernels are used exactly as in the untransposed loop,
-//   update     eng::rfs_update / eng::zrfs_update, unchanged.
-// A file of its own: the CPU test build (oracle/Makefile) links a fixed list of the host sources against a CPU restatement of the untransposed double
-// kernels only, so no file of that list may reference the transposed kernels or sweeps.
+//              permutation on both sides, so r_perm and the update kernel are used exactly as in the untransposed loop,
+//   update     eng::rfs_update, unchanged.
+// A file of its own: the CPU test build (oracle/Makefile) links a fixed list of the host sources without the transposed sweeps, so no file of that list
+// may instantiate a transposed policy.
 //
 // The transposed index (Handle::d_rfs_tcp / d_rfs_tri / d_rfs_tpos).  Column pointers, and per entry in column order its row and its POSITION in the CSR
 // value array -- no second copy of the values: sluamd_[dz]UpdateValues and sluamd_[dz]Equilibrate rewrite / scale d_rfs_av in place and nothing can go
@@ -55,23 +56,6 @@ int sluamd::ensure_tindex(Handle *H, const char *who)
     return 0;
 }
 
-template <bool Z, bool CONJ> void TRfs<Z, CONJ>::residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
-{
-    if (Z) eng::zrfs_residual_t(s, CONJ, (int) H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
-    else eng::rfs_residual_t(s, (int) H->hs.n, H->d_rfs_tcp.p, H->d_rfs_tri.p, H->d_rfs_tpos.p, H->d_rfs_av.p, x, b, H->d_rfs_pc.p, r_perm, H->d_rfs_s.p, safe1, safe2);
-}
-template <bool Z, bool CONJ> void TRfs<Z, CONJ>::update(hipStream_t s, const Handle *H, const double *dx_perm, double *x)
-{
-    if (Z) eng::zrfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
-    else eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
-}
-template <bool Z, bool CONJ> int TRfs<Z, CONJ>::solve(Handle *H, double *r_perm, int n) { return run_tsolve(H, Z && CONJ, r_perm, n, 1); }
-namespace sluamd {
-template struct TRfs<false, false>;
-template struct TRfs<true, false>;
-template struct TRfs<true, true>;
-}
-
 namespace {
 
 // One entry for the four calls below.  trans == SLUAMD_NOTRANS: the untransposed call of the precision.  Else the checks in the order of the transposed
@@ -88,11 +72,10 @@ int refine_entry(sluamd_handle_t h, int trans, const void *Bv, int64_t ldb, void
         return host ? sluamd_pdgsrfs3d(h, B, ldb, X, ldx, nrhs, berr, steps) : sluamd_pdgsrfs3d_dev(h, B, ldb, X, ldx, nrhs, berr, steps);
     }
     Handle *H = &h->H;
-    if (int rc = z ? rfs_checks<TRfs<true, false>>(H) : rfs_checks<TRfs<false, false>>(H)) return rc;
+    if (int rc = z ? rfs_checks<Rfs<true, 1>>(H) : rfs_checks<Rfs<false, 1>>(H)) return rc;
     if (nrhs == 0) { if (steps) *steps = 0; return 0; }
     if (int rc = ensure_tindex(H, name)) return rc;
-    auto run = [&](auto K) { return host ? rfs_host<decltype(K)>(h, B, ldb, X, ldx, nrhs, berr, steps) : rfs_dev<decltype(K)>(h, B, ldb, X, ldx, nrhs, berr, steps); };
-    return !z ? run(TRfs<false, false>()) : trans == SLUAMD_CONJ ? run(TRfs<true, true>()) : run(TRfs<true, false>());
+    return rfs_dispatch(z, trans, [&](auto K) { return host ? rfs_host<decltype(K)>(h, B, ldb, X, ldx, nrhs, berr, steps) : rfs_dev<decltype(K)>(h, B, ldb, X, ldx, nrhs, berr, steps); });
 }
 
 }  // namespace

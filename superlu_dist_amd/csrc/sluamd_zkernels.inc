@@ -1084,57 +1084,3 @@ __global__ void kz_scatter_values(zc *__restrict__ val, const int64_t *__restric
     int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (e < nnz) val[pos[e]] = a[e];
 }
-
-// ---- iterative refinement, complex16 (pzgsrfs3d, SRC/complex16/pzgsrfs.c:365-514) ------------------------------------
-// The twin of k_rfs_residual: one pass over the CSR matrix does both pzgsmv calls of the reference -- r = b - A x, stored permuted
-// (r_perm[perm_c[i]] = r_i), and temp_i = sum_j abs1(a_ij) abs1(x_j) + abs1(b_i) with abs1(z) = |re| + |im| (slud_z_abs1,
-// pzgsmv.c:324, pzgsrfs.c:463) -- and berr = max_i abs1(r_i) / temp_i with the SAFE1/SAFE2 guards (:466-471).  Every value, x and b
-// entry is one 16-byte load; the maximum is reduced inside the workgroup and leaves with ONE integer atomicMax on its bit pattern
-// (non-negative doubles order like their bit patterns: the result does not depend on the order of the workgroups).
-// HBM-bound: 20 B per nonzero (value + column index) + 56 B per row (b, r_perm, row pointer, perm_c, x_i once).
-__global__ __launch_bounds__(256) void k_zrfs_residual(int n, const int *__restrict__ rp, const int *__restrict__ ci,
-                                                       const zc *__restrict__ av, const zc *__restrict__ x,
-                                                       const zc *__restrict__ b, const int *__restrict__ pc,
-                                                       zc *__restrict__ r_perm, unsigned long long *__restrict__ s_out,
-                                                       double safe1, double safe2)
-{
-    __shared__ double red[4];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    double q = 0.0;
-    if (i < n) {
-        double axr = 0.0, axi = 0.0, t = 0.0;
-        for (int e = rp[i]; e < rp[i + 1]; ++e) {
-            const zc a = av[e], xv = x[ci[e]];
-            axr += a.x * xv.x - a.y * xv.y;
-            axi += a.x * xv.y + a.y * xv.x;
-            t += (fabs(a.x) + fabs(a.y)) * (fabs(xv.x) + fabs(xv.y));
-        }
-        const zc bi = b[i];
-        const zc r = make_double2(bi.x - axr, bi.y - axi);
-        t += fabs(bi.x) + fabs(bi.y);
-        r_perm[pc[i]] = r;
-        const double ar = fabs(r.x) + fabs(r.y);
-        if (t > safe2) q = ar / t;
-        else if (t != 0.0) q = (safe1 + ar) / t;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q = fmax(q, __shfl_xor(q, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = q;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        q = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-        atomicMax(s_out, (unsigned long long) __double_as_longlong(q));
-    }
-}
-
-// x_i += dx_perm[perm_c[i]] (pzgsrfs.c:490-496 after the solve), one complex value per thread
-__global__ __launch_bounds__(256) void k_zrfs_update(int n, const int *__restrict__ pc, const zc *__restrict__ dx_perm, zc *__restrict__ x)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        const zc d = dx_perm[pc[i]];
-        zc v = x[i];
-        v.x += d.x; v.y += d.y;
-        x[i] = v;
-    }
-}

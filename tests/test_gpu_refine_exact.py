@@ -1,4 +1,4 @@
-"""The refinement kernels (k_rfs_residual / k_rfs_update, k_zrfs_residual / k_zrfs_update) and the driver loop of sluamd_refine.h against trajectories
+"""The refinement kernels (k_rfs_residual / k_rfs_update of both precisions) and the driver loop of sluamd_refine.h against trajectories
 known EXACTLY: tests/refine_exact_cases.py attaches a matrix that is not the factored one to handles holding exact factors and predicts berr of every pass,
 every stop decision, the step count and the final X in integers (bitwise equal to the oracle's restatement: test_refine_exact_cases_cpu.py).  Every
 comparison of values in this file is numpy.array_equal on bit patterns: X, berr and the padding rows; the step counts are compared as integers."""

@@ -1,5 +1,5 @@
 """Iterative refinement of the transposed and conjugate-transposed systems (sluamd_p[dz]gsrfs3d_trans[_dev], LUHandle.pdgsrfs3d(trans=)): the residual kernels
-k_rfs_residual_t / kz_rfs_residual_t over the transposed index, the transposed sweeps as the correction, the loop of sluamd_refine.h.
+k_rfs_residual<V, true, CONJ> over the transposed index, the transposed sweeps as the correction, the loop of sluamd_refine.h.
 
 Exact part: tests/refine_trans_cases.py predicts berr of every pass, every stop decision, the step count and the final X in integers (its own bounds
 asserted by test_refine_trans_cases_cpu.py); every comparison of values here is numpy.array_equal on bit patterns, the step counts are integers.

@@ -1,4 +1,4 @@
-"""Complex16 iterative refinement on the device (sluamd_zAttachMatrix / sluamd_pzgsrfs3d[_dev]: k_zrfs_residual + k_zrfs_update
+"""Complex16 iterative refinement on the device (sluamd_zAttachMatrix / sluamd_pzgsrfs3d[_dev]: k_rfs_residual<double2> + k_rfs_update<double2>
 around the complex triangular solves) against the reference's pzgsrfs3d records (IterRefine = SLU_DOUBLE) and the CPU oracle's
 restatement of it; the refinement of grid handles (replicated form) in both precisions.  The bounds are those of
 test_gpu_refine.py: X within 1e-12 max|x| of a reference record and within 1e-11 (relative) of the oracle, berr <= 4 eps,
