@@ -2,6 +2,7 @@
 // exchange, Z ancestor reduction) and pdgstrs3d (level-set forward / backward sweeps with the matching exchanges).
 // All device work goes through eng:: (sluamd_kernels.hip), all communication through Comm (sluamd_comm.h).
 #include <algorithm>
+#include <cassert>
 #include <cstring>
 #include "sluamd_comm.h"
 #include "sluamd_sweep.h"
@@ -83,14 +84,14 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
     auto deferred_inv = [&](hipStream_t st, int l) {
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
         eng::panel_site = {l, nn, -1, 1};
-        eng::full_inv(st, T, S.d_nodes + n0, S.d_finv_prefix + po, nn, S.finv_prefix[po + nn], S.max_nsupc[l]);
+        eng::full_inv(st, T, S.nodes.d + n0, S.finv_prefix.d + po, nn, S.finv_prefix.h[po + nn], S.max_nsupc[l]);
         H->st.num_launches++;
     };
     int cur_level = 0, cur_pass = 0;
     // per-tile records of the list schedules (k_schur mmode 1 / 2): built once per schedule, on its first factorisation
     if (S.maps_state == 0) {
         S.maps_state = -1;
-        if (!H->env.no_tile_maps && !H->opt.deterministic && !S.ulist.empty()) {
+        if (!H->env.no_tile_maps && !H->opt.deterministic && !S.ulist.h.empty()) {
             S.m_off.assign(2 * S.nlevels + 1, 0);
             for (int l = 0; l < S.nlevels; ++l)
                 for (int g = 0; g < 2; ++g) {
@@ -111,8 +112,8 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
                     for (int g = 0; g < 2; ++g) {
                         const int u0 = S.u_off[(2 * l + g) * 4], nu = S.u_off[(2 * l + g) * 4 + 4] - u0;
                         if (!nu) continue;
-                        if (H->z) eng::zschur(s, g == 0 ? 0 : 1, T, nullptr, nullptr, 0, 0, nu, H->d_info.p, S.d_ulist + u0, 0, S.d_tmaps.p + S.m_off[2 * l + g], 1);
-                        else eng::schur(s, g == 0 ? (H->env.schur_4waves ? 1 : 0) : 2, T, nullptr, nullptr, 0, 0, nu, H->d_info.p, S.d_ulist + u0, 0, S.d_tmaps.p + S.m_off[2 * l + g], 1);
+                        if (H->z) eng::zschur(s, g == 0 ? 0 : 1, T, nullptr, nullptr, 0, 0, nu, H->d_info.p, S.ulist.d + u0, 0, S.d_tmaps.p + S.m_off[2 * l + g], 1);
+                        else eng::schur(s, g == 0 ? (H->env.schur_4waves ? 1 : 0) : 2, T, nullptr, nullptr, 0, 0, nu, H->d_info.p, S.ulist.d + u0, 0, S.d_tmaps.p + S.m_off[2 * l + g], 1);
                     }
                 S.maps_state = 1;
                 H->st.bytes_device += (int64_t) bytes;
@@ -137,7 +138,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         int64_t le = -1, ue = -1;
         for (int l = 0; l < S.nlevels; ++l) {
             for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i) {
-                const int k = S.nodes[i];
+                const int k = S.nodes.h[i];
                 if ((H->h_flags[k] & SNF_L_OWN) && H->hs.lval_len[k]) le = std::max(le, H->hs.lval_off[k] + H->hs.lval_len[k]);
                 if ((H->h_flags[k] & SNF_U_OWN) && H->hs.uval_len[k]) ue = std::max(ue, H->hs.uval_off[k] + H->hs.uval_len[k]);
             }
@@ -147,7 +148,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
     else if (H->red_all) hipStreamWaitEvent(s, H->red_all, 0);     // nothing chunk-wise pending: whatever an earlier reduction still adds must be in
     auto panelA = [&](int l) {
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
-        const int *nodes = S.d_nodes + n0;
+        const int *nodes = S.nodes.d + n0;
         const int mx = S.max_nsupc[l];
         eng::panel_site = {l, nn, -1, 0};
         if (!lv_lend.empty()) {   // the panels of this level must hold the partner layer's contributions before they are factored
@@ -158,7 +159,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         if (H->z) {   // Local_Zgstrf2 (pzgstrf2.c); the complex panel solves substitute on the factored block: no inverses
             eng::zdiag_lu(ps, T, nodes, nn, mx, H->opt.replace_tiny_pivot, thresh, H->d_info.p);
             if (xy) {   // zDiagFactIBCast (ztrfCommWrapper.c): packed diagonal blocks down the process column and along the process row
-                eng::pack_diag(ps, T, nodes, S.d_dg_prefix + po, S.d_dg_off + po, nn, S.dg_prefix[po + nn], H->d_val.p + 2 * S.dg_stage_off[l], 2);
+                eng::pack_diag(ps, T, nodes, S.dg_prefix.d + po, S.dg_off.d + po, nn, S.dg_prefix.h[po + nn], H->d_val.p + 2 * S.dg_stage_off[l], 2);
                 ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
                 if (!rc_x) rc_x = exchange(H, S.x_diag_send[l], S.x_diag_recv[l], ps);
                 ev_end(H, H->ev_xchg, H->ev_xchg_used, ps);
@@ -171,14 +172,14 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         const int big_regs = (H->env.diag_tail > 0 && nn == 1 && l >= S.nlevels - H->env.diag_tail) ? 4 : 0;
         eng::diag_lu(ps, T, nodes, nn, mx, (H->opt.replace_tiny_pivot ? 1 : 0) | (H->env.diag_v1 ? 2 : 0) | big_regs, thresh, H->d_info.p);   // Local_Dgstrf2 (+ dinv of the owned blocks)
         if (xy) {   // dDiagFactIBCast (dtrfCommWrapper.c:32-118): diagonal blocks down the process column and along the process row
-            eng::pack_diag(ps, T, nodes, S.d_dg_prefix + po, S.d_dg_off + po, nn, S.dg_prefix[po + nn], H->d_val.p + S.dg_stage_off[l]);
+            eng::pack_diag(ps, T, nodes, S.dg_prefix.d + po, S.dg_off.d + po, nn, S.dg_prefix.h[po + nn], H->d_val.p + S.dg_stage_off[l]);
             ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
             if (!rc_x) rc_x = exchange(H, S.x_diag_send[l], S.x_diag_recv[l], ps);
             ev_end(H, H->ev_xchg, H->ev_xchg_used, ps);
-            eng::diag_inv(ps, T, nodes, S.d_inv_prefix + po, nn, S.inv_prefix[po + nn]);   // column / row peers invert the diagonal blocks they received
+            eng::diag_inv(ps, T, nodes, S.inv_prefix.d + po, nn, S.inv_prefix.h[po + nn]);   // column / row peers invert the diagonal blocks they received
         }
         const bool inv_here = gemm_panels && !tail_level(l);
-        if (inv_here) eng::full_inv(ps, T, nodes, S.d_finv_prefix + po, nn, S.finv_prefix[po + nn], mx);   // Linv / Uinv (the solve uses the owner's too)
+        if (inv_here) eng::full_inv(ps, T, nodes, S.finv_prefix.d + po, nn, S.finv_prefix.h[po + nn], mx);   // Linv / Uinv (the solve uses the owner's too)
         ev_end(H, H->ev_panel, H->ev_panel_used, ps);
         H->st.num_launches += 1 + (inv_here ? 1 : 0) + (xy ? 2 : 0);
     };
@@ -192,20 +193,20 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         const int nl = o1 - o0, nu = o2 - o1;
         if (nl + nu == 0) return;
         eng::panel_site = {l, S.lvl_off[l + 1] - S.lvl_off[l], part, 0};
-        if (gemm_panels && !tail_level(l)) eng::panel_gemm(st, T, nullptr, nullptr, nullptr, 0, nl, nu, mx, S.d_ps_units + o0);
-        else eng::panel_trsm(st, T, nullptr, nullptr, nullptr, 0, nl, nu, 64, mx, S.d_ps_units + o0);
+        if (gemm_panels && !tail_level(l)) eng::panel_gemm(st, T, nullptr, nullptr, nullptr, 0, nl, nu, mx, S.ps_units.d + o0);
+        else eng::panel_trsm(st, T, nullptr, nullptr, nullptr, 0, nl, nu, 64, mx, S.ps_units.d + o0);
         H->st.num_launches++;
     };
     auto panelB = [&](int l) {
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
-        const int *nodes = S.d_nodes + n0;
+        const int *nodes = S.nodes.d + n0;
         const int mx = S.max_nsupc[l];
-        const int nl = S.ltr_prefix[po + nn], nu = S.utr_prefix[po + nn];
+        const int nl = S.ltr_prefix.h[po + nn], nu = S.utr_prefix.h[po + nn];
         eng::panel_site = {l, nn, -1, 0};
         ev_begin(H, H->ev_panel, H->ev_panel_used, ps);
         if (H->z) {   // zLPanelTrSolve / zUPanelTrSolve (ztrfCommWrapper.c): 64-row strips / 64-column chunks
-            const int znl = S.zltr_prefix[po + nn], znu = S.bwd_prefix[po + nn];
-            eng::zpanel_trsm(ps, T, nodes, S.d_zltr_prefix + po, S.d_bwd_prefix + po, nn, znl, znu, mx);
+            const int znl = S.zltr_prefix.h[po + nn], znu = S.bwd_prefix.h[po + nn];
+            eng::zpanel_trsm(ps, T, nodes, S.zltr_prefix.d + po, S.bwd_prefix.d + po, nn, znl, znu, mx);
             if (xy) {
                 ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
                 if (!rc_x) rc_x = exchange(H, S.x_panel_send[l], S.x_panel_recv[l], ps);   // zIBcastRecvLPanel / zIBcastRecvUPanel
@@ -215,8 +216,8 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
             H->st.num_launches += (znl + znu > 0);
             return;
         }
-        if (gemm_panels && !tail_level(l)) eng::panel_gemm(ps, T, nodes, S.d_ltr_prefix + po, S.d_utr_prefix + po, nn, nl, nu, mx);   // chain-free GEMM form of dLPanelTrSolve / dUPanelTrSolve
-        else eng::panel_trsm(ps, T, nodes, S.d_ltr_prefix + po, S.d_utr_prefix + po, nn, nl, nu, trsm_rs(*H, (mx + 31) & ~31), mx);
+        if (gemm_panels && !tail_level(l)) eng::panel_gemm(ps, T, nodes, S.ltr_prefix.d + po, S.utr_prefix.d + po, nn, nl, nu, mx);   // chain-free GEMM form of dLPanelTrSolve / dUPanelTrSolve
+        else eng::panel_trsm(ps, T, nodes, S.ltr_prefix.d + po, S.utr_prefix.d + po, nn, nl, nu, trsm_rs(*H, (mx + 31) & ~31), mx);
         if (xy) {
             ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
             if (!rc_x) rc_x = exchange(H, S.x_panel_send[l], S.x_panel_recv[l], ps);   // dIBcastRecvLPanel / dIBcastRecvUPanel
@@ -250,16 +251,16 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
             // the diagonal-block tiles of the next level (part 0, on the panel stream) when they are few: split K over several workgroups per tile
             const int ks = (lookahead && p0 == 0 && p1 == 0 && g == 0 && nu <= 64 && !H->z && !H->env.schur_4waves) ? H->env.ksplit : 1;
             // a launch of the bulk alone: the XCDs' ranges of equal modelled cost (balance_bulk)
-            const bool bal = p0 == 3 && p1 == 3 && S.d_x_off && !S.x_off.empty() && S.x_off[10 * (size_t) (2 * l + g) + 9] > 0;
-            if (nu) schur(st, g == 0, nu, nullptr, nullptr, 0, 0, S.d_ulist + u0, (lookahead && p1 < 3) ? 1 : 0, tm, ks, bal ? S.d_x_off + 10 * (size_t) (2 * l + g) : nullptr,
-                          bal ? S.x_off[10 * (size_t) (2 * l + g) + 9] : 0);
+            const bool bal = p0 == 3 && p1 == 3 && S.x_off.d && !S.x_off.h.empty() && S.x_off.h[10 * (size_t) (2 * l + g) + 9] > 0;
+            if (nu) schur(st, g == 0, nu, nullptr, nullptr, 0, 0, S.ulist.d + u0, (lookahead && p1 < 3) ? 1 : 0, tm, ks, bal ? S.x_off.d + 10 * (size_t) (2 * l + g) : nullptr,
+                          bal ? S.x_off.h[10 * (size_t) (2 * l + g) + 9] : 0);
         }
     };
     // deterministic mode: one supernode per launch over its full tile grid -- tiles of one k hit distinct destinations, the
     // summation order is fixed
     auto grid_launch = [&](hipStream_t st, int l) {
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0;
-        const int *nodes = S.d_nodes + n0;
+        const int *nodes = S.nodes.d + n0;
         const int nbig = S.n_big[l];
         for (int g = 0; g < 2; ++g) {
             const int cnt = g == 0 ? nbig : nn - nbig;
@@ -267,8 +268,8 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
             const int so = S.lvl_soff[l] + (g == 0 ? 0 : nbig + 1);
             const int *gn = nodes + (g == 0 ? 0 : nbig);
             for (int i = 0; i < cnt; ++i) {
-                const int c = S.tile_prefix[so + i + 1] - S.tile_prefix[so + i];
-                if (c) schur(st, g == 0, c, gn, S.d_tile_prefix + so, cnt, S.tile_prefix[so + i], nullptr);
+                const int c = S.tile_prefix.h[so + i + 1] - S.tile_prefix.h[so + i];
+                if (c) schur(st, g == 0, c, gn, S.tile_prefix.d + so, cnt, S.tile_prefix.h[so + i], nullptr);
             }
         }
     };
@@ -290,7 +291,7 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
             if (H->opt.deterministic) { cur_pass = 3; grid_launch(s, l); }
             // (the bulk as its own launch: its XCD ranges are balanced, LevelSched::x_off)
             else {
-                const bool bal = !S.x_off.empty() && (S.x_off[10 * (size_t) (2 * l) + 9] > 0 || S.x_off[10 * (size_t) (2 * l + 1) + 9] > 0);
+                const bool bal = !S.x_off.h.empty() && (S.x_off.h[10 * (size_t) (2 * l) + 9] > 0 || S.x_off.h[10 * (size_t) (2 * l + 1) + 9] > 0);
                 if (T.defer && S.lvl_defer[l]) { cur_pass = 0; list_launch(s, l, 0, 0); cur_pass = 1; list_launch(s, l, 1, 1); cur_pass = 3; if (bal) { list_launch(s, l, 2, 2); list_launch(s, l, 3, 3); } else list_launch(s, l, 2, 3); }
                 else if (bal) { cur_pass = 3; list_launch(s, l, 0, 2); list_launch(s, l, 3, 3); }
                 else { cur_pass = 3; list_launch(s, l, 0, 3); }
@@ -542,7 +543,7 @@ int ensure_dinv(Handle *H)
         for (int l = 0; l < S.nlevels; ++l) {
             const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
             eng::panel_site = {l, nn, -1, 2};       // on demand, after the factorisation
-            eng::diag_inv(H->stream, H->T, S.d_nodes + n0, S.d_inv_prefix + po, nn, S.inv_prefix[po + nn]);
+            eng::diag_inv(H->stream, H->T, S.nodes.d + n0, S.inv_prefix.d + po, nn, S.inv_prefix.h[po + nn]);
         }
     H->dinv_ready = true;
     return 0;
@@ -558,7 +559,7 @@ int ensure_inv(Handle *H)
         for (int l = 0; l < S.nlevels; ++l) {
             const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
             eng::panel_site = {l, nn, -1, 2};
-            eng::full_inv(H->stream, H->T, S.d_nodes + n0, S.d_finv_prefix + po, nn, S.finv_prefix[po + nn], S.max_nsupc[l]);
+            eng::full_inv(H->stream, H->T, S.nodes.d + n0, S.finv_prefix.d + po, nn, S.finv_prefix.h[po + nn], S.max_nsupc[l]);
         }
     for (size_t gi = 0; gi < H->groups.size(); ++gi) group_inverse(H, (int) gi, H->stream);
     H->inv_ready = true;
@@ -631,94 +632,29 @@ int xseg_exchange(Handle *H, double *d_x, int64_t ldx, int nrhs, const std::vect
 // second vector of the sweeps below: the diagonal solves are out of place (strips of one supernode = independent workgroups)
 int ensure_w(Handle *H, int64_t doubles) { return H->d_w.reserve(doubles, H->device, "the second vector of the sweeps"); }
 
-// Joined links (LevelSched::join): ONE launch per level.  Forward: the joined units of level l + 1 apply the level-l updates to their own block of the
+// The link sweeps of a one-rank double handle are two drivers, solve_fwd_links and solve_bwd_links: per level either a JOINED link (one launch) or a TWO-LAUNCH link
+// (urgent updates, then diagonal strips beside the far updates), chosen by level_joined; on a schedule without joined tables (LevelSched::join false) every level
+// takes two launches and nothing is zeroed.  options.deterministic has its own pair (solve_*_links_serial), whose order is different on purpose.
+// Joined links: ONE launch per level.  Forward: the joined units of level l + 1 apply the level-l updates to their own block of the
 // right-hand side and ADD their share of y_j = Linv_j (...) into w (zeroed first); every other row of the level-l panels is updated by the regular units in
 // the same launch.  Backward: the joined units of level l subtract U(k, columns of level l + 1) x themselves and ADD x_k = Uinv_k (...) into d_x (the forest's
 // rows zeroed first; the top level keeps the storing strips).
 static void zero_forest(Handle *H, LevelSched &S, double *x, int64_t ldx, int nrhs)
 {
-    if ((int) S.nodes.size() == H->hs.nsupers) { for (int q = 0; q < nrhs; ++q) hipMemsetAsync(x + (int64_t) q * ldx, 0, sizeof(double) * (size_t) H->hs.xsup[H->hs.nsupers], H->stream); }
-    else eng::zero_nodes(H->stream, H->T, S.d_nodes, (int) S.nodes.size(), x, ldx, nrhs);
+    if ((int) S.nodes.h.size() == H->hs.nsupers) { for (int q = 0; q < nrhs; ++q) hipMemsetAsync(x + (int64_t) q * ldx, 0, sizeof(double) * (size_t) H->hs.xsup[H->hs.nsupers], H->stream); }
+    else eng::zero_nodes(H->stream, H->T, S.nodes.d, (int) S.nodes.h.size(), x, ldx, nrhs);
 }
-// Per level m: joined when it holds at most SLUAMD_JOIN_MAX_NODES supernodes (the recomputation-free joined units win where a level is a chain of round
+// Per level m: joined when the schedule has joined tables and the level holds at most SLUAMD_JOIN_MAX_NODES supernodes (the recomputation-free joined units win where a level is a chain of round
 // trips; levels of hundreds of supernodes with several sources each keep the two-launch form).  The two forms meet in any order: a level's diagonal blocks
 // are either stored by strips or added by joined units into zeroed rows, and the level below hands over exactly the rows / columns its successor's form expects.
-static inline bool level_joined(const Handle *H, const LevelSched &S, int m, int nrhs = 1)
+static inline bool level_joined(const Handle *H, const LevelSched &S, int m, int nrhs)
 {
-    if (nrhs >= 4) return false;       // blocks of right-hand sides take the two-launch links: their units read the factor entries once per FOUR right-hand sides (k_sweep / k_fwd_update / k_bwd_update <.., RK = 4>), the joined units once per right-hand side
+    if (!S.join || nrhs >= 4) return false;       // blocks of right-hand sides take the two-launch links: their units read the factor entries once per FOUR right-hand sides (k_sweep / k_fwd_update / k_bwd_update <.., RK = 4>), the joined units once per right-hand side
     if (!S.lvl_has_group.empty() && S.lvl_has_group[m]) return false;      // merged groups: strips of the group inverse, two launches for up to four levels
     return S.lvl_off[m + 1] - S.lvl_off[m] <= H->env.join_max_nodes;
 }
-static int solve_fwd_join(Handle *H, LevelSched &S, double *d_x, int64_t ldx, int nrhs)
-{
-    const DevTables &T = H->T;
-    hipStream_t s = H->stream;
-    const int nl = S.nlevels;
-    if (nl == 0) return 0;
-    double *w = H->d_w.p;
-    const int4 *fr = S.d_fwd_recs, *dr = S.d_diag_recs;
-    zero_forest(H, S, w, ldx, nrhs);
-    if (level_joined(H, S, 0, nrhs)) eng::sweep_join(s, true, T, S.d_jf_recs + 8 * (size_t) S.jf_off[0], S.jf_off[1] - S.jf_off[0], S.d_jf_aux, nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[0]);
-    else eng::sweep_step(s, true, T, S.d_diag_units + S.du_off[0], S.du_off[1] - S.du_off[0], nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[0], dr + 2 * (size_t) S.du_off[0], nullptr);
-    H->st.solve_launches += 1;
-    for (int l = 0; l < nl; ++l) {      // the panels of level l, and the diagonal blocks of level l + 1
-        const int mx = std::max(S.max_nsupc[l], l + 1 < nl ? S.max_nsupc[l + 1] : 0);
-        if (nrhs < 4 && (l + 1 == nl || level_joined(H, S, l + 1))) {
-            const int j0 = l + 1 < nl ? S.jf_off[l + 1] : 0, nj = l + 1 < nl ? S.jf_off[l + 2] - j0 : 0;
-            eng::sweep_join(s, true, T, S.d_jf_recs + 8 * (size_t) j0, nj, S.d_jf_aux, S.d_jfu_recs + 2 * (size_t) S.jfu_off[l], S.jfu_off[l + 1] - S.jfu_off[l], d_x, w, ldx, nrhs, mx);
-            H->st.solve_launches += 1;
-        } else {
-            const int u0 = S.fu_off[2 * l], u1 = S.fu_off[2 * l + 1], u2 = S.fu_off[2 * l + 2];
-            const int nd = l + 1 < nl ? S.du_off[l + 2] - S.du_off[l + 1] : 0;       // (the last level's panels update other forests' rows only: no diagonal strips beside them)
-            eng::fwd_update(s, T, nullptr, nullptr, 0, u1 - u0, w, d_x, ldx, nrhs, S.max_nsupc[l], S.d_fwd_units + u0, fr + 2 * (size_t) u0);
-            eng::sweep_step(s, true, T, S.d_diag_units + S.du_off[l + 1], nd, S.d_fwd_units + u1, u2 - u1, d_x, w, ldx, nrhs, mx, dr + 2 * (size_t) S.du_off[l + 1], fr + 2 * (size_t) u1);
-            H->st.solve_launches += 2;
-        }
-    }
-    return 0;
-}
-static int solve_bwd_join(Handle *H, LevelSched &S, double *d_x, int64_t ldx, int nrhs)
-{
-    const DevTables &T = H->T;
-    hipStream_t s = H->stream;
-    const int nl = S.nlevels;
-    if (nl == 0) return 0;
-    double *w = H->d_w.p;
-    const int4 *br = S.d_bwd_recs, *dr = S.d_diag_recs;
-    zero_forest(H, S, d_x, ldx, nrhs);
-    // the chunks of a level whose columns lie beyond the next level run beside the diagonal blocks of the level ABOVE; the top level's (columns of ancestors in
-    // other forests, solved before this sweep) run first, alone.  In which form a level's chunks come follows from its own form: joined -> every chunk, the
-    // columns of the next level skipped (its joined units apply them); two-launch -> the far chunks here, the urgent ones in their own launch later.
-    auto chunks = [&](int l, const int4 *&recs, const int2 *&units, int &n) {
-        if (l < 0) { recs = nullptr; units = nullptr; n = 0; }
-        else if (level_joined(H, S, l, nrhs)) { recs = S.d_jbu_recs + 2 * (size_t) S.jbu_off[l]; units = nullptr; n = S.jbu_off[l + 1] - S.jbu_off[l]; }
-        else { const int b1 = S.bu_off[2 * l + 1], b2 = S.bu_off[2 * l + 2]; recs = br + 2 * (size_t) b1; units = S.d_bwd_units + b1; n = b2 - b1; }
-    };
-    {
-        const int4 *recs; const int2 *units; int n;
-        chunks(nl - 1, recs, units, n);
-        eng::sweep_step(s, false, T, nullptr, 0, units, n, d_x, w, ldx, nrhs, S.max_nsupc[nl - 1], nullptr, recs);
-        H->st.solve_launches += 1;
-    }
-    for (int l = nl - 1; l >= 0; --l) {
-        const int mx = std::max(S.max_nsupc[l], l > 0 ? S.max_nsupc[l - 1] : 0);
-        const int4 *recs; const int2 *units; int n;
-        chunks(l - 1, recs, units, n);
-        if (level_joined(H, S, l, nrhs)) {
-            eng::sweep_join(s, false, T, S.d_jb_recs + 4 * (size_t) S.jb_off[l], S.jb_off[l + 1] - S.jb_off[l], S.d_jb_aux, recs, n, d_x, w, ldx, nrhs, mx);
-            H->st.solve_launches += 1;
-        } else {
-            const int u0 = S.bu_off[2 * l], u1 = S.bu_off[2 * l + 1];
-            eng::bwd_update(s, T, nullptr, nullptr, 0, u1 - u0, d_x, w, ldx, nrhs, S.max_nsupc[l], S.d_bwd_units + u0, br + 2 * (size_t) u0);
-            eng::sweep_step(s, false, T, S.d_diag_units + S.du_off[l], S.du_off[l + 1] - S.du_off[l], units, n, d_x, w, ldx, nrhs, mx, dr + 2 * (size_t) S.du_off[l], recs);
-            H->st.solve_launches += 2;
-        }
-    }
-    return 0;
-}
-
-// Forward links.  x (= d_x) holds the right-hand side minus the updates applied so far; w receives the solved blocks y_k = Linv (x_k)
-// and is what the updates read.  After the forward sweeps of all Z levels w holds y for every supernode solved on this rank.
+// Forward links, every level in its own form.  x (= d_x) holds the right-hand side minus the updates applied so far; w receives the solved blocks
+// y_k = Linv (x_k) and is what the updates read.  After the forward sweeps of all Z levels w holds y for every supernode solved on this rank.
 static int solve_fwd_links(Handle *H, LevelSched &S, double *d_x, int64_t ldx, int nrhs)
 {
     const DevTables &T = H->T;
@@ -726,20 +662,28 @@ static int solve_fwd_links(Handle *H, LevelSched &S, double *d_x, int64_t ldx, i
     const int nl = S.nlevels;
     if (nl == 0) return 0;
     double *w = H->d_w.p;
-    const int4 *fr = S.d_fwd_recs, *dr = S.d_diag_recs;     // unit records (null on complex handles)
-    eng::sweep_step(s, true, T, S.d_diag_units + S.du_off[0], S.du_off[1] - S.du_off[0], nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[0], dr ? dr + 2 * (size_t) S.du_off[0] : nullptr, nullptr);
-    for (int l = 0; l < nl; ++l) {
-        const int u0 = S.fu_off[2 * l], u1 = S.fu_off[2 * l + 1], u2 = S.fu_off[2 * l + 2];
-        const int nd = (l + 1 < nl) ? S.du_off[l + 2] - S.du_off[l + 1] : 0;
+    const int4 *fr = S.fwd_recs.d, *dr = S.diag_recs.d;
+    auto joined = [&](int m) { return level_joined(H, S, m, nrhs); };
+    if (S.join) zero_forest(H, S, w, ldx, nrhs);       // (the joined units ADD into w; also when nrhs >= 4 leaves no level joined)
+    if (joined(0)) eng::sweep_join(s, true, T, S.jf_recs.d + 8 * (size_t) S.jf_off[0], S.jf_off[1] - S.jf_off[0], S.jf_aux.d, nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[0]);
+    else eng::sweep_step(s, true, T, S.diag_units.d + S.du_off[0], S.du_off[1] - S.du_off[0], nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[0], dr + 2 * (size_t) S.du_off[0], nullptr);
+    H->st.solve_launches += S.join ? 1 : 0;            // (a schedule without joined tables has never counted its first launch)
+    for (int l = 0; l < nl; ++l) {      // the panels of level l, and the diagonal blocks of level l + 1
         const int mx = std::max(S.max_nsupc[l], l + 1 < nl ? S.max_nsupc[l + 1] : 0);
-        eng::fwd_update(s, T, nullptr, nullptr, 0, u1 - u0, w, d_x, ldx, nrhs, S.max_nsupc[l], S.d_fwd_units + u0, fr ? fr + 2 * (size_t) u0 : nullptr);
-        eng::sweep_step(s, true, T, S.d_diag_units + (nd ? S.du_off[l + 1] : 0), nd, S.d_fwd_units + u1, u2 - u1, d_x, w, ldx, nrhs, mx,
-                        dr ? dr + 2 * (size_t) (nd ? S.du_off[l + 1] : 0) : nullptr, fr ? fr + 2 * (size_t) u1 : nullptr);
-        H->st.solve_launches += 2;
+        if (l + 1 < nl ? joined(l + 1) : (S.join && nrhs < 4)) {      // (the last level's panels: one launch over the jfu records wherever they exist and run)
+            const int j0 = l + 1 < nl ? S.jf_off[l + 1] : 0, nj = l + 1 < nl ? S.jf_off[l + 2] - j0 : 0;
+            eng::sweep_join(s, true, T, S.jf_recs.d + 8 * (size_t) j0, nj, S.jf_aux.d, S.jfu_recs.d + 2 * (size_t) S.jfu_off[l], S.jfu_off[l + 1] - S.jfu_off[l], d_x, w, ldx, nrhs, mx);
+            H->st.solve_launches += 1;
+        } else {
+            const int u0 = S.fu_off[2 * l], u1 = S.fu_off[2 * l + 1], u2 = S.fu_off[2 * l + 2];
+            const int nd = l + 1 < nl ? S.du_off[l + 2] - S.du_off[l + 1] : 0;       // (the last level's panels update other forests' rows only: no diagonal strips beside them)
+            eng::fwd_update(s, T, nullptr, nullptr, 0, u1 - u0, w, d_x, ldx, nrhs, S.max_nsupc[l], S.fwd_units.d + u0, fr + 2 * (size_t) u0);
+            eng::sweep_step(s, true, T, S.diag_units.d + S.du_off[l + 1], nd, S.fwd_units.d + u1, u2 - u1, d_x, w, ldx, nrhs, mx, dr + 2 * (size_t) S.du_off[l + 1], fr + 2 * (size_t) u1);
+            H->st.solve_launches += 2;
+        }
     }
     return 0;
 }
-
 // Backward links: w_k (the forward solution) minus the updates U(k, :) x accumulates in w; the final x_k = Uinv w_k goes to d_x.
 static int solve_bwd_links(Handle *H, LevelSched &S, double *d_x, int64_t ldx, int nrhs)
 {
@@ -748,27 +692,39 @@ static int solve_bwd_links(Handle *H, LevelSched &S, double *d_x, int64_t ldx, i
     const int nl = S.nlevels;
     if (nl == 0) return 0;
     double *w = H->d_w.p;
-    const int4 *br = S.d_bwd_recs, *dr = S.d_diag_recs;
-    {   // far chunks of the top level (columns of ancestors in other forests, solved before this sweep)
-        const int u1 = S.bu_off[2 * (nl - 1) + 1], u2 = S.bu_off[2 * (nl - 1) + 2];
-        eng::sweep_step(s, false, T, nullptr, 0, S.d_bwd_units + u1, u2 - u1, d_x, w, ldx, nrhs, S.max_nsupc[nl - 1], nullptr, br ? br + 2 * (size_t) u1 : nullptr);
-        H->st.solve_launches += 1;
-    }
+    const int4 *br = S.bwd_recs.d, *dr = S.diag_recs.d;
+    auto joined = [&](int m) { return level_joined(H, S, m, nrhs); };
+    if (S.join) zero_forest(H, S, d_x, ldx, nrhs);     // (the joined units ADD into d_x)
+    // the chunks of a level whose columns lie beyond the next level run beside the diagonal blocks of the level ABOVE; the top level's (columns of ancestors in
+    // other forests, solved before this sweep) run first, alone.  In which form a level's chunks come follows from its own form: joined -> every chunk, the
+    // columns of the next level skipped (its joined units apply them); two-launch -> the far chunks here, the urgent ones in their own launch later.
+    auto chunks = [&](int l, const int4 *&recs, const int2 *&units, int &n) {
+        if (l < 0) { recs = nullptr; units = nullptr; n = 0; }
+        else if (joined(l)) { recs = S.jbu_recs.d + 2 * (size_t) S.jbu_off[l]; units = nullptr; n = S.jbu_off[l + 1] - S.jbu_off[l]; }
+        else { const int b1 = S.bu_off[2 * l + 1], b2 = S.bu_off[2 * l + 2]; recs = br + 2 * (size_t) b1; units = S.bwd_units.d + b1; n = b2 - b1; }
+    };
+    const int4 *recs; const int2 *units; int n;
+    chunks(nl - 1, recs, units, n);
+    eng::sweep_step(s, false, T, nullptr, 0, units, n, d_x, w, ldx, nrhs, S.max_nsupc[nl - 1], nullptr, recs);
+    H->st.solve_launches += 1;
     for (int l = nl - 1; l >= 0; --l) {
-        const int u0 = S.bu_off[2 * l], u1 = S.bu_off[2 * l + 1];
-        const int nd = S.du_off[l + 1] - S.du_off[l];
-        const int b1 = l > 0 ? S.bu_off[2 * (l - 1) + 1] : 0, b2 = l > 0 ? S.bu_off[2 * (l - 1) + 2] : 0;   // far chunks of level l-1: x of levels >= l+1 only
         const int mx = std::max(S.max_nsupc[l], l > 0 ? S.max_nsupc[l - 1] : 0);
-        eng::bwd_update(s, T, nullptr, nullptr, 0, u1 - u0, d_x, w, ldx, nrhs, S.max_nsupc[l], S.d_bwd_units + u0, br ? br + 2 * (size_t) u0 : nullptr);
-        eng::sweep_step(s, false, T, S.d_diag_units + S.du_off[l], nd, S.d_bwd_units + b1, b2 - b1, d_x, w, ldx, nrhs, mx,
-                        dr ? dr + 2 * (size_t) S.du_off[l] : nullptr, br ? br + 2 * (size_t) b1 : nullptr);
-        H->st.solve_launches += 2;
+        chunks(l - 1, recs, units, n);
+        if (joined(l)) {
+            eng::sweep_join(s, false, T, S.jb_recs.d + 4 * (size_t) S.jb_off[l], S.jb_off[l + 1] - S.jb_off[l], S.jb_aux.d, recs, n, d_x, w, ldx, nrhs, mx);
+            H->st.solve_launches += 1;
+        } else {
+            const int u0 = S.bu_off[2 * l], u1 = S.bu_off[2 * l + 1];
+            eng::bwd_update(s, T, nullptr, nullptr, 0, u1 - u0, d_x, w, ldx, nrhs, S.max_nsupc[l], S.bwd_units.d + u0, br + 2 * (size_t) u0);
+            eng::sweep_step(s, false, T, S.diag_units.d + S.du_off[l], S.du_off[l + 1] - S.du_off[l], units, n, d_x, w, ldx, nrhs, mx, dr + 2 * (size_t) S.du_off[l], recs);
+            H->st.solve_launches += 2;
+        }
     }
     return 0;
 }
 
-// The links of a handle created with options.deterministic: the same units, records and vectors as solve_fwd_links / solve_bwd_links, but every update unit is a
-// launch of its own, in list order.  Units of one launch subtract from shared rows of x with fp64 atomics, in whatever order they arrive; one unit per launch
+// The links of a handle created with options.deterministic: the same units, records and vectors as the two-launch links of solve_fwd_links / solve_bwd_links, but
+// per level the diagonal units, then every update unit as a launch of its own, in list order (no urgent / bulk split).  Units of one launch subtract from shared rows of x with fp64 atomics, in whatever order they arrive; one unit per launch
 // on one stream fixes that order, so a solve repeats bit for bit (the diagonal units write distinct blocks out of place and stay together).  As slow as the
 // deterministic factorisation is: one launch per unit.
 static int solve_fwd_links_serial(Handle *H, LevelSched &S, double *d_x, int64_t ldx, int nrhs)
@@ -778,12 +734,12 @@ static int solve_fwd_links_serial(Handle *H, LevelSched &S, double *d_x, int64_t
     const int nl = S.nlevels;
     if (nl == 0) return 0;
     double *w = H->d_w.p;
-    const int4 *fr = S.d_fwd_recs, *dr = S.d_diag_recs;
+    const int4 *fr = S.fwd_recs.d, *dr = S.diag_recs.d;
     for (int l = 0; l < nl; ++l) {
         const int nd = S.du_off[l + 1] - S.du_off[l];
-        eng::sweep_step(s, true, T, S.d_diag_units + S.du_off[l], nd, nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[l], dr ? dr + 2 * (size_t) S.du_off[l] : nullptr, nullptr);
+        eng::sweep_step(s, true, T, S.diag_units.d + S.du_off[l], nd, nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[l], dr + 2 * (size_t) S.du_off[l], nullptr);
         for (int u = S.fu_off[2 * l]; u < S.fu_off[2 * l + 2]; ++u)
-            eng::fwd_update(s, T, nullptr, nullptr, 0, 1, w, d_x, ldx, nrhs, S.max_nsupc[l], S.d_fwd_units + u, fr ? fr + 2 * (size_t) u : nullptr);
+            eng::fwd_update(s, T, nullptr, nullptr, 0, 1, w, d_x, ldx, nrhs, S.max_nsupc[l], S.fwd_units.d + u, fr + 2 * (size_t) u);
         H->st.solve_launches += 1 + S.fu_off[2 * l + 2] - S.fu_off[2 * l];
     }
     return 0;
@@ -796,12 +752,12 @@ static int solve_bwd_links_serial(Handle *H, LevelSched &S, double *d_x, int64_t
     const int nl = S.nlevels;
     if (nl == 0) return 0;
     double *w = H->d_w.p;
-    const int4 *br = S.d_bwd_recs, *dr = S.d_diag_recs;
+    const int4 *br = S.bwd_recs.d, *dr = S.diag_recs.d;
     for (int l = nl - 1; l >= 0; --l) {     // every chunk of level l reads x of levels above l (or of other forests) only: all of them, then the level's diagonal units
         for (int u = S.bu_off[2 * l]; u < S.bu_off[2 * l + 2]; ++u)
-            eng::bwd_update(s, T, nullptr, nullptr, 0, 1, d_x, w, ldx, nrhs, S.max_nsupc[l], S.d_bwd_units + u, br ? br + 2 * (size_t) u : nullptr);
+            eng::bwd_update(s, T, nullptr, nullptr, 0, 1, d_x, w, ldx, nrhs, S.max_nsupc[l], S.bwd_units.d + u, br + 2 * (size_t) u);
         const int nd = S.du_off[l + 1] - S.du_off[l];
-        eng::sweep_step(s, false, T, S.d_diag_units + S.du_off[l], nd, nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[l], dr ? dr + 2 * (size_t) S.du_off[l] : nullptr, nullptr);
+        eng::sweep_step(s, false, T, S.diag_units.d + S.du_off[l], nd, nullptr, 0, d_x, w, ldx, nrhs, S.max_nsupc[l], dr + 2 * (size_t) S.du_off[l], nullptr);
         H->st.solve_launches += 1 + S.bu_off[2 * l + 2] - S.bu_off[2 * l];
     }
     return 0;
@@ -836,11 +792,11 @@ static int solve_fwd_z(Handle *H, int z, double *d_x, int64_t ldx, int nrhs)
     LevelSched &S = H->sched[z];
     const bool xy = H->grid.Pr * H->grid.Pc > 1;
     if (!xy && !H->z && !H->profile) {
-        int rc = ensure_w(H, ldx * (int64_t) max_rhs_chunk(H));
-        if (!rc && H->opt.deterministic) return solve_fwd_links_serial(H, S, d_x, ldx, nrhs);
-        if (!rc && !H->ssched.empty() && H->ssched[z].join && groups_fit(H, nrhs)) return solve_fwd_join(H, H->ssched[z], d_x, ldx, nrhs);     // merged chain groups: the contracted schedule
-        if (!rc && S.join) return solve_fwd_join(H, S, d_x, ldx, nrhs);
-        return rc ? rc : solve_fwd_links(H, S, d_x, ldx, nrhs);
+        if (int rc = ensure_w(H, ldx * (int64_t) max_rhs_chunk(H))) return rc;
+        assert(!H->z);      // the links read the unit records, which complex16 handles do not have
+        if (H->opt.deterministic) return solve_fwd_links_serial(H, S, d_x, ldx, nrhs);
+        const bool grouped = !H->ssched.empty() && H->ssched[z].join && groups_fit(H, nrhs);     // merged chain groups: the contracted schedule
+        return solve_fwd_links(H, grouped ? H->ssched[z] : S, d_x, ldx, nrhs);      // joined levels where S.join, two launches per level elsewhere
     }
     const int n = sweep_forest(H, S, true, d_x, ldx, nrhs, H->z ? plain_z : plain_d);      // (counts no launches: Handle::st)
     return n < 0 ? n : 0;
@@ -850,11 +806,11 @@ static int solve_bwd_z(Handle *H, int z, double *d_x, int64_t ldx, int nrhs)
     LevelSched &S = H->sched[z];
     const bool xy = H->grid.Pr * H->grid.Pc > 1;
     if (!xy && !H->z && !H->profile) {
-        int rc = ensure_w(H, ldx * (int64_t) max_rhs_chunk(H));      // (already there: the forward sweep ran first)
-        if (!rc && H->opt.deterministic) return solve_bwd_links_serial(H, S, d_x, ldx, nrhs);
-        if (!rc && !H->ssched.empty() && H->ssched[z].join && groups_fit(H, nrhs)) return solve_bwd_join(H, H->ssched[z], d_x, ldx, nrhs);
-        if (!rc && S.join) return solve_bwd_join(H, S, d_x, ldx, nrhs);
-        return rc ? rc : solve_bwd_links(H, S, d_x, ldx, nrhs);
+        if (int rc = ensure_w(H, ldx * (int64_t) max_rhs_chunk(H))) return rc;      // (already there: the forward sweep ran first)
+        assert(!H->z);      // the links read the unit records, which complex16 handles do not have
+        if (H->opt.deterministic) return solve_bwd_links_serial(H, S, d_x, ldx, nrhs);
+        const bool grouped = !H->ssched.empty() && H->ssched[z].join && groups_fit(H, nrhs);     // merged chain groups: the contracted schedule
+        return solve_bwd_links(H, grouped ? H->ssched[z] : S, d_x, ldx, nrhs);      // joined levels where S.join, two launches per level elsewhere
     }
     const int n = sweep_forest(H, S, false, d_x, ldx, nrhs, H->z ? plain_z : plain_d);
     return n < 0 ? n : 0;
@@ -883,7 +839,7 @@ static int zsolve_fused(Handle *H, double *x, int64_t ldx, int nr)
         for (int l = 0; l < S.nlevels; ++l) {
             const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
             if (fused(S, l)) {
-                eng::zsweep_fused(s, true, T, S.d_nodes + n0, S.d_zffu_prefix + po, nn, S.zffu_prefix[po + nn], x, H->d_w.p, ldx, nr, S.max_nsupc[l], nullptr);
+                eng::zsweep_fused(s, true, T, S.nodes.d + n0, S.zffu_prefix.d + po, nn, S.zffu_prefix.h[po + nn], x, H->d_w.p, ldx, nr, S.max_nsupc[l], nullptr);
                 H->st.solve_launches += 1;
             } else H->st.solve_launches += sweep_level(H, S, l, true, x, ldx, nr, plain_z);      // (one rank: no exchange, no error)
         }
@@ -892,7 +848,7 @@ static int zsolve_fused(Handle *H, double *x, int64_t ldx, int nr)
         for (int l = S.nlevels - 1; l >= 0; --l) {
             const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
             if (fused(S, l)) {
-                eng::zsweep_fused(s, false, T, S.d_nodes + n0, S.d_zbfu_prefix + po, nn, S.zbfu_prefix[po + nn], x, H->d_w.p, ldx, nr, S.max_nsupc[l], H->d_ztickets.p);
+                eng::zsweep_fused(s, false, T, S.nodes.d + n0, S.zbfu_prefix.d + po, nn, S.zbfu_prefix.h[po + nn], x, H->d_w.p, ldx, nr, S.max_nsupc[l], H->d_ztickets.p);
                 H->st.solve_launches += 1;
             } else H->st.solve_launches += sweep_level(H, S, l, false, x, ldx, nr, plain_z);
         }

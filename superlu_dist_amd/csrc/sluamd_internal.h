@@ -169,44 +169,53 @@ struct DevTables {
 // One exchange message of the XY panel exchange: a contiguous range of the value arena sent to / received from one peer
 struct XMsg { int peer; int64_t off, len; };   // world rank, arena offset, doubles
 
+// One planned table of a schedule: the host image and its device copy (null until the table is uploaded; owned by the bag it went into).
+// upload(): sluamd_plan.h, beside the helper it goes through
+template <class T> struct PlanTable {
+    std::vector<T> h;
+    T *d = nullptr;
+    int upload(DevBag &keep, const char *what);
+    void drop_host() { std::vector<T>().swap(h); }
+};
+
+// The level schedule of one forest.  Every table that goes to the device is ONE PlanTable member (S.table.h on the host, S.table.d on the device; upload_schedule,
+// sluamd_plan.cpp, says which are uploaded on which handles); plain vectors are host-only
 struct LevelSched {
     int nlevels = 0;
     std::vector<int> lvl_off;       // [nlevels+1] into nodes
-    std::vector<int> nodes;         // supernodes sorted by level (big-tile supernodes first inside a level)
-    std::vector<int> tile_prefix;   // per node (aligned with nodes), exclusive prefix WITHIN its level (+1 total slot per level)
-    std::vector<int> ltr_prefix;    // L-TRSM strips
-    std::vector<int> utr_prefix;    // U-TRSM column chunks
-    std::vector<int> inv_prefix;    // diagonal sub-block inversion tasks
-    std::vector<int> zltr_prefix;   // complex path: 64-row L strips (the 64-column U chunks reuse bwd_prefix)
+    PlanTable<int> nodes;           // supernodes sorted by level (big-tile supernodes first inside a level)
+    PlanTable<int> tile_prefix;     // per node (aligned with nodes), exclusive prefix WITHIN its level (+1 total slot per level)
+    PlanTable<int> ltr_prefix;      // L-TRSM strips
+    PlanTable<int> utr_prefix;      // U-TRSM column chunks
+    PlanTable<int> inv_prefix;      // diagonal sub-block inversion tasks
+    PlanTable<int> zltr_prefix;     // complex path: 64-row L strips (the 64-column U chunks reuse bwd_prefix)
     std::vector<int> lvl_poff;      // [nlevels+1] offset of each level's prefix arrays (size nodes_in_level+1)
     std::vector<int> lvl_soff;      // [nlevels+1] offset of each level's Schur prefix arrays (big group | small group)
     std::vector<int> n_big;         // per level: nodes using the 128x128 tile configuration (listed first)
-    std::vector<int> fwd_prefix, bwd_prefix;  // solve work units: 64-row L strips / 64-column U chunks
-    std::vector<int> zfwd_prefix;             // complex path: 256-row L strips
-    std::vector<int> zffu_prefix, zbfu_prefix; // complex path, fused links (eng::zsweep_fused): 256-row strips / 64-column chunks with AT LEAST ONE unit per owned diagonal block
-    int *d_zffu_prefix = nullptr, *d_zbfu_prefix = nullptr;
+    PlanTable<int> fwd_prefix, bwd_prefix;    // solve work units: 64-row L strips / 64-column U chunks
+    PlanTable<int> zfwd_prefix;               // complex path: 256-row L strips
+    PlanTable<int> zffu_prefix, zbfu_prefix;   // complex path, fused links (eng::zsweep_fused): 256-row strips / 64-column chunks with AT LEAST ONE unit per owned diagonal block (uploaded on complex16 handles)
     // the same units as explicit (supernode, strip / chunk) lists, per level [urgent | bulk]: urgent = touches a supernode of the
     // adjacent level (l+1: rows the forward update writes / columns the backward update reads) = what the next diagonal solve of the
     // chain waits for, bulk = levels >= l+2 only (launched together with that diagonal solve, eng::sweep_step)
-    std::vector<int2> fwd_units, bwd_units;
+    PlanTable<int2> fwd_units, bwd_units;
     std::vector<int> fu_off, bu_off;          // [2*nlevels+1]: index 2*level + part
-    std::vector<int2> diag_units;             // (supernode, 64-row strip) of every owned diagonal block, level by level: the out-of-place diagonal solves of the sweeps
+    PlanTable<int2> diag_units;               // (supernode, 64-row strip) of every owned diagonal block, level by level: the out-of-place diagonal solves of the sweeps
     std::vector<int> du_off;                  // [nlevels+1]
-    std::vector<int> finv_prefix;   // per level (lvl_poff layout): 64-row identity strips of the Linv / Uinv computation, 2 * ceil(ns / 64) per owned diagonal block
+    PlanTable<int> finv_prefix;     // per level (lvl_poff layout): 64-row identity strips of the Linv / Uinv computation, 2 * ceil(ns / 64) per owned diagonal block
     std::vector<int> max_nsupc;     // per level
     std::vector<double> lvl_flops_schur, lvl_flops_panel;   // per level, THIS rank's share: exact-segment Schur flops of its tiles; diagonal LU + panel solves it owns (sluamd_plan_table)
-    std::vector<uint8_t> lvl_has_group;   // (contracted schedule of the sweeps) the level holds a merged chain group: always run as a joined link
+    std::vector<uint8_t> lvl_has_group;   // (contracted schedule of the sweeps) the level holds a merged chain group: never joined (level_joined), the strips of the group inverse take two launches
     bool no_join = false;           // the sweeps follow Handle::ssched: no joined tables for this schedule
     std::vector<uint8_t> lvl_defer; // per level: some supernode's non-urgent tiles are deferred to its K-fused partner
     // Split panel solves (look-ahead schedule, 1 x 1 layers, real): per level the 64-row strips of L(:, k) / 64-column chunks of U(k, :) that the level's
     // part-0 tiles (destination: a diagonal block of the next level) read -- "urgent": solved first, on the panel stream, so that the next level's diagonal
     // LU starts after those strips and their tiles alone -- and all the others, solved beside that diagonal LU on the urgent-tile stream.
     // ps_units: per split level [urgent L | urgent U | rest L | rest U]; ps_off[4 l .. 4 l + 4] its boundaries (equal: level not split)
-    std::vector<int2> ps_units;
+    PlanTable<int2> ps_units;       // (uploaded only when some level is split)
     std::vector<int> ps_off;        // [4*nlevels+1]
-    int2 *d_ps_units = nullptr;
-    std::vector<int> sn_level;      // [nsupers] level of each supernode in this schedule (-1: not in it)
-    std::vector<int4> ulist;        // tile lists (k, absolute row tile, absolute column tile, destination block or -1): per level and tile-size group
+    PlanTable<int> sn_level;        // [nsupers] level of each supernode in this schedule (-1: not in it)
+    PlanTable<int4> ulist;          // tile lists (k, absolute row tile, absolute column tile, destination block or -1): per level and tile-size group
                                     // [diagonal blocks of level l+1 | rest of the level-(l+1) panels | level-(l+2) panels | bulk, 8 x 8 bands per supernode]
     std::vector<int> u_off;         // [8*nlevels+1] offsets into ulist: index (2*level + group) * 4 + part
     std::vector<int64_t> m_off;     // [2*nlevels+1] first int of the tile records of (level, group) in d_tmaps (record of tile u of the group: + (u - u_off[group start]) * rec)
@@ -214,12 +223,11 @@ struct LevelSched {
     // Balanced bulk launches (round 6; balance_bulk): k_schur gives XCD x the tiles [x_off[x], x_off[x + 1]) of the launch -- eight contiguous ranges of EQUAL MODELLED COST
     // (K chunks of all sources x share of the waves that run MFMAs) instead of equal counts; the level's supernodes are listed longest tiles first.
     // x_off: 10 ints per (level, group) at 10 * (2 * level + group): nine range boundaries relative to the launch's first tile + the longest range; [9] == 0: not balanced
-    std::vector<int> x_off;
-    int *d_x_off = nullptr;
+    PlanTable<int> x_off;
     int maps_state = 0;             // 0: not built yet, 1: built, -1: unavailable (memory / switched off)
     // ---- XY block-cyclic exchange plan (empty on a 1 x 1 layer): per level, in ascending supernode order ----
-    std::vector<int> dg_prefix;               // per node (lvl_poff layout): 1024-double chunks of the own diagonal blocks to pack
-    std::vector<int64_t> dg_off;              // ... and their offsets inside the level's diagonal staging range
+    PlanTable<int> dg_prefix;                 // per node (lvl_poff layout): 1024-double chunks of the own diagonal blocks to pack
+    PlanTable<int64_t> dg_off;                // ... and their offsets inside the level's diagonal staging range
     std::vector<std::vector<XMsg>> x_diag_send, x_diag_recv;     // phase 1: packed diagonal blocks (column + row peers)
     std::vector<std::vector<XMsg>> x_panel_send, x_panel_recv;   // phase 2: L slots along the process row, U slots down the column
     std::vector<int64_t> dg_stage_off;        // [nlevels] arena offset of the level's packed own diagonal blocks
@@ -229,17 +237,9 @@ struct LevelSched {
     // ... and of the TRANSPOSED sweeps (sluamd_tsolve.cpp), where the two directions swap: partial sums of x_k are reduced along process COLUMN k % Pc to the
     // diagonal owner, x_k is broadcast along process ROW k % Pr.  Built on request, after the handle exists (sluamd_PlanTransposedSweeps -> plan_trans_exchange)
     std::vector<std::vector<XSeg>> xt_red_send, xt_red_recv, xt_bc_send, xt_bc_recv;
-    // device copies
-    int *d_nodes = nullptr, *d_tile_prefix = nullptr, *d_ltr_prefix = nullptr, *d_utr_prefix = nullptr;
-    int *d_fwd_prefix = nullptr, *d_bwd_prefix = nullptr, *d_inv_prefix = nullptr, *d_sn_level = nullptr, *d_zltr_prefix = nullptr;
-    int *d_finv_prefix = nullptr, *d_zfwd_prefix = nullptr;
-    int4 *d_ulist = nullptr;
-    int2 *d_fwd_units = nullptr, *d_bwd_units = nullptr, *d_diag_units = nullptr;
     // unit records of the 1 x 1 layer sweeps, two int4 per unit in the order of the unit lists: what a unit otherwise looks up in six tables
     // behind its list entry (fwd / bwd_update_body, diag_strip_body)
-    std::vector<int4> fwd_recs, bwd_recs, diag_recs;
-    int4 *d_fwd_recs = nullptr, *d_bwd_recs = nullptr, *d_diag_recs = nullptr;
-    int *d_dg_prefix = nullptr; int64_t *d_dg_off = nullptr;
+    PlanTable<int4> fwd_recs, bwd_recs, diag_recs;      // (double handles; the host images are dropped once uploaded)
     // ---- joined sweeps (round 4; 1 x 1 layers, real) ----
     // The level-set sweeps above pay TWO dependent launches per level: the urgent updates of level l, then the diagonal solves of level l + 1.  Joined
     // form: the diagonal solve of supernode j (level l + 1) is cut into 64 x 64 blocks (s, c) of its inverse, and the unit of block (s, c) first applies the
@@ -256,9 +256,8 @@ struct LevelSched {
     //   jb_aux: one int4 (leading zeros, value offset, global column, 0) per near column
     //   regular units: the 2-int4 records of fwd_recs / bwd_recs; bit 16 of .y (width) set = the unit has near rows / columns to skip
     bool join = false;
-    std::vector<int4> jf_recs, jf_aux, jb_recs, jb_aux, jfu_recs, jbu_recs;
+    PlanTable<int4> jf_recs, jf_aux, jb_recs, jb_aux, jfu_recs, jbu_recs;      // (uploaded when `join`; the host images are dropped)
     std::vector<int> jf_off, jb_off, jfu_off, jbu_off;     // [nlevels + 1] unit ranges per level
-    int4 *d_jf_recs = nullptr, *d_jf_aux = nullptr, *d_jb_recs = nullptr, *d_jb_aux = nullptr, *d_jfu_recs = nullptr, *d_jbu_recs = nullptr;
 };
 
 struct Comm;   // sluamd_comm.h

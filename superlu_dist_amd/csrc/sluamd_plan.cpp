@@ -487,7 +487,7 @@ static void build_tile_lists(const HostTables &t, const std::vector<int> &lvl, c
     //   part 3: the bulk, supernode after supernode in bands of 8 row tiles, column-major inside a band: the ~64 tiles an XCD
     //           runs at a time form an 8 x 8 block that shares 8 L row tiles and 8 U column tiles in that XCD's L2.
     // A deferred (K-fused) supernode runs parts 0 and 1 only; its partner on the next level applies everything else.
-    S.sn_level = lvl;
+    S.sn_level.h = lvl;
     S.u_off.assign(8 * S.nlevels + 1, 0);
     const bool plan_debug = getenv("SLUAMD_PLAN_DEBUG") != nullptr;
     double dbg_exact[2] = {0, 0}, dbg_exec[2] = {0, 0}, dbg_full[2] = {0, 0}, dbg_tiles[2] = {0, 0};
@@ -495,13 +495,13 @@ static void build_tile_lists(const HostTables &t, const std::vector<int> &lvl, c
     // per supernode, independent of every other one: its tiles in the four parts (parallel over the planner's threads, dynamic chunks -- a leaf has a
     // handful of tiles, a supernode of the top separator tens of thousands), concatenated afterwards in schedule order
     struct NodeTiles { std::vector<int4> part[4]; };
-    std::vector<NodeTiles> nt(S.nodes.size());
-    parallel_chunks((int64_t) S.nodes.size(), 16, [&](int64_t i0, int64_t i1) {
+    std::vector<NodeTiles> nt(S.nodes.h.size());
+    parallel_chunks((int64_t) S.nodes.h.size(), 16, [&](int64_t i0, int64_t i1) {
         std::vector<int8_t> cflag;
         std::vector<int> dcache;
         std::vector<Cand> cand, bulk;
         for (int64_t i = i0; i < i1; ++i) {
-            const int k = S.nodes[i], l = lvl[k];
+            const int k = S.nodes.h[i], l = lvl[k];
             std::vector<int4> *bucket = nt[i].part;
             const int nrt = t.sn_nrt[k], nct = t.sn_nct[k];
             if (!nrt || !nct) continue;
@@ -567,19 +567,19 @@ static void build_tile_lists(const HostTables &t, const std::vector<int> &lvl, c
     {
         size_t tot = 0;
         for (auto &q : nt) for (auto &v : q.part) tot += v.size();
-        S.ulist.reserve(S.ulist.size() + tot);
+        S.ulist.h.reserve(S.ulist.h.size() + tot);
     }
     for (int l = 0; l < S.nlevels; ++l) {
         const int nbig = S.n_big[l];
         for (int g = 0; g < 2; ++g) {
             const int b = S.lvl_off[l] + (g == 0 ? 0 : nbig), e = (g == 0) ? S.lvl_off[l] + nbig : S.lvl_off[l + 1];
             for (int part = 0; part < 4; ++part) {
-                const size_t first = S.ulist.size();
-                for (int i = b; i < e; ++i) S.ulist.insert(S.ulist.end(), nt[i].part[part].begin(), nt[i].part[part].end());
-                S.u_off[(2 * l + g) * 4 + part + 1] = (int) S.ulist.size();
+                const size_t first = S.ulist.h.size();
+                for (int i = b; i < e; ++i) S.ulist.h.insert(S.ulist.h.end(), nt[i].part[part].begin(), nt[i].part[part].end());
+                S.u_off[(2 * l + g) * 4 + part + 1] = (int) S.ulist.h.size();
                 if (plan_debug)
-                    for (size_t q = first; q < S.ulist.size(); ++q) {       // executed MFMA area (in the granularity at which idle waves skip) against the useful area, weighted by the source width
-                        const int4 u = S.ulist[q];
+                    for (size_t q = first; q < S.ulist.h.size(); ++q) {       // executed MFMA area (in the granularity at which idle waves skip) against the useful area, weighted by the source width
+                        const int4 u = S.ulist.h[q];
                         const int nr = t.rtile[u.y].z, nc = t.ctile[u.z].z;
                         const int ksz = (int) (t.sn_ldu[u.x]);
                         dbg_exact[g] += (double) nr * nc * ksz;
@@ -618,7 +618,7 @@ static inline double tile_cost(const Handle &H, const HostTables &t, const int4 
 // (their order inside a level is free: the scatter is atomic) and the list is cut into eight ranges of equal modelled cost; a range's tail then holds its shortest tiles.
 static void balance_bulk(const Handle &H, const HostTables &t, LevelSched &S)
 {
-    S.x_off.assign(20 * (size_t) S.nlevels, 0);
+    S.x_off.h.assign(20 * (size_t) S.nlevels, 0);
     if (H.env.balance_min_tiles <= 0 || H.opt.deterministic) return;
     struct Seg { int a, n; double c; };
     std::vector<Seg> segs;
@@ -632,18 +632,18 @@ static void balance_bulk(const Handle &H, const HostTables &t, LevelSched &S)
             segs.clear();
             for (int i = 0; i < n;) {
                 int j = i;
-                while (j < n && S.ulist[u0 + j].x == S.ulist[u0 + i].x) ++j;
-                int4 full = S.ulist[u0 + i];
+                while (j < n && S.ulist.h[u0 + j].x == S.ulist.h[u0 + i].x) ++j;
+                int4 full = S.ulist.h[u0 + i];
                 segs.push_back({i, j - i, tile_cost(H, t, full, g, 0.0)});     // (the first tile of a run: the K of the run; its ragged tiles are priced below)
                 i = j;
             }
             std::stable_sort(segs.begin(), segs.end(), [](const Seg &x, const Seg &y) { return x.c > y.c; });
             tmp.clear(); tmp.reserve(n);
-            for (const Seg &sg : segs) tmp.insert(tmp.end(), S.ulist.begin() + u0 + sg.a, S.ulist.begin() + u0 + sg.a + sg.n);
-            std::copy(tmp.begin(), tmp.end(), S.ulist.begin() + u0);
+            for (const Seg &sg : segs) tmp.insert(tmp.end(), S.ulist.h.begin() + u0 + sg.a, S.ulist.h.begin() + u0 + sg.a + sg.n);
+            std::copy(tmp.begin(), tmp.end(), S.ulist.h.begin() + u0);
             pre.assign(n + 1, 0.0);
-            for (int i = 0; i < n; ++i) pre[i + 1] = pre[i] + tile_cost(H, t, S.ulist[u0 + i], g, H.env.balance_ovh);
-            int *xo = S.x_off.data() + 10 * (size_t) (2 * l + g);
+            for (int i = 0; i < n; ++i) pre[i + 1] = pre[i] + tile_cost(H, t, S.ulist.h[u0 + i], g, H.env.balance_ovh);
+            int *xo = S.x_off.h.data() + 10 * (size_t) (2 * l + g);
             xo[0] = 0; xo[8] = n;
             for (int x = 1; x < 8; ++x) {
                 const double want = pre[n] * x / 8.0;
@@ -672,8 +672,8 @@ static void report_balance(const Handle &H, const HostTables &t, const LevelSche
             if (n <= 0) continue;
             const int slots = g == 0 ? 64 : 160;
             cost.resize(n);
-            for (int i = 0; i < n; ++i) cost[i] = tile_cost(H, t, S.ulist[u0 + i], g, ovh);
-            const int *xo = S.x_off.empty() ? nullptr : S.x_off.data() + 10 * (size_t) (2 * l + g);
+            for (int i = 0; i < n; ++i) cost[i] = tile_cost(H, t, S.ulist.h[u0 + i], g, ovh);
+            const int *xo = S.x_off.h.empty() ? nullptr : S.x_off.h.data() + 10 * (size_t) (2 * l + g);
             const bool bal = xo && xo[9] > 0;
             const int chunk = (n + 7) >> 3;
             double sum = 0, mx_x = 0, mk = 0;
@@ -698,7 +698,7 @@ static void report_balance(const Handle &H, const HostTables &t, const LevelSche
         for (int l = 0; l < S.nlevels; ++l)
             for (int g = 0; g < 2; ++g)
                 for (int u = S.u_off[(2 * l + g) * 4]; u < S.u_off[(2 * l + g) * 4 + 4]; ++u) {
-                    const int k = S.ulist[u].x;
+                    const int k = S.ulist.h[u].x;
                     int ns2 = 0, ch = chunks_of(k);
                     if (!H.h_fuse_prev.empty())
                         for (int j = 0; j < 3 && H.h_fuse_prev[3 * (size_t) k + j] >= 0; ++j) { ++ns2; ch += chunks_of(H.h_fuse_prev[3 * (size_t) k + j]); }
@@ -720,7 +720,7 @@ static void report_balance(const Handle &H, const HostTables &t, const LevelSche
 // successor to hurry for), at most SLUAMD_PANEL_SPLIT supernodes, and at least one strip on each side of the cut.
 static void build_panel_split(const Handle &H, const HostTables &t, LevelSched &S)
 {
-    S.ps_units.clear();
+    S.ps_units.h.clear();
     S.ps_off.assign(4 * (size_t) S.nlevels + 1, 0);
     const bool eligible = H.grid.Pr * H.grid.Pc == 1 && !H.z && !H.opt.deterministic && H.env.panel_split_max_nodes > 0 && !H.env.trsm_panels;
     std::vector<uint8_t> lurg, uurg;
@@ -728,12 +728,12 @@ static void build_panel_split(const Handle &H, const HostTables &t, LevelSched &
     std::vector<int> idx_of(H.hs.nsupers, -1);   // position of a supernode inside its level
     for (int l = 0; l < S.nlevels; ++l) {
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0;
-        const size_t base = S.ps_units.size();
+        const size_t base = S.ps_units.h.size();
         bool split = eligible && l > 0 && l + 1 < S.nlevels && nn <= H.env.panel_split_max_nodes && trsm_rs(H, (S.max_nsupc[l] + 31) & ~31) == 64;
         if (split) {
             loff.assign(nn + 1, 0); uoff.assign(nn + 1, 0);
             for (int i = 0; i < nn; ++i) {
-                const int k = S.nodes[n0 + i];
+                const int k = S.nodes.h[n0 + i];
                 idx_of[k] = i;
                 loff[i + 1] = loff[i] + (t.sn_nsupr[k] - t.sn_ldiag[k] + 63) / 64;
                 uoff[i + 1] = uoff[i] + (t.sn_ncolu[k] + 63) / 64;
@@ -741,7 +741,7 @@ static void build_panel_split(const Handle &H, const HostTables &t, LevelSched &
             lurg.assign(loff[nn], 0); uurg.assign(uoff[nn], 0);
             for (int g = 0; g < 2; ++g)
                 for (int u = S.u_off[(2 * l + g) * 4]; u < S.u_off[(2 * l + g) * 4 + 1]; ++u) {      // part 0 of the level's two tile-size groups
-                    const int4 e = S.ulist[u];
+                    const int4 e = S.ulist.h[u];
                     const int k = e.x;
                     const int idx = idx_of[k];
                     const int4 rt = t.rtile[e.y], ct = t.ctile[e.z];
@@ -758,11 +758,11 @@ static void build_panel_split(const Handle &H, const HostTables &t, LevelSched &
         if (split)
             for (int part = 0; part < 2; ++part) {            // [urgent L | urgent U | rest L | rest U]
                 for (int i = 0; i < nn; ++i)
-                    for (int s = loff[i]; s < loff[i + 1]; ++s) if ((lurg[s] != 0) == (part == 0)) S.ps_units.push_back(make_int2(S.nodes[n0 + i], s - loff[i]));
-                S.ps_off[4 * l + 2 * part + 1] = (int) S.ps_units.size();
+                    for (int s = loff[i]; s < loff[i + 1]; ++s) if ((lurg[s] != 0) == (part == 0)) S.ps_units.h.push_back(make_int2(S.nodes.h[n0 + i], s - loff[i]));
+                S.ps_off[4 * l + 2 * part + 1] = (int) S.ps_units.h.size();
                 for (int i = 0; i < nn; ++i)
-                    for (int c = uoff[i]; c < uoff[i + 1]; ++c) if ((uurg[c] != 0) == (part == 0)) S.ps_units.push_back(make_int2(S.nodes[n0 + i], c - uoff[i]));
-                S.ps_off[4 * l + 2 * part + 2] = (int) S.ps_units.size();
+                    for (int c = uoff[i]; c < uoff[i + 1]; ++c) if ((uurg[c] != 0) == (part == 0)) S.ps_units.h.push_back(make_int2(S.nodes.h[n0 + i], c - uoff[i]));
+                S.ps_off[4 * l + 2 * part + 2] = (int) S.ps_units.h.size();
             }
         else for (int q = 1; q <= 4; ++q) S.ps_off[4 * l + q] = (int) base;
         if (l + 1 < S.nlevels) S.ps_off[4 * (l + 1)] = S.ps_off[4 * l + 4];
@@ -785,10 +785,10 @@ static void build_schedule(Handle &H, const HostTables &t, const std::vector<int
     S.lvl_off.assign(S.nlevels + 1, 0);
     for (int k : list) S.lvl_off[lvl[k] + 1]++;
     for (int l = 0; l < S.nlevels; ++l) S.lvl_off[l + 1] += S.lvl_off[l];
-    S.nodes.resize(list.size());
+    S.nodes.h.resize(list.size());
     std::vector<int> fill(S.lvl_off.begin(), S.lvl_off.end() - (S.nlevels ? 1 : 0));
     for (int pass = 1; pass >= 0; --pass)   // big-tile supernodes first inside each level
-        for (int k : list) if ((int) t.sn_big[k] == pass) S.nodes[fill[lvl[k]]++] = k;
+        for (int k : list) if ((int) t.sn_big[k] == pass) S.nodes.h[fill[lvl[k]]++] = k;
     S.n_big.assign(S.nlevels, 0);
     for (int k : list) if (t.sn_big[k]) S.n_big[lvl[k]]++;
     S.lvl_soff.assign(S.nlevels + 1, 0);
@@ -796,38 +796,38 @@ static void build_schedule(Handle &H, const HostTables &t, const std::vector<int
     S.lvl_poff.assign(S.nlevels + 1, 0);
     for (int l = 0; l < S.nlevels; ++l) S.lvl_poff[l + 1] = S.lvl_poff[l] + (S.lvl_off[l + 1] - S.lvl_off[l]) + 1;
     const int psz = S.lvl_poff[S.nlevels];
-    S.tile_prefix.assign(S.lvl_soff[S.nlevels], 0); S.ltr_prefix.assign(psz, 0); S.utr_prefix.assign(psz, 0);
-    S.fwd_prefix.assign(psz, 0); S.bwd_prefix.assign(psz, 0); S.inv_prefix.assign(psz, 0); S.zltr_prefix.assign(psz, 0);
-    S.dg_prefix.assign(psz, 0); S.dg_off.assign(psz, 0);
-    S.finv_prefix.assign(psz, 0); S.zfwd_prefix.assign(psz, 0);
-    S.zffu_prefix.assign(psz, 0); S.zbfu_prefix.assign(psz, 0);
+    S.tile_prefix.h.assign(S.lvl_soff[S.nlevels], 0); S.ltr_prefix.h.assign(psz, 0); S.utr_prefix.h.assign(psz, 0);
+    S.fwd_prefix.h.assign(psz, 0); S.bwd_prefix.h.assign(psz, 0); S.inv_prefix.h.assign(psz, 0); S.zltr_prefix.h.assign(psz, 0);
+    S.dg_prefix.h.assign(psz, 0); S.dg_off.h.assign(psz, 0);
+    S.finv_prefix.h.assign(psz, 0); S.zfwd_prefix.h.assign(psz, 0);
+    S.zffu_prefix.h.assign(psz, 0); S.zbfu_prefix.h.assign(psz, 0);
     S.max_nsupc.assign(S.nlevels, 0);
     for (int l = 0; l < S.nlevels; ++l)
         for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i)
-            S.max_nsupc[l] = std::max(S.max_nsupc[l], nsupc_of(hs, S.nodes[i]));
+            S.max_nsupc[l] = std::max(S.max_nsupc[l], nsupc_of(hs, S.nodes.h[i]));
     for (int l = 0; l < S.nlevels; ++l) {
         int po = S.lvl_poff[l];
         int so = S.lvl_soff[l];
         const int rs = trsm_rs(H, (S.max_nsupc[l] + 31) & ~31);   // strip height of this level's TRSM launch
         for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i, ++po, ++so) {
-            const int k = S.nodes[i];
+            const int k = S.nodes.h[i];
             if (i - S.lvl_off[l] == S.n_big[l]) ++so;      // start of the small group: its own prefix, from 0
-            S.tile_prefix[so + 1] = S.tile_prefix[so] + t.sn_nrt[k] * t.sn_nct[k];
+            S.tile_prefix.h[so + 1] = S.tile_prefix.h[so] + t.sn_nrt[k] * t.sn_nct[k];
             const int nsupc = nsupc_of(hs, k);
             const int fl = t.sn_flags[k];
             const int rrows = t.sn_nsupr[k] - t.sn_ldiag[k];
             const int lrows = (fl & SNF_L_OWN) ? rrows : 0;                 // L TRSM / forward update: the owner of the L slot
             const int ucols = (fl & SNF_U_OWN) ? t.sn_ncolu[k] : 0;         // U TRSM / backward update: the owner of the U slot
-            S.ltr_prefix[po + 1] = S.ltr_prefix[po] + (lrows + rs - 1) / rs;
-            S.utr_prefix[po + 1] = S.utr_prefix[po] + (ucols + rs - 1) / rs;
-            S.inv_prefix[po + 1] = S.inv_prefix[po] + ((fl & SNF_HAS_DIAG) ? 2 * ((nsupc + 31) / 32) : 0);
-            S.zltr_prefix[po + 1] = S.zltr_prefix[po] + (lrows + 63) / 64;
-            S.fwd_prefix[po + 1] = S.fwd_prefix[po] + (lrows + 63) / 64;
-            S.zfwd_prefix[po + 1] = S.zfwd_prefix[po] + (lrows + 255) / 256;
-            S.zffu_prefix[po + 1] = S.zffu_prefix[po] + ((fl & SNF_OWN_DIAG) ? std::max(1, (lrows + 255) / 256) : (lrows + 255) / 256);
-            S.zbfu_prefix[po + 1] = S.zbfu_prefix[po] + ((fl & SNF_OWN_DIAG) ? std::max(1, (ucols + 63) / 64) : (ucols + 63) / 64);
-            S.bwd_prefix[po + 1] = S.bwd_prefix[po] + (ucols + 63) / 64;
-            S.finv_prefix[po + 1] = S.finv_prefix[po] + ((fl & (xy_gemm ? SNF_HAS_DIAG : SNF_OWN_DIAG)) ? 2 * ((nsupc + 15) / 16) : 0);    // FIS = 16-row identity strips
+            S.ltr_prefix.h[po + 1] = S.ltr_prefix.h[po] + (lrows + rs - 1) / rs;
+            S.utr_prefix.h[po + 1] = S.utr_prefix.h[po] + (ucols + rs - 1) / rs;
+            S.inv_prefix.h[po + 1] = S.inv_prefix.h[po] + ((fl & SNF_HAS_DIAG) ? 2 * ((nsupc + 31) / 32) : 0);
+            S.zltr_prefix.h[po + 1] = S.zltr_prefix.h[po] + (lrows + 63) / 64;
+            S.fwd_prefix.h[po + 1] = S.fwd_prefix.h[po] + (lrows + 63) / 64;
+            S.zfwd_prefix.h[po + 1] = S.zfwd_prefix.h[po] + (lrows + 255) / 256;
+            S.zffu_prefix.h[po + 1] = S.zffu_prefix.h[po] + ((fl & SNF_OWN_DIAG) ? std::max(1, (lrows + 255) / 256) : (lrows + 255) / 256);
+            S.zbfu_prefix.h[po + 1] = S.zbfu_prefix.h[po] + ((fl & SNF_OWN_DIAG) ? std::max(1, (ucols + 63) / 64) : (ucols + 63) / 64);
+            S.bwd_prefix.h[po + 1] = S.bwd_prefix.h[po] + (ucols + 63) / 64;
+            S.finv_prefix.h[po + 1] = S.finv_prefix.h[po] + ((fl & (xy_gemm ? SNF_HAS_DIAG : SNF_OWN_DIAG)) ? 2 * ((nsupc + 15) / 16) : 0);    // FIS = 16-row identity strips
         }
     }
     // solve units as explicit lists, per level [urgent | bulk]: a strip of L(:,k) is urgent when one of its rows belongs to a supernode
@@ -839,7 +839,7 @@ static void build_schedule(Handle &H, const HostTables &t, const std::vector<int
         for (int l = 0; l < S.nlevels; ++l)
             for (int part = 0; part < 2; ++part) {
                 for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i) {
-                    const int k = S.nodes[i], fl = t.sn_flags[k];
+                    const int k = S.nodes.h[i], fl = t.sn_flags[k];
                     const int ldiag = t.sn_ldiag[k];
                     const int nstrip = (fl & SNF_L_OWN) ? (t.sn_nsupr[k] - ldiag + 63) / 64 : 0;
                     urg.assign(nstrip, 0);
@@ -849,7 +849,7 @@ static void build_schedule(Handle &H, const HostTables &t, const std::vector<int
                         const int r0 = t.lb_rowoff[bi] - ldiag, r1 = r0 + t.lb_nbrow[bi] - 1;
                         for (int sidx = r0 / 64; sidx <= r1 / 64; ++sidx) urg[sidx] = 1;
                     }
-                    for (int sidx = 0; sidx < nstrip; ++sidx) if ((urg[sidx] != 0) == (part == 0)) S.fwd_units.push_back(make_int2(k, sidx));
+                    for (int sidx = 0; sidx < nstrip; ++sidx) if ((urg[sidx] != 0) == (part == 0)) S.fwd_units.h.push_back(make_int2(k, sidx));
                     const int nchunk = (fl & SNF_U_OWN) ? (t.sn_ncolu[k] + 63) / 64 : 0;
                     urg.assign(nchunk, 0);
                     for (int b = 0; b < t.sn_nub[k] && nchunk; ++b) {
@@ -858,20 +858,20 @@ static void build_schedule(Handle &H, const HostTables &t, const std::vector<int
                         const int c0 = t.ub_stcol[bi], c1 = c0 + t.ub_ncols[bi] - 1;
                         for (int c = c0 / 64; c <= c1 / 64; ++c) urg[c] = 1;
                     }
-                    for (int c = 0; c < nchunk; ++c) if ((urg[c] != 0) == (part == 0)) S.bwd_units.push_back(make_int2(k, c));
+                    for (int c = 0; c < nchunk; ++c) if ((urg[c] != 0) == (part == 0)) S.bwd_units.h.push_back(make_int2(k, c));
                 }
-                S.fu_off[2 * l + part + 1] = (int) S.fwd_units.size();
-                S.bu_off[2 * l + part + 1] = (int) S.bwd_units.size();
+                S.fu_off[2 * l + part + 1] = (int) S.fwd_units.h.size();
+                S.bu_off[2 * l + part + 1] = (int) S.bwd_units.h.size();
             }
     }
-    S.diag_units.clear(); S.du_off.assign(S.nlevels + 1, 0);
+    S.diag_units.h.clear(); S.du_off.assign(S.nlevels + 1, 0);
     for (int l = 0; l < S.nlevels; ++l) {
         for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i) {
-            const int k = S.nodes[i];
+            const int k = S.nodes.h[i];
             if (!(t.sn_flags[k] & SNF_OWN_DIAG)) continue;
-            for (int st = 0; st < (nsupc_of(hs, k) + 63) / 64; ++st) S.diag_units.push_back(make_int2(k, st));
+            for (int st = 0; st < (nsupc_of(hs, k) + 63) / 64; ++st) S.diag_units.h.push_back(make_int2(k, st));
         }
-        S.du_off[l + 1] = (int) S.diag_units.size();
+        S.du_off[l + 1] = (int) S.diag_units.h.size();
     }
     H.setup.lap("sched.prefixes_sweep_units");
     // K-fused chain groups of up to four supernodes (a, a+1, a+2, a+3) in consecutive levels: every member but the last
@@ -894,7 +894,7 @@ static void build_schedule(Handle &H, const HostTables &t, const std::vector<int
             const int maxprev = (!xy_layer && S.nlevels - (l + 1) > H.env.fuse_tail_guard && S.lvl_off[l + 2] - S.lvl_off[l + 1] >= H.env.fuse_group_min_nodes) ? maxprev_env : 1;
             cands.clear();
             for (int i = S.lvl_off[l + 1]; i < S.lvl_off[l + 2]; ++i) {
-                const int b = S.nodes[i], a = b - 1;
+                const int b = S.nodes.h[i], a = b - 1;
                 if (a < 0 || lvl[a] != l) continue;
                 if (!H.env.fuse_small && (!t.sn_big[a] || !t.sn_big[b])) continue;      // (SLUAMD_FUSE_SMALL: pairs whose successor runs the 64 x 64 configuration too)
                 PairCand c;
@@ -969,15 +969,15 @@ static void build_schedule(Handle &H, const HostTables &t, const std::vector<int
 static bool build_join(Handle &H, LevelSched &S, const HostTables &t)
 {
     const HostStruct &hs = H.hs;
-    const std::vector<int> &lev = S.sn_level;
+    const std::vector<int> &lev = S.sn_level.h;
     const int nl = S.nlevels;
     auto lohi = [](int64_t v, int &lo, int &hi) { lo = (int) (uint32_t) v; hi = (int) (v >> 32); };
     auto grp = [&](int k) { return H.grp_of.empty() ? -1 : H.grp_of[k]; };
     struct Src { int k, bi; };
     std::vector<std::vector<Src>> srcs(hs.nsupers);
-    std::vector<int> near_off(hs.nsupers, 0), near_cnt(hs.nsupers, 0);      // per supernode: its near columns in S.jb_aux
+    std::vector<int> near_off(hs.nsupers, 0), near_cnt(hs.nsupers, 0);      // per supernode: its near columns in S.jb_aux.h
     // near flags + the sources of every supernode
-    for (int k : S.nodes) {
+    for (int k : S.nodes.h) {
         const int l = lev[k], fl = t.sn_flags[k], gk = grp(k);
         if (fl & SNF_L_OWN)
             for (int b = 0; b < t.sn_nlb[k]; ++b) {
@@ -1005,7 +1005,7 @@ static bool build_join(Handle &H, LevelSched &S, const HostTables &t)
     for (int l = 0; l < nl; ++l) {
         // regular units of every supernode of the level (members of groups included), and the near-column lists of the backward joined units
         for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i) {
-            const int k = S.nodes[i], fl = t.sn_flags[k];
+            const int k = S.nodes.h[i], fl = t.sn_flags[k];
             const int fst = hs.xsup[k], ns = hs.xsup[k + 1] - fst;
             if (fl & SNF_L_OWN) {
                 const int ldiag = t.sn_ldiag[k], lda = t.sn_nsupr[k];
@@ -1015,7 +1015,7 @@ static bool build_join(Handle &H, LevelSched &S, const HostTables &t)
                     for (int r = 0; r < nr; ++r) nnear += H.h_lrow_near[t.sn_lrow[k] + row0 + r] != 0;
                     if (nnear == nr) continue;
                     int4 b; lohi(t.sn_lval[k] + row0, b.x, b.y); lohi(t.sn_lrow[k] + row0, b.z, b.w);
-                    S.jfu_recs.push_back(make_int4(fst, ns | (nnear ? 1 << 16 : 0), lda, row0)); S.jfu_recs.push_back(b);
+                    S.jfu_recs.h.push_back(make_int4(fst, ns | (nnear ? 1 << 16 : 0), lda, row0)); S.jfu_recs.h.push_back(b);
                 }
             }
             if (fl & SNF_U_OWN) {
@@ -1026,19 +1026,19 @@ static bool build_join(Handle &H, LevelSched &S, const HostTables &t)
                     for (int c = 0; c < nc; ++c) nnear += H.h_ucol_near[t.sn_ucol[k] + c0 + c] != 0;
                     if (nnear == nc) continue;
                     int4 b; lohi(t.sn_ucol[k] + c0, b.x, b.y); lohi(t.sn_uval[k], b.z, b.w);
-                    S.jbu_recs.push_back(make_int4(fst, ns | (nnear ? 1 << 16 : 0), nc, 0)); S.jbu_recs.push_back(b);
+                    S.jbu_recs.h.push_back(make_int4(fst, ns | (nnear ? 1 << 16 : 0), nc, 0)); S.jbu_recs.h.push_back(b);
                 }
-                near_off[k] = (int) S.jb_aux.size();
+                near_off[k] = (int) S.jb_aux.h.size();
                 for (int c = 0; c < ncolu; ++c) {
                     const int64_t ci = t.sn_ucol[k] + c;
-                    if (H.h_ucol_near[ci] == 1) S.jb_aux.push_back(make_int4(t.ucol_ld[ci], t.ucol_cp[ci], t.ucol_gc[ci], 0));
+                    if (H.h_ucol_near[ci] == 1) S.jb_aux.h.push_back(make_int4(t.ucol_ld[ci], t.ucol_cp[ci], t.ucol_gc[ci], 0));
                 }
-                near_cnt[k] = (int) S.jb_aux.size() - near_off[k];
+                near_cnt[k] = (int) S.jb_aux.h.size() - near_off[k];
             }
         }
         // joined units: one node = one supernode, or one merged group (emitted at its first member; all members are in this level)
         for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i) {
-            const int k = S.nodes[i];
+            const int k = S.nodes.h[i];
             if (!(t.sn_flags[k] & SNF_OWN_DIAG)) continue;
             const int gk = grp(k);
             int nm = 1, mem[4] = {k, 0, 0, 0}, mo[4] = {0, 0, 0, 0}, mw[4] = {hs.xsup[k + 1] - hs.xsup[k], 0, 0, 0};
@@ -1062,11 +1062,11 @@ static bool build_join(Handle &H, LevelSched &S, const HostTables &t)
                 }
                 const int nsrc = (int) sv.size() / 2;
                 int ovf = 0;
-                if (nsrc > 3) { ovf = (int) S.jf_aux.size() / 2; S.jf_aux.insert(S.jf_aux.end(), sv.begin() + 6, sv.end()); }
+                if (nsrc > 3) { ovf = (int) S.jf_aux.h.size() / 2; S.jf_aux.h.insert(S.jf_aux.h.end(), sv.begin() + 6, sv.end()); }
                 for (int st = c; st < nb; ++st) {
                     int4 b; lohi(linv, b.x, b.y); b.z = nsrc; b.w = ovf;
-                    S.jf_recs.push_back(make_int4(fst, ns, st, c)); S.jf_recs.push_back(b);
-                    for (int q = 0; q < 6; ++q) S.jf_recs.push_back(q < (int) sv.size() ? sv[q] : make_int4(0, 0, 0, 0));
+                    S.jf_recs.h.push_back(make_int4(fst, ns, st, c)); S.jf_recs.h.push_back(b);
+                    for (int q = 0; q < 6; ++q) S.jf_recs.h.push_back(q < (int) sv.size() ? sv[q] : make_int4(0, 0, 0, 0));
                 }
             }
             // backward: block (s, c), s <= c; near columns = every column of the next level in the U row of the member that holds block c
@@ -1075,12 +1075,12 @@ static bool build_join(Handle &H, LevelSched &S, const HostTables &t)
                 for (int st = 0; st <= c; ++st) {
                     int4 b; lohi(uinv, b.x, b.y); b.z = near_off[km]; b.w = near_cnt[km];
                     int4 u; lohi(t.sn_uval[km], u.x, u.y); u.z = mo[m]; u.w = mw[m];
-                    S.jb_recs.push_back(make_int4(fst, ns, st, c)); S.jb_recs.push_back(b); S.jb_recs.push_back(u); S.jb_recs.push_back(make_int4(0, 0, 0, 0));
+                    S.jb_recs.h.push_back(make_int4(fst, ns, st, c)); S.jb_recs.h.push_back(b); S.jb_recs.h.push_back(u); S.jb_recs.h.push_back(make_int4(0, 0, 0, 0));
                 }
             }
         }
-        S.jf_off[l + 1] = (int) S.jf_recs.size() / 8; S.jb_off[l + 1] = (int) S.jb_recs.size() / 4;
-        S.jfu_off[l + 1] = (int) S.jfu_recs.size() / 2; S.jbu_off[l + 1] = (int) S.jbu_recs.size() / 2;
+        S.jf_off[l + 1] = (int) S.jf_recs.h.size() / 8; S.jb_off[l + 1] = (int) S.jb_recs.h.size() / 4;
+        S.jfu_off[l + 1] = (int) S.jfu_recs.h.size() / 2; S.jbu_off[l + 1] = (int) S.jbu_recs.h.size() / 2;
     }
     return true;
 }
@@ -1180,20 +1180,20 @@ static void build_solve_sched(Handle &H, const HostTables &t, const std::vector<
 {
     const HostStruct &hs = H.hs;
     S.nlevels = nslev;
-    S.sn_level = slev;
+    S.sn_level.h = slev;
     S.lvl_off.assign(nslev + 1, 0);
     for (int k : list) S.lvl_off[slev[k] + 1]++;
     for (int l = 0; l < nslev; ++l) S.lvl_off[l + 1] += S.lvl_off[l];
-    S.nodes.resize(list.size());
+    S.nodes.h.resize(list.size());
     std::vector<int> fill(S.lvl_off.begin(), S.lvl_off.end() - (nslev ? 1 : 0));
-    for (int k : list) S.nodes[fill[slev[k]]++] = k;
+    for (int k : list) S.nodes.h[fill[slev[k]]++] = k;
     S.n_big.assign(nslev, 0);
     S.lvl_soff.assign(nslev + 1, 0); S.lvl_poff.assign(nslev + 1, 0);
     for (int l = 0; l < nslev; ++l) { S.lvl_soff[l + 1] = S.lvl_soff[l] + (S.lvl_off[l + 1] - S.lvl_off[l]) + 2; S.lvl_poff[l + 1] = S.lvl_poff[l] + (S.lvl_off[l + 1] - S.lvl_off[l]) + 1; }
     S.max_nsupc.assign(nslev, 0);
     for (int l = 0; l < nslev; ++l)
         for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i) {
-            const int k = S.nodes[i];
+            const int k = S.nodes.h[i];
             const int w = H.grp_of[k] >= 0 ? H.groups[H.grp_of[k]].nG : nsupc_of(hs, k);      // the strips of a group stage the group's whole right-hand side
             S.max_nsupc[l] = std::max(S.max_nsupc[l], w);
         }
@@ -1202,7 +1202,7 @@ static void build_solve_sched(Handle &H, const HostTables &t, const std::vector<
     for (int l = 0; l < nslev; ++l)
         for (int part = 0; part < 2; ++part) {
             for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i) {
-                const int k = S.nodes[i], fl = t.sn_flags[k];
+                const int k = S.nodes.h[i], fl = t.sn_flags[k];
                 const int ldiag = t.sn_ldiag[k];
                 const int nstrip = (fl & SNF_L_OWN) ? (t.sn_nsupr[k] - ldiag + 63) / 64 : 0;
                 urg.assign(nstrip, 0);
@@ -1212,7 +1212,7 @@ static void build_solve_sched(Handle &H, const HostTables &t, const std::vector<
                     const int r0 = t.lb_rowoff[bi] - ldiag, r1 = r0 + t.lb_nbrow[bi] - 1;
                     for (int sidx = r0 / 64; sidx <= r1 / 64; ++sidx) urg[sidx] = 1;
                 }
-                for (int sidx = 0; sidx < nstrip; ++sidx) if ((urg[sidx] != 0) == (part == 0)) S.fwd_units.push_back(make_int2(k, sidx));
+                for (int sidx = 0; sidx < nstrip; ++sidx) if ((urg[sidx] != 0) == (part == 0)) S.fwd_units.h.push_back(make_int2(k, sidx));
                 const int nchunk = (fl & SNF_U_OWN) ? (t.sn_ncolu[k] + 63) / 64 : 0;
                 urg.assign(nchunk, 0);
                 for (int b = 0; b < t.sn_nub[k] && nchunk; ++b) {
@@ -1221,21 +1221,21 @@ static void build_solve_sched(Handle &H, const HostTables &t, const std::vector<
                     const int c0 = t.ub_stcol[bi], c1 = c0 + t.ub_ncols[bi] - 1;
                     for (int c = c0 / 64; c <= c1 / 64; ++c) urg[c] = 1;
                 }
-                for (int c = 0; c < nchunk; ++c) if ((urg[c] != 0) == (part == 0)) S.bwd_units.push_back(make_int2(k, c));
+                for (int c = 0; c < nchunk; ++c) if ((urg[c] != 0) == (part == 0)) S.bwd_units.h.push_back(make_int2(k, c));
             }
-            S.fu_off[2 * l + part + 1] = (int) S.fwd_units.size();
-            S.bu_off[2 * l + part + 1] = (int) S.bwd_units.size();
+            S.fu_off[2 * l + part + 1] = (int) S.fwd_units.h.size();
+            S.bu_off[2 * l + part + 1] = (int) S.bwd_units.h.size();
         }
-    S.diag_units.clear(); S.du_off.assign(nslev + 1, 0);
+    S.diag_units.h.clear(); S.du_off.assign(nslev + 1, 0);
     for (int l = 0; l < nslev; ++l) {
         for (int i = S.lvl_off[l]; i < S.lvl_off[l + 1]; ++i) {
-            const int k = S.nodes[i];
+            const int k = S.nodes.h[i];
             if (!(t.sn_flags[k] & SNF_OWN_DIAG)) continue;
             int w = nsupc_of(hs, k);
             if (H.grp_of[k] >= 0) { const Handle::SolveGroup &G = H.groups[H.grp_of[k]]; if (G.k[0] != k) continue; w = G.nG; }      // the group's strips, at its first member
-            for (int st = 0; st < (w + 63) / 64; ++st) S.diag_units.push_back(make_int2(k, st));
+            for (int st = 0; st < (w + 63) / 64; ++st) S.diag_units.h.push_back(make_int2(k, st));
         }
-        S.du_off[l + 1] = (int) S.diag_units.size();
+        S.du_off[l + 1] = (int) S.diag_units.h.size();
     }
     S.lvl_has_group.assign(nslev, 0);
     for (int k : list) if (H.grp_of[k] >= 0) S.lvl_has_group[slev[k]] = 1;
@@ -1243,48 +1243,32 @@ static void build_solve_sched(Handle &H, const HostTables &t, const std::vector<
     S.u_off.assign(8 * nslev + 1, 0);
     S.ps_off.assign(4 * (size_t) nslev + 1, 0);
     const int psz = S.lvl_poff[nslev];
-    for (auto *v : {&S.tile_prefix}) v->assign(S.lvl_soff[nslev], 0);
-    for (auto *v : {&S.ltr_prefix, &S.utr_prefix, &S.fwd_prefix, &S.bwd_prefix, &S.inv_prefix, &S.zltr_prefix, &S.dg_prefix, &S.finv_prefix, &S.zfwd_prefix, &S.zffu_prefix, &S.zbfu_prefix})
+    for (auto *v : {&S.tile_prefix.h}) v->assign(S.lvl_soff[nslev], 0);
+    for (auto *v : {&S.ltr_prefix.h, &S.utr_prefix.h, &S.fwd_prefix.h, &S.bwd_prefix.h, &S.inv_prefix.h, &S.zltr_prefix.h, &S.dg_prefix.h, &S.finv_prefix.h, &S.zfwd_prefix.h, &S.zffu_prefix.h, &S.zbfu_prefix.h})
         v->assign(psz, 0);
-    S.dg_off.assign(psz, 0);
+    S.dg_off.h.assign(psz, 0);
 }
 
 static int upload_schedule(Handle &H, LevelSched &S, const HostTables &t)
 {
     int rc;
-    if ((rc = upload(H.d_misc, S.nodes, &S.d_nodes, "the table nodes"))) return rc;
-    if ((rc = upload(H.d_misc, S.tile_prefix, &S.d_tile_prefix, "the table tile_prefix"))) return rc;
-    if ((rc = upload(H.d_misc, S.ltr_prefix, &S.d_ltr_prefix, "the table ltr_prefix"))) return rc;
-    if ((rc = upload(H.d_misc, S.utr_prefix, &S.d_utr_prefix, "the table utr_prefix"))) return rc;
-    if ((rc = upload(H.d_misc, S.fwd_prefix, &S.d_fwd_prefix, "the table fwd_prefix"))) return rc;
-    if ((rc = upload(H.d_misc, S.bwd_prefix, &S.d_bwd_prefix, "the table bwd_prefix"))) return rc;
-    if ((rc = upload(H.d_misc, S.inv_prefix, &S.d_inv_prefix, "the table inv_prefix"))) return rc;
-    if ((rc = upload(H.d_misc, S.zltr_prefix, &S.d_zltr_prefix, "the table zltr_prefix"))) return rc;
-    if ((rc = upload(H.d_misc, S.sn_level, &S.d_sn_level, "the table sn_level"))) return rc;
-    if ((rc = upload(H.d_misc, S.ulist, &S.d_ulist, "the table ulist"))) return rc;
-    if ((rc = upload(H.d_misc, S.x_off, &S.d_x_off, "the table x_off"))) return rc;
-    if ((rc = upload(H.d_misc, S.dg_prefix, &S.d_dg_prefix, "the table dg_prefix"))) return rc;
-    if ((rc = upload(H.d_misc, S.zfwd_prefix, &S.d_zfwd_prefix, "the table zfwd_prefix"))) return rc;
-    if (H.z) {
-        if ((rc = upload(H.d_misc, S.zffu_prefix, &S.d_zffu_prefix, "the table zffu_prefix"))) return rc;
-        if ((rc = upload(H.d_misc, S.zbfu_prefix, &S.d_zbfu_prefix, "the table zbfu_prefix"))) return rc;
-    }
-    if ((rc = upload(H.d_misc, S.finv_prefix, &S.d_finv_prefix, "the table finv_prefix"))) return rc;
-    if ((rc = upload(H.d_misc, S.dg_off, &S.d_dg_off, "the table dg_off"))) return rc;
-    if ((rc = upload(H.d_misc, S.fwd_units, &S.d_fwd_units, "the table fwd_units"))) return rc;
-    if ((rc = upload(H.d_misc, S.bwd_units, &S.d_bwd_units, "the table bwd_units"))) return rc;
-    if ((rc = upload(H.d_misc, S.diag_units, &S.d_diag_units, "the table diag_units"))) return rc;
-    if (!S.ps_units.empty()) if ((rc = upload(H.d_misc, S.ps_units, &S.d_ps_units, "the table ps_units"))) return rc;
+    // one line per table, in upload order; the error message of a failed allocation names the table
+#define UPLOAD(x) if ((rc = S.x.upload(H.d_misc, "the table " #x))) return rc
+    UPLOAD(nodes); UPLOAD(tile_prefix); UPLOAD(ltr_prefix); UPLOAD(utr_prefix); UPLOAD(fwd_prefix); UPLOAD(bwd_prefix); UPLOAD(inv_prefix); UPLOAD(zltr_prefix); UPLOAD(sn_level); UPLOAD(ulist); UPLOAD(x_off);
+    UPLOAD(dg_prefix); UPLOAD(zfwd_prefix);
+    if (H.z) { UPLOAD(zffu_prefix); UPLOAD(zbfu_prefix); }
+    UPLOAD(finv_prefix); UPLOAD(dg_off); UPLOAD(fwd_units); UPLOAD(bwd_units); UPLOAD(diag_units);
+    if (!S.ps_units.h.empty()) UPLOAD(ps_units);
     H.setup.lap("upload.schedule_lists");
     if (!H.z) {
         // unit records (k_sweep / k_fwd_update / k_bwd_update): the scalars of every unit in the order of the unit lists
         const HostStruct &hs = H.hs;
         auto lohi = [](int64_t v, int &lo, int &hi) { lo = (int) (uint32_t) v; hi = (int) (v >> 32); };
-        S.fwd_recs.resize(2 * S.fwd_units.size()); S.bwd_recs.resize(2 * S.bwd_units.size()); S.diag_recs.resize(2 * S.diag_units.size());
+        S.fwd_recs.h.resize(2 * S.fwd_units.h.size()); S.bwd_recs.h.resize(2 * S.bwd_units.h.size()); S.diag_recs.h.resize(2 * S.diag_units.h.size());
         const bool grouped = !S.lvl_has_group.empty() && !H.grp_of.empty() && !H.h_lrow_near.empty();
         auto grp = [&](int k) { return grouped ? H.grp_of[k] : -1; };
         if (grouped)        // the dead rows / columns of the members (see build_join), before the records that announce them
-            for (int k : S.nodes) {
+            for (int k : S.nodes.h) {
                 const int gk = grp(k);
                 if (gk < 0) continue;
                 if (t.sn_flags[k] & SNF_L_OWN)
@@ -1298,52 +1282,46 @@ static int upload_schedule(Handle &H, LevelSched &S, const HostTables &t)
                         if (t.ub_ncols[bi] && grp(t.ub_gid[bi]) == gk) for (int c = 0; c < t.ub_ncols[bi]; ++c) H.h_ucol_near[t.sn_ucol[k] + t.ub_stcol[bi] + c] = 2;
                     }
             }
-        for (size_t u = 0; u < S.fwd_units.size(); ++u) {
-            const int k = S.fwd_units[u].x, strip = S.fwd_units[u].y;
+        for (size_t u = 0; u < S.fwd_units.h.size(); ++u) {
+            const int k = S.fwd_units.h[u].x, strip = S.fwd_units.h[u].y;
             const int fst = hs.xsup[k], ns = hs.xsup[k + 1] - fst, row0 = t.sn_ldiag[k] + strip * 64;
             int4 b; lohi(t.sn_lval[k] + row0, b.x, b.y); lohi(t.sn_lrow[k] + row0, b.z, b.w);
             int dead = 0;
             if (grp(k) >= 0) for (int r = row0; r < std::min(row0 + 64, t.sn_nsupr[k]); ++r) dead |= H.h_lrow_near[t.sn_lrow[k] + r] == 2;
-            S.fwd_recs[2 * u] = make_int4(fst, ns | (dead ? 2 << 16 : 0), t.sn_nsupr[k], row0); S.fwd_recs[2 * u + 1] = b;
+            S.fwd_recs.h[2 * u] = make_int4(fst, ns | (dead ? 2 << 16 : 0), t.sn_nsupr[k], row0); S.fwd_recs.h[2 * u + 1] = b;
         }
-        for (size_t u = 0; u < S.bwd_units.size(); ++u) {
-            const int k = S.bwd_units[u].x, chunk = S.bwd_units[u].y;
+        for (size_t u = 0; u < S.bwd_units.h.size(); ++u) {
+            const int k = S.bwd_units.h[u].x, chunk = S.bwd_units.h[u].y;
             const int fst = hs.xsup[k], ns = hs.xsup[k + 1] - fst, nc = std::min(64, t.sn_ncolu[k] - chunk * 64);
             int4 b; lohi(t.sn_ucol[k] + (int64_t) chunk * 64, b.x, b.y); lohi(t.sn_uval[k], b.z, b.w);
             int dead = 0;
             if (grp(k) >= 0) for (int c = 0; c < nc; ++c) dead |= H.h_ucol_near[t.sn_ucol[k] + (int64_t) chunk * 64 + c] == 2;
-            S.bwd_recs[2 * u] = make_int4(fst, ns | (dead ? 2 << 16 : 0), nc, 0); S.bwd_recs[2 * u + 1] = b;
+            S.bwd_recs.h[2 * u] = make_int4(fst, ns | (dead ? 2 << 16 : 0), nc, 0); S.bwd_recs.h[2 * u + 1] = b;
         }
-        for (size_t u = 0; u < S.diag_units.size(); ++u) {
-            const int k = S.diag_units[u].x, strip = S.diag_units[u].y;
+        for (size_t u = 0; u < S.diag_units.h.size(); ++u) {
+            const int k = S.diag_units.h[u].x, strip = S.diag_units.h[u].y;
             const int fst = hs.xsup[k];
             int ns = hs.xsup[k + 1] - fst;
             int64_t li = t.sn_inv[k];
             if (grp(k) >= 0) { const Handle::SolveGroup &G = H.groups[grp(k)]; ns = G.nG; li = G.ginv; }
             int4 b; lohi(li, b.x, b.y); lohi(li + (int64_t) ns * ns, b.z, b.w);
-            S.diag_recs[2 * u] = make_int4(fst, ns, strip, 0); S.diag_recs[2 * u + 1] = b;
+            S.diag_recs.h[2 * u] = make_int4(fst, ns, strip, 0); S.diag_recs.h[2 * u + 1] = b;
         }
-        if ((rc = upload(H.d_misc, S.fwd_recs, &S.d_fwd_recs, "the table fwd_recs"))) return rc;
-        if ((rc = upload(H.d_misc, S.bwd_recs, &S.d_bwd_recs, "the table bwd_recs"))) return rc;
-        if ((rc = upload(H.d_misc, S.diag_recs, &S.d_diag_recs, "the table diag_recs"))) return rc;
-        std::vector<int4>().swap(S.fwd_recs); std::vector<int4>().swap(S.bwd_recs); std::vector<int4>().swap(S.diag_recs);
+        UPLOAD(fwd_recs); UPLOAD(bwd_recs); UPLOAD(diag_recs);
+        S.fwd_recs.drop_host(); S.bwd_recs.drop_host(); S.diag_recs.drop_host();
         H.setup.lap("upload.sweep_unit_records");
         S.join = false;
         if (H.grid.Pr * H.grid.Pc == 1 && H.env.solve_join && !H.h_lrow_near.empty() && !S.no_join) {
             const std::vector<uint8_t> keep_l = H.h_lrow_near, keep_u = H.h_ucol_near;
             if (build_join(H, S, t)) {
                 S.join = true;
-                if ((rc = upload(H.d_misc, S.jf_recs, &S.d_jf_recs, "the table jf_recs"))) return rc;
-                if ((rc = upload(H.d_misc, S.jf_aux, &S.d_jf_aux, "the table jf_aux"))) return rc;
-                if ((rc = upload(H.d_misc, S.jb_recs, &S.d_jb_recs, "the table jb_recs"))) return rc;
-                if ((rc = upload(H.d_misc, S.jb_aux, &S.d_jb_aux, "the table jb_aux"))) return rc;
-                if ((rc = upload(H.d_misc, S.jfu_recs, &S.d_jfu_recs, "the table jfu_recs"))) return rc;
-                if ((rc = upload(H.d_misc, S.jbu_recs, &S.d_jbu_recs, "the table jbu_recs"))) return rc;
+                UPLOAD(jf_recs); UPLOAD(jf_aux); UPLOAD(jb_recs); UPLOAD(jb_aux); UPLOAD(jfu_recs); UPLOAD(jbu_recs);
             } else { H.h_lrow_near = keep_l; H.h_ucol_near = keep_u; }
-            for (auto *v : {&S.jf_recs, &S.jf_aux, &S.jb_recs, &S.jb_aux, &S.jfu_recs, &S.jbu_recs}) std::vector<int4>().swap(*v);
+            for (auto *v : {&S.jf_recs, &S.jf_aux, &S.jb_recs, &S.jb_aux, &S.jfu_recs, &S.jbu_recs}) v->drop_host();
             H.setup.lap("upload.joined_sweep_tables");
         }
     }
+#undef UPLOAD
     return 0;
 }
 
@@ -1371,7 +1349,7 @@ int plan_trans_exchange(Handle *H)
         for (LevelSched &S : H->sched) {
             S.xt_red_send.assign(S.nlevels, {}); S.xt_red_recv.assign(S.nlevels, {}); S.xt_bc_send.assign(S.nlevels, {}); S.xt_bc_recv.assign(S.nlevels, {});
             for (int l = 0; l < S.nlevels; ++l) {
-                std::vector<int> nodes(S.nodes.begin() + S.lvl_off[l], S.nodes.begin() + S.lvl_off[l + 1]);
+                std::vector<int> nodes(S.nodes.h.begin() + S.lvl_off[l], S.nodes.h.begin() + S.lvl_off[l + 1]);
                 std::sort(nodes.begin(), nodes.end());
                 for (int r2 = 0; r2 < g.Pr; ++r2) {       // partial sums: along my process column, to / at the diagonal owner
                     if (r2 == g.r) continue;
@@ -1719,19 +1697,19 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
                 {
                     std::vector<int> order(nn);
                     std::iota(order.begin(), order.end(), 0);
-                    std::sort(order.begin(), order.end(), [&](int a, int b) { return S.nodes[n0 + a] < S.nodes[n0 + b]; });
+                    std::sort(order.begin(), order.end(), [&](int a, int b) { return S.nodes.h[n0 + a] < S.nodes.h[n0 + b]; });
                     int64_t o = 0;
                     for (int i : order) {
-                        const int k = S.nodes[n0 + i];
+                        const int k = S.nodes.h[n0 + i];
                         off_of[i] = o;
                         if (t.sn_flags[k] & SNF_OWN_DIAG) o += (int64_t) nsupc_of(hs, k) * nsupc_of(hs, k);
                     }
                 }
                 for (int i = 0; i < nn; ++i) {
-                    const int k = S.nodes[n0 + i];
+                    const int k = S.nodes.h[n0 + i];
                     const int64_t sz = (t.sn_flags[k] & SNF_OWN_DIAG) ? (int64_t) nsupc_of(hs, k) * nsupc_of(hs, k) : 0;
-                    S.dg_prefix[po + i + 1] = S.dg_prefix[po + i] + (int) ((sz + 1023) / 1024);
-                    S.dg_off[po + i] = off_of[i];
+                    S.dg_prefix.h[po + i + 1] = S.dg_prefix.h[po + i] + (int) ((sz + 1023) / 1024);
+                    S.dg_off.h[po + i] = off_of[i];
                 }
             }
         }
@@ -1814,7 +1792,7 @@ int plan_and_upload(Handle *H, SlotInput &in, HostTables &t)
     }
     H->st.reserved_i = H->fused_pairs;   // K-fused supernode pairs (diagnostic)
     H->st.schur_tiles = 0;               // until the first factorisation: the PLANNED tile executions of one factorisation (list schedules)
-    for (auto &S : H->sched) H->st.schur_tiles += (int64_t) S.ulist.size();
+    for (auto &S : H->sched) H->st.schur_tiles += (int64_t) S.ulist.h.size();
     if ((rc = H->d_info.alloc(8, H->device, "the factorisation's info words"))) return rc;
     if (H->z) {
         if ((rc = H->d_ztickets.alloc(std::max(ns, 1), H->device, "the ticket counters of the fused backward links"))) return rc;

@@ -77,6 +77,8 @@ static int upload(DevBag &keep, const std::vector<Tv> &h, Tv **d, const char *wh
     return 0;
 }
 
+template <class T> int PlanTable<T>::upload(DevBag &keep, const char *what) { return sluamd::upload(keep, h, &d, what); }
+
 int check_device(int dev);
 void read_env(Handle::Env &e);
 int trsm_rs(const Handle &H, int nsp);

@@ -12,11 +12,11 @@
 
 namespace sluamd {
 
-// the table an update launch counts its work units in: host image and device copy of one of LevelSched's per-level prefix arrays (lvl_poff layout)
-struct UnitTable { std::vector<int> LevelSched::*h; int *LevelSched::*d; };
-constexpr UnitTable UNITS_FWD = {&LevelSched::fwd_prefix, &LevelSched::d_fwd_prefix};      // 64-row L strips
-constexpr UnitTable UNITS_BWD = {&LevelSched::bwd_prefix, &LevelSched::d_bwd_prefix};      // 64-column U chunks
-constexpr UnitTable UNITS_ZFWD = {&LevelSched::zfwd_prefix, &LevelSched::d_zfwd_prefix};   // complex16: 256-row L strips
+// the table an update launch counts its work units in: one of LevelSched's per-level prefix tables (lvl_poff layout)
+typedef PlanTable<int> LevelSched::*UnitTable;
+constexpr UnitTable UNITS_FWD = &LevelSched::fwd_prefix;     // 64-row L strips
+constexpr UnitTable UNITS_BWD = &LevelSched::bwd_prefix;     // 64-column U chunks
+constexpr UnitTable UNITS_ZFWD = &LevelSched::zfwd_prefix;   // complex16: 256-row L strips
 
 struct LevelKernels {
     // the two launches of a level: x = the chunk's vector, ldx in values of the handle's precision; fwd = the ascending sweep
@@ -35,14 +35,14 @@ static inline int sweep_level(Handle *H, LevelSched &S, int l, bool fwd, double 
     const int64_t ldxd = ldx * (H->z ? 2 : 1);      // the exchanges see doubles (run lists in doubles), the kernels values
     const auto &red_send = K.trans ? S.xt_red_send : S.xs_red_send, &red_recv = K.trans ? S.xt_red_recv : S.xs_red_recv;
     const auto &bc_send = K.trans ? S.xt_bc_send : S.xs_bc_send, &bc_recv = K.trans ? S.xt_bc_recv : S.xs_bc_recv;
-    const UnitTable &U = fwd ? K.fwd_units : K.bwd_units;
+    const PlanTable<int> &U = S.*(fwd ? K.fwd_units : K.bwd_units);
     const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
     int rc;
-    if (!fwd) K.update(s, fwd, H->T, S.d_nodes + n0, S.*U.d + po, nn, (S.*U.h)[po + nn], x, ldx, nr, S.max_nsupc[l], ctx);
+    if (!fwd) K.update(s, fwd, H->T, S.nodes.d + n0, U.d + po, nn, U.h[po + nn], x, ldx, nr, S.max_nsupc[l], ctx);
     if (xy && (rc = xseg_exchange(H, x, ldxd, nr, red_send[l], 3, red_recv[l], 2, s))) return rc;
-    K.diag(s, fwd, H->T, S.d_nodes + n0, nn, x, ldx, nr, S.max_nsupc[l], ctx);
+    K.diag(s, fwd, H->T, S.nodes.d + n0, nn, x, ldx, nr, S.max_nsupc[l], ctx);
     if (xy && (rc = xseg_exchange(H, x, ldxd, nr, bc_send[l], 0, bc_recv[l], 1, s))) return rc;
-    if (fwd) K.update(s, fwd, H->T, S.d_nodes + n0, S.*U.d + po, nn, (S.*U.h)[po + nn], x, ldx, nr, S.max_nsupc[l], ctx);
+    if (fwd) K.update(s, fwd, H->T, S.nodes.d + n0, U.d + po, nn, U.h[po + nn], x, ldx, nr, S.max_nsupc[l], ctx);
     return 2;
 }
 
