@@ -207,6 +207,9 @@ int sluamd_get_stats(sluamd_handle_t h, sluamd_stats_t *out);
 /* wall-clock breakdown of the handle's creation as "phase=seconds;phase=seconds;..." (host planner phases, arena allocation, table uploads,
  * distribution of A): the pre-processing a caller pays once per sparsity structure (pddistribute3d + the GPU handle set-up of the reference) */
 int sluamd_setup_times(sluamd_handle_t h, char *buf, int32_t cap);
+/* Diagnostics: how many device allocations the library has requested in this process so far (every one goes through one helper; the pool's chunks and
+ * the caller's own allocations are not counted).  Two reads around a call tell whether the call allocated. */
+int64_t sluamd_device_alloc_count(void);
 /* The plan of this rank, one row of SLUAMD_PLAN_COLS doubles per (Z level, DAG level): supernodes, Schur / panel flops of THIS rank, bytes and messages of the two XY
  * exchange phases, bytes of the Z reduction that follows the Z level (column list at the definition, sluamd_api.cpp).  buf may be NULL: *rows = rows needed.
  * Host data only (no device work): what a scaling model needs from the library (scripts/scale_model.py; the reference prints the same quantities as its
@@ -389,6 +392,27 @@ int sluamd_pzgsrfs3d_gmres(sluamd_handle_t h, int trans, const sluamd_doublecomp
                            int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves);
 int sluamd_pzgsrfs3d_gmres_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
                                int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves);
+
+/* Blocked refinement: the contract of sluamd_p[dz]gsrfs3d_trans[_dev] -- trans, B, X, ldb, ldx, nrhs, the ordering, berr[j], equilibrated handles, grid
+ * handles (replicated form, collective; transposed calls after sluamd_PlanTransposedSweeps) -- with all right-hand sides carried through the loop TOGETHER,
+ * in panels of 16 columns (the block that one pass of the fp64 MFMA sweeps over the factors serves): per step one residual pass over the columns of the
+ * panel that are still active, ONE solve with the resident factors for all columns that continue, one update of exactly those.  The calls above pay one
+ * pass over the factors per column and step.  Per column nothing differs from those calls: the same residual and berr (the same kernel text, bitwise), the
+ * same continue / stop decision from that column's own previous berr and step count, the same update; a column that has stopped is not touched again, so
+ * X, berr and the step counts are those of sluamd_p[dz]gsrfs3d[_trans] column by column wherever the sweeps return the same correction for a column alone
+ * and inside a block (exactly representable data, deterministic handles).
+ * steps (may be NULL): nrhs entries, steps[j] = the steps of right-hand side j itself.  nrhs == 0 returns 0 and writes nothing.
+ * Device memory: 16 n values and 16 words on the first block call of a handle, 32 n values more on the first call of the host form; released with the
+ * attached matrix.  On grids the decisions of a panel are agreed by one min-all-reduce per step.
+ * Errors beyond those of sluamd_p[dz]gsrfs3d_trans: the handle of a batch (sluamd_BatchHandle), SLUAMD_EINVAL. */
+int sluamd_pdgsrfs3d_block(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs,
+                           double *berr, int32_t *steps);
+int sluamd_pdgsrfs3d_block_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs,
+                               double *berr, int32_t *steps);
+int sluamd_pzgsrfs3d_block(sluamd_handle_t h, int trans, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X,
+                           int64_t ldx, int32_t nrhs, double *berr, int32_t *steps);
+int sluamd_pzgsrfs3d_block_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
+                               int64_t ldx, int32_t nrhs, double *berr, int32_t *steps);
 
 /* ---- Equil = YES: row / column equilibration on the device and the solve phase of the expert driver in the caller's ordering and
  * scaling (pdgsequ + pdlaqgs at the head of pdgssvx3d, SRC/double/pdgssvx3d.c:673-729; B scaled by R before the solve, :1450-1465;

@@ -65,13 +65,14 @@ class RowPerm(C.Structure):
 EXPORTS = [
     "sluamd_default_options", "sluamd_dCreateLUHandle", "sluamd_dSetValues", "sluamd_pdgstrf3d",
     "sluamd_dCopyLU2Host", "sluamd_pdgstrs3d", "sluamd_pdgstrs3d_dev", "sluamd_pdgstrs3d_dist", "sluamd_pzgstrs3d_dist", "sluamd_dDestroyLUHandle",
-    "sluamd_get_stats", "sluamd_setup_times", "sluamd_poisson3d", "sluamd_dGetDiagInv", "sluamd_last_error", "sluamd_device_count", "sluamd_device_pci_bus_id", "sluamd_device_pool_trim", "sluamd_plan_table", "sluamd_plan_xlists", "sluamd_PlanTransposedSweeps", "sluamd_dsymbfact", "sluamd_dsymbfact_unsym", "sluamd_order_nd", "sluamd_symb_info",
+    "sluamd_get_stats", "sluamd_setup_times", "sluamd_device_alloc_count", "sluamd_poisson3d", "sluamd_dGetDiagInv", "sluamd_last_error", "sluamd_device_count", "sluamd_device_pci_bus_id", "sluamd_device_pool_trim", "sluamd_plan_table", "sluamd_plan_xlists", "sluamd_PlanTransposedSweeps", "sluamd_dsymbfact", "sluamd_dsymbfact_unsym", "sluamd_order_nd", "sluamd_symb_info",
     "sluamd_symb_view", "sluamd_symb_grid_footprint", "sluamd_ddistribute_host", "sluamd_dCreateLUHandleFromSymb", "sluamd_symb_free",
     "sluamd_zCreateLUHandle", "sluamd_zSetValues", "sluamd_pzgstrf3d", "sluamd_zCopyLU2Host", "sluamd_pzgstrs3d",
     "sluamd_dAttachMatrix", "sluamd_pdgsrfs3d", "sluamd_pdgsrfs3d_dev",
     "sluamd_zAttachMatrix", "sluamd_pzgsrfs3d", "sluamd_pzgsrfs3d_dev",
     "sluamd_pdgstrs3d_trans", "sluamd_pdgstrs3d_trans_dev", "sluamd_pzgstrs3d_trans", "sluamd_pzgstrs3d_trans_dev",
     "sluamd_pdgsrfs3d_trans", "sluamd_pdgsrfs3d_trans_dev", "sluamd_pzgsrfs3d_trans", "sluamd_pzgsrfs3d_trans_dev",
+    "sluamd_pdgsrfs3d_block", "sluamd_pdgsrfs3d_block_dev", "sluamd_pzgsrfs3d_block", "sluamd_pzgsrfs3d_block_dev",
     "sluamd_default_gmres", "sluamd_pdgsrfs3d_gmres", "sluamd_pdgsrfs3d_gmres_dev", "sluamd_pzgsrfs3d_gmres", "sluamd_pzgsrfs3d_gmres_dev",
     "sluamd_dEquilibrate", "sluamd_zEquilibrate", "sluamd_GetScalings",
     "sluamd_dEquilibrateWith", "sluamd_zEquilibrateWith", "sluamd_dLargeDiag", "sluamd_zLargeDiag", "sluamd_SetRowPerm",
@@ -148,6 +149,9 @@ def bind(L):
     L.sluamd_symb_grid_footprint.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, P_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.sluamd_set_profile.argtypes = [C.c_void_p, C.c_int]
     L.sluamd_setup_times.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+    if hasattr(L, "sluamd_device_alloc_count"):      # diagnostics of later builds: an older build given through SLUAMD_LIB (A/B timing) has none
+        L.sluamd_device_alloc_count.argtypes = []
+        L.sluamd_device_alloc_count.restype = C.c_int64
     L.sluamd_poisson3d.argtypes = [C.c_int32, C.c_int32, C.c_int32, P_int, P_int, P_dbl]
     L.sluamd_poisson3d.restype = C.c_int64
     L.sluamd_dGetDiagInv.argtypes = [C.c_void_p, C.c_int32, P_dbl, P_dbl]
@@ -166,6 +170,10 @@ def bind(L):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int32]
     # transposed refinement: only in the product library (the CPU test build has neither the transposed sweeps nor the transposed residual kernels)
     for name in ("sluamd_pdgsrfs3d_trans", "sluamd_pdgsrfs3d_trans_dev", "sluamd_pzgsrfs3d_trans", "sluamd_pzgsrfs3d_trans_dev"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, P_dbl, P_int]
+    # blocked refinement: only in the product library (its block kernels have no CPU restatement); steps: nrhs entries, may be NULL
+    for name in ("sluamd_pdgsrfs3d_block", "sluamd_pdgsrfs3d_block_dev", "sluamd_pzgsrfs3d_block", "sluamd_pzgsrfs3d_block_dev"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, P_dbl, P_int]
     # GMRES refinement: only in the product library (its Krylov kernels have no CPU restatement)

@@ -474,6 +474,7 @@ void free_rfs(Handle *H)
     H->d_rfs_tcp.reset(); H->d_rfs_tri.reset(); H->d_rfs_tpos.reset();       // (the transposed index belongs to the pattern that goes)
     H->d_rp_pr.reset(); H->d_rp_pcpr.reset(); H->d_rp_rs.reset();            // (and so does the row permutation of sluamd_SetRowPerm)
     H->d_gm_work.reset(); H->d_gm_part.reset(); H->gm_restart = 0;            // (and the Krylov workspace of sluamd_p[dz]gsrfs3d_gmres)
+    H->d_rfs_bwork.reset(); H->d_rfs_bstage.reset(); H->d_rfs_bs.reset();     // (and the panels of sluamd_p[dz]gsrfs3d_block)
     H->rfs_nnz = 0;
     H->rfs_z = false;
 }
@@ -551,6 +552,8 @@ void sluamd_dDestroyLUHandle(sluamd_handle_t h)
     if (H->stream) hipStreamDestroy(H->stream);
     delete h;      // the device buffers (DevBuf / DevBag / PoolBuf members of Handle) release themselves here
 }
+
+int64_t sluamd_device_alloc_count(void) { return dev_alloc_calls().load(); }
 
 int sluamd_setup_times(sluamd_handle_t h, char *buf, int32_t cap)
 {

@@ -11,6 +11,7 @@
 // No sub-allocation, no caching: an owner and a helper.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <string>
 #include <utility>
@@ -28,8 +29,12 @@ void devpool_free(void *p);               // pool ranges and plain allocations a
 void devpool_trim(int device);            // device < 0: every device
 size_t devpool_cached_bytes(int device);
 
+// how many times dev_alloc was asked in this process (sluamd_device_alloc_count): what a test reads to see that a second call allocates nothing
+inline std::atomic<int64_t> &dev_alloc_calls() { static std::atomic<int64_t> n{0}; return n; }
+
 inline int dev_alloc(void **p, size_t bytes, int device, const char *what)
 {
+    ++dev_alloc_calls();
     bytes = std::max<size_t>(bytes, 1);
     hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) {

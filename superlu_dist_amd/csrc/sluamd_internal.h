@@ -389,6 +389,9 @@ struct Handle {
     // GMRES refinement (sluamd_gmres.cpp), allocated on the first such call: [v_0 .. v_gm_restart | z | w | x0 | 0] of n values each (a double vector padded to an
     // even count) and the reductions' partials slab + results.  They go with the attached matrix (free_rfs)
     DevBuf<double> d_gm_work, d_gm_part; int gm_restart = 0;
+    // blocked refinement (sluamd_brefine.cpp), allocated on the first such call: r_perm of a panel of 16 columns, one berr word per column of the panel, and
+    // (host form only) the panel of B and of X.  They go with the attached matrix (free_rfs)
+    DevBuf<double> d_rfs_bwork, d_rfs_bstage; DevBuf<unsigned long long> d_rfs_bs;
     bool batch_owned = false;                               // the handle of a batch object (sluamd_BatchHandle lends it out)
     void *h_pinned = nullptr; size_t pinned_bytes = 0;      // bounded pinned staging buffer (value upload / download)
     bool z = false;                                         // complex16 (doublecomplex) values: 16-byte elements

@@ -2,11 +2,11 @@
 // (SRC/complex16/pzgsrfs.c:365-514), written once for both precisions and for A x = b, A^T x = b and A^H x = b.  The stopping rule and its constants
 // (rfs_guards, rfs_continue), the per-column work through the resident work vectors and the collective continue / stop decision on grids live here.
 // A form is the policy K = Rfs<Z, TRANS> below:
-//   K::z                 complex16 (values, x, b, r_perm of two doubles)
+//   K::z                 complex16 (values, x, b, r_perm of two doubles);  K::trans   0 / 1 / 2 as below
 //   K::attach            name for the error messages: this precision's attach call
 //   K::residual(s, H, x, b, r_perm, safe1, safe2)   r_perm = Pc (b - op(A) x), *H->d_rfs_s.p = max(*H->d_rfs_s.p, berr bits)
 //   K::update(s, H, dx_perm, x)                     x += Pc^T dx_perm
-//   K::solve(H, r_perm, n)                          the correction, in place in r_perm: run_solve_dev for A x = b, the transposed sweeps otherwise
+//   K::solve(H, r_perm, n[, nrhs])                  the correction, in place in r_perm: run_solve_dev for A x = b, the transposed sweeps otherwise
 //                                                   (A^T d = r is A1^T (Pc d) = Pc r for the factors of A1 = Pc A Pc^T: the same permutation on both
 //                                                   sides, so r_perm and K::update are used exactly alike)
 // A template, so a file instantiates the forms it names and no others: sluamd_api.cpp names Rfs<false, 0> only, and the CPU test build, which links the host
@@ -28,6 +28,7 @@ int ensure_tindex(Handle *H, const char *who);
 
 template <bool Z, int TRANS> struct Rfs {   // TRANS: 0 = A x = b, 1 = A^T x = b, 2 = A^H x = b (complex16; needs ensure_tindex first, like 1)
     static constexpr bool z = Z;
+    static constexpr int trans = TRANS;
     static constexpr const char *attach = Z ? "sluamd_zAttachMatrix" : "sluamd_dAttachMatrix";
     static void residual(hipStream_t s, const Handle *H, const double *x, const double *b, double *r_perm, double safe1, double safe2)
     {
@@ -40,10 +41,10 @@ template <bool Z, int TRANS> struct Rfs {   // TRANS: 0 = A x = b, 1 = A^T x = b
         if constexpr (!Z && TRANS == 0) eng::rfs_update(s, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
         else eng::rfs_update(s, Z, (int) H->hs.n, H->d_rfs_pc.p, dx_perm, x);
     }
-    static int solve(Handle *H, double *r_perm, int n)
+    static int solve(Handle *H, double *r_perm, int n, int nrhs = 1)      // nrhs > 1: the block form (sluamd_brefine.cpp), columns n values apart
     {
-        if constexpr (TRANS != 0) return run_tsolve(H, Z && TRANS == 2, r_perm, n, 1);
-        else return run_solve_dev(H, r_perm, n, 1);
+        if constexpr (TRANS != 0) return run_tsolve(H, Z && TRANS == 2, r_perm, n, nrhs);
+        else return run_solve_dev(H, r_perm, n, nrhs);
     }
 };
 // the policy of a (precision, trans) pair known at run time: f(Rfs<..>()) of the form that SLUAMD_NOTRANS / SLUAMD_TRANS / SLUAMD_CONJ names (the conjugate

@@ -1,6 +1,7 @@
 // sluamd_rkernels.inc -- the kernels of iterative refinement (pdgsrfs3d, SRC/double/pdgsrfs.c:345-510; pzgsrfs3d, SRC/complex16/pzgsrfs.c:365-514), written once
 // for double and complex16, A x = b / A^T x = b / A^H x = b, one matrix and batches.  Included by sluamd_kernels.hip (k_rfs_residual, k_rfs_update behind
-// eng::rfs_residual / eng::rfs_update) and by sluamd_bkernels.inc (k_batch_residual, k_batch_update call rfs_row / rfs_add): everything here is a template or
+// eng::rfs_residual / eng::rfs_update), by sluamd_bkernels.inc (k_batch_residual, k_batch_update call rfs_row / rfs_add) and by sluamd_mkernels.inc (the block
+// kernels call rfs_term / rfs_quot / rfs_block_max / rfs_add): everything here is a template or
 // forced inline, V = double or double2 {x = re, y = im}.
 //
 // One pass over the matrix does both of the reference's p[dz]gsmv calls (abs = 0 and abs = 1): the residual r = b - op(A) x, stored permuted by the caller
@@ -27,6 +28,23 @@ __device__ __forceinline__ double2 rfs_sub(double2 b, double2 ax) { return make_
 __device__ __forceinline__ void rfs_add(double &v, double d) { v += d; }
 __device__ __forceinline__ void rfs_add(double2 &v, double2 d) { v.x += d.x; v.y += d.y; }
 
+// The two halves of a row, shared by the column form (rfs_row) and the block form (k_rfs_residual_block, sluamd_mkernels.inc, one pair of accumulators per
+// column): one entry into (ax, t), and the end of the row -- b last, then the three-branch quotient
+template <class V> __device__ __forceinline__ void rfs_term(V &ax, double &t, const V a, const V xv)
+{
+    rfs_mad(ax, a, xv);
+    t += rfs_abs1(a) * rfs_abs1(xv);
+}
+template <class V> __device__ __forceinline__ double rfs_quot(const V ax, double t, const V bval, double safe1, double safe2, V &r)
+{
+    r = rfs_sub(bval, ax);
+    t += rfs_abs1(bval);
+    const double ar = rfs_abs1(r);
+    if (t > safe2) return ar / t;
+    if (t != 0.0) return (safe1 + ar) / t;
+    return 0.0;
+}
+
 // r = bval - sum_e op(a_e) x[xi[e]] over the entries [e0, e1); returns the row's backward error q (0 for a row whose weight is 0).  ap (POS only): the
 // position of entry e in av
 template <class V, bool CONJ, bool POS>
@@ -37,15 +55,9 @@ __device__ __forceinline__ double rfs_row(int e0, int e1, const int *__restrict_
     double t = 0.0;
     for (int e = e0; e < e1; ++e) {
         const V a = rfs_op<CONJ>(av[POS ? ap[e] : e]), xv = x[xi[e]];
-        rfs_mad(ax, a, xv);
-        t += rfs_abs1(a) * rfs_abs1(xv);
+        rfs_term(ax, t, a, xv);
     }
-    r = rfs_sub(bval, ax);
-    t += rfs_abs1(bval);
-    const double ar = rfs_abs1(r);
-    if (t > safe2) return ar / t;
-    if (t != 0.0) return (safe1 + ar) / t;
-    return 0.0;
+    return rfs_quot(ax, t, bval, safe1, safe2, r);
 }
 
 // max of q over the workgroup (256 threads, all of them call it) into *s_out: wave, LDS, ONE integer atomicMax on the bit pattern -- non-negative doubles

@@ -373,27 +373,37 @@ class LUHandle:
         """Device copy of the ORIGINAL matrix (CSR) + perm_c for pdgsrfs3d (sluamd_dAttachMatrix, or sluamd_zAttachMatrix on a complex16 handle)."""
         _attach_matrix(self._h, self.z, n, rowptr, colind, nzval, perm_c)
 
-    def pdgsrfs3d(self, b, x, trans="N", method="plain", restart=None, inner_tol=None, max_solves=None):
+    def pdgsrfs3d(self, b, x, trans="N", method="plain", restart=None, inner_tol=None, max_solves=None, block=False):
         """Iterative refinement of x (original ordering) for the attached matrix; returns (x, berr[nrhs], steps).
+        block=True: all right-hand sides go through the loop together, in panels of 16 columns with one solve per step for the columns that continue
+        (sluamd_p[dz]gsrfs3d_block); returns (x, berr[nrhs], steps[nrhs]), every column's own count; b and x are checked as for trans = "T" / "C";
+        not with method="gmres" (ValueError).
         method="gmres": the correction of every step is a cycle of GMRES preconditioned by the factors (sluamd_p[dz]gsrfs3d_gmres; restart, inner_tol,
         max_solves: sluamd_gmres_t, None = the library's default); returns (x, berr[nrhs], steps, solves[nrhs]), steps counting the outer steps.  b and x
         are checked as for trans = "T" / "C"; ValueError also for another method, or for restart / inner_tol / max_solves with method="plain".
         pzgsrfs3d on a complex16 handle (complex b and x).  trans = "T" / "C": the transposed / conjugate-transposed system A^T x = b, A^H x = b of
         the attached matrix (sluamd_p[dz]gsrfs3d_trans), x e.g. from pdgstrs3d(trans=...).  ValueError, before any library call:
         a trans other than "N", "T", "C"; b or x of another dtype than the handle's; shapes that differ or are not (n,) / (n, nrhs)."""
+        _check_block(block, method)
         opt = _gmres_opt(method, restart, inner_tol, max_solves)
         if opt is not None:
             return _gsrfs3d_gmres(self._h, self.z, b, x, trans, self.n, opt)
+        if block:
+            return _gsrfs3d_block(self._h, self.z, b, x, trans, self.n)
         return _gsrfs3d(self._h, self.z, b, x, trans, self.n)
 
     pzgsrfs3d = pdgsrfs3d
 
-    def pdgsrfs3d_dev(self, d_b, ldb, d_x, ldx, nrhs, trans="N", method="plain", restart=None, inner_tol=None, max_solves=None):
+    def pdgsrfs3d_dev(self, d_b, ldb, d_x, ldx, nrhs, trans="N", method="plain", restart=None, inner_tol=None, max_solves=None, block=False):
         """sluamd_p[dz]gsrfs3d_dev: b, x device pointers (column-major, ld in values); x refined in place.  Returns (berr[nrhs], steps).
+        block=True: sluamd_p[dz]gsrfs3d_block_dev, returns (berr[nrhs], steps[nrhs]); not with method="gmres" (ValueError).
         trans = "T" / "C": sluamd_p[dz]gsrfs3d_trans_dev.  method="gmres": sluamd_p[dz]gsrfs3d_gmres_dev, returns (berr[nrhs], steps, solves[nrhs])."""
+        _check_block(block, method)
         opt = _gmres_opt(method, restart, inner_tol, max_solves)
         if opt is not None:
             return _gsrfs3d_gmres_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans, opt)
+        if block:
+            return _gsrfs3d_block_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans)
         return _gsrfs3d_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans)
 
     pzgsrfs3d_dev = pdgsrfs3d_dev
@@ -529,6 +539,38 @@ def _gsrfs3d_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans="N"):
     name = "sluamd_pzgsrfs3d_dev" if z else "sluamd_pdgsrfs3d_dev"
     _lib.check(_lib.entry(name)(h, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), _pd(berr), C.byref(steps)), name)
     return berr[:int(nrhs)], steps.value
+
+
+def _check_block(block, method):
+    if block and method == "gmres":
+        raise ValueError("block=True belongs to method='plain': the GMRES refinement takes one right-hand side at a time")
+
+
+def _gsrfs3d_block(h, z, b, x, trans, n):
+    """sluamd_p[dz]gsrfs3d_block on host arrays: (x, berr[nrhs], steps[nrhs])"""
+    t = _trans_code(trans)
+    dt = np.complex128 if z else np.float64
+    for what, a in (("b", b), ("x", x)):
+        if np.asarray(a).dtype != np.dtype(dt):
+            raise ValueError(f"pdgsrfs3d(block=True): the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
+    if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
+        raise ValueError(f"pdgsrfs3d(block=True): b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
+    b = np.asfortranarray(np.array(b, dtype=dt)); x = np.asfortranarray(np.array(x, dtype=dt))
+    if b.ndim == 1:
+        b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
+    nrhs = b.shape[1]
+    berr = np.zeros(max(nrhs, 1)); steps = np.zeros(max(nrhs, 1), dtype=np.int32)
+    name = "sluamd_pzgsrfs3d_block" if z else "sluamd_pdgsrfs3d_block"
+    _lib.check(_lib.entry(name)(h, t, b.ctypes.data_as(C.c_void_p), max(b.shape[0], 1), x.ctypes.data_as(C.c_void_p), max(x.shape[0], 1), nrhs, _pd(berr), _pi(steps)), name)
+    return x, berr[:nrhs], steps[:nrhs]
+
+
+def _gsrfs3d_block_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans):
+    t = _trans_code(trans)
+    berr = np.zeros(max(int(nrhs), 1)); steps = np.zeros(max(int(nrhs), 1), dtype=np.int32)
+    name = "sluamd_pzgsrfs3d_block_dev" if z else "sluamd_pdgsrfs3d_block_dev"
+    _lib.check(_lib.entry(name)(h, t, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), _pd(berr), _pi(steps)), name)
+    return berr[:int(nrhs)], steps[:int(nrhs)]
 
 
 def _gmres_opt(method, restart, inner_tol, max_solves):
@@ -725,10 +767,16 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
     refine="gmres": the refinement is the GMRES one (LUHandle.pdgsrfs3d(method="gmres")); `refine_solves` joins `berr` and `refine_steps` in the stats.
     With equil=True the solve runs with refine=0 and the SCALED system is refined: b' = R o b, x' = x / C, then x = C o x'.  Not with grid or rowperm
     (ValueError).
+    refine="block": the refinement is the blocked one (LUHandle.pdgsrfs3d(block=True): all right-hand sides together, one solve per step); `refine_steps` in
+    the stats is then an array, every column's own count.  With the forms that refine through gssvx_solve (equil, rowperm) the solve runs with refine=0 and
+    the blocked refinement follows on the attached system (equil: the scaled one, as for "gmres"); not with rowperm (ValueError).
     Returns (x, info, stats[, handle, symb])."""
-    gmres = isinstance(refine, str)
+    block = isinstance(refine, str) and refine == "block"
+    if block and rowperm is not None:
+        raise ValueError("refine='block' is not part of the rowperm form of this driver -- keep the handle and call LUHandle.pdgsrfs3d(block=True)")
+    gmres = isinstance(refine, str) and not block
     if gmres and refine != "gmres":
-        raise ValueError(f"refine must be False, True or 'gmres', not {refine!r}")
+        raise ValueError(f"refine must be False, True, 'gmres' or 'block', not {refine!r}")
     if gmres and ((grid is not None and tuple(grid) != (1, 1, 1)) or rowperm is not None):
         raise ValueError("refine='gmres' is not part of the grid and rowperm forms of this driver -- keep the handle and call LUHandle.pdgsrfs3d(method='gmres')")
     if refine and _trans_code(trans):
@@ -761,7 +809,7 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
         if gmres:
             x, st["berr"], st["refine_steps"], st["refine_solves"] = h.pdgsrfs3d(b, x, method="gmres")
         else:
-            x, berr, steps = h.pdgsrfs3d(b, x)
+            x, berr, steps = h.pdgsrfs3d(b, x, block=block)
             st["berr"] = berr; st["refine_steps"] = steps
     if keep:
         return x, info, st, h, symb
@@ -772,6 +820,7 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
 def _gssvx3d_grid(n, rowptr, colind, nzval, b, perm_c, relax, maxsup, replace_tiny, anorm, refine, trans, equil, deterministic, grid):
     """the grid=(Pr, Pc, Pz) path of pdgssvx3d: one thread per rank, replicated right-hand sides, every step collective"""
     from . import grid3d
+    block = refine == "block"
     Pr, Pc, Pz = grid
     symb = Symbolic(n, rowptr, colind, perm_c, relax, maxsup)
     sn_tree = symb.partition(Pz) if Pz > 1 else None
@@ -789,12 +838,14 @@ def _gssvx3d_grid(n, rowptr, colind, nzval, b, perm_c, relax, maxsup, replace_ti
             if equil:
                 eq = h.equilibrate(n, rowptr, colind, nzval, symb.perm_c)
                 info = h.pdgstrf3d(0.5 * float(np.finfo(np.float32).eps) * eq["anorm"])
-                out = h.gssvx_solve(b, trans=trans, refine=refine)
+                out = h.gssvx_solve(b, trans=trans, refine=refine and not block)
                 extra.update(equed=eq["equed"], rowcnd=eq["rowcnd"], colcnd=eq["colcnd"], amax=eq["amax"])
                 if eq["info"] > 0:
                     extra["equil_info"] = eq["info"]
                 x = out
-                if refine:
+                if block:
+                    x, extra["berr"], extra["refine_steps"] = _refine_scaled(h, b, x, block=True)
+                elif refine:
                     x, extra["berr"], extra["refine_steps"] = out
             else:
                 info = h.pdgstrf3d(pivot_thresh(n, rowptr, colind, nzval) if anorm is None else 0.5 * float(np.finfo(np.float32).eps) * anorm)
@@ -803,7 +854,7 @@ def _gssvx3d_grid(n, rowptr, colind, nzval, b, perm_c, relax, maxsup, replace_ti
                 x = np.asfortranarray(h.pdgstrs3d(xp, trans=trans)[symb.perm_c, :])
                 if refine:
                     h.attach_matrix(n, rowptr, colind, nzval, symb.perm_c)
-                    x, extra["berr"], extra["refine_steps"] = h.pdgsrfs3d(b, x)
+                    x, extra["berr"], extra["refine_steps"] = h.pdgsrfs3d(b, x, block=block)
             st = h.stats()
             st.update(extra)
             return x, info, st
@@ -857,8 +908,8 @@ def _gssvx3d_equil(h, symb, n, rowptr, colind, nzval, b, keep, refine, trans):
     """the Equil = YES path of pdgssvx3d: equilibrate on the device, thresh from the scaled matrix's 1-norm, factor, expert solve"""
     eq = h.equilibrate(n, rowptr, colind, nzval, symb.perm_c)
     info = h.pdgstrf3d(0.5 * float(np.finfo(np.float32).eps) * eq["anorm"])
-    gmres = refine == "gmres"
-    out = h.gssvx_solve(b, trans=trans, refine=refine and not gmres)
+    gmres, block = refine == "gmres", refine == "block"
+    out = h.gssvx_solve(b, trans=trans, refine=refine and not gmres and not block)
     st = h.stats()
     st.update(equed=eq["equed"], rowcnd=eq["rowcnd"], colcnd=eq["colcnd"], amax=eq["amax"])
     if eq["info"] > 0:
@@ -869,12 +920,23 @@ def _gssvx3d_equil(h, symb, n, rowptr, colind, nzval, b, keep, refine, trans):
         bs = np.asfortranarray(np.array(b, dtype=x.dtype).reshape(x.shape) * r[:, None])
         xs, st["berr"], st["refine_steps"], st["refine_solves"] = h.pdgsrfs3d(bs, np.asfortranarray(x / c[:, None]), method="gmres")
         x = np.asfortranarray(xs * c[:, None])
+    elif block:
+        x, st["berr"], st["refine_steps"] = _refine_scaled(h, b, x, block=True)
     elif refine:
         x, st["berr"], st["refine_steps"] = out
     if keep:
         return x, info, st, h, symb
     h.destroy(); symb.free()
     return x, info, st
+
+
+def _refine_scaled(h, b, x, **kw):
+    """refinement of an equilibrated handle by hand (untransposed): the attached matrix is the scaled one, R A C -- refine (R A C) x' = R o b from x' = x / C,
+    then x = C o x'.  Returns (x, berr, steps)"""
+    r, c = h.scalings()
+    bs = np.asfortranarray(np.array(b, dtype=x.dtype).reshape(x.shape) * r[:, None])
+    xs, berr, steps = h.pdgsrfs3d(bs, np.asfortranarray(x / c[:, None]), **kw)
+    return np.asfortranarray(xs * c[:, None]), berr, steps
 
 
 pzgssvx3d = pdgssvx3d   # complex16 input (nzval complex) takes the pzgstrf3d / pzgstrs3d path of the same driver

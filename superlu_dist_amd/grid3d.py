@@ -220,11 +220,14 @@ class GridHandle:
         from .driver import _attach_matrix
         _attach_matrix(self._h, self.z, n, rowptr, colind, nzval, perm_c)
 
-    def pdgsrfs3d(self, b, x, trans="N"):
+    def pdgsrfs3d(self, b, x, trans="N", block=False):
         """Iterative refinement, replicated form (collective): the complete b and initial x (original ordering) on every rank;
         returns (the complete refined x, berr[nrhs], steps) -- the same on every rank.  pzgsrfs3d on a complex16 handle.
-        trans = "T" / "C": the system A^T x = b / A^H x = b of the attached matrix (sluamd_p[dz]gsrfs3d_trans; after plan_transposed()), with LUHandle.pdgsrfs3d's argument checks."""
-        from .driver import _gsrfs3d
+        trans = "T" / "C": the system A^T x = b / A^H x = b of the attached matrix (sluamd_p[dz]gsrfs3d_trans; after plan_transposed()), with LUHandle.pdgsrfs3d's argument checks.
+        block=True: the blocked form (sluamd_p[dz]gsrfs3d_block), steps = every column's own count [nrhs]."""
+        from .driver import _gsrfs3d, _gsrfs3d_block
+        if block:
+            return _gsrfs3d_block(self._h, self.z, b, x, trans, self.n)
         return _gsrfs3d(self._h, self.z, b, x, trans, self.n)
 
     pzgsrfs3d = pdgsrfs3d
