@@ -392,6 +392,22 @@ int sluamd_pzgsrfs3d_gmres(sluamd_handle_t h, int trans, const sluamd_doublecomp
                            int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves);
 int sluamd_pzgsrfs3d_gmres_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
                                int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves);
+/* test hook: ONE operation of the Krylov kernels of the GMRES refinement, through the chunk loops the cycle itself runs, on vectors laid out as the cycle's
+ * workspace (16-byte aligned, zero-filled; a double vector of odd order padded to an even count).  No handle: host pointers, the current device, its null
+ * stream.  z: 0 double, 1 complex16; vs = 1 or 2 doubles per value; ns = doubles per padded vector = z ? 2 n : n + (n & 1).  V: nv vectors of n values,
+ * contiguous; placed vstride doubles apart on the device (even, >= ns; the gap behind a vector holds NaN).  x: n values.  xout: ns doubles, the pad
+ * included.  coef: nv coefficients of vs doubles.  The partial sums and the result words hold NaN before the operation.
+ *   SLUAMD_KRYLOV_DOTS     nv in [0, 64]: res[vs k ..] = v_k^H x, res[vs nv] = ||x||^2 (partials of the first chunk's launch); xout = x as the kernels left it
+ *   SLUAMD_KRYLOV_AXPYS    nv in [1, 64]: x -= sum_k v_k coef_k, coef read from device memory; xout = x, res[0] = ||x||^2 of the new x
+ *   SLUAMD_KRYLOV_SCALE    xout = x / h into a vector of its own that held NaN (nv, V, coef, res unused)
+ *   SLUAMD_KRYLOV_COMBINE  nv in [1, 64]: x = (add ? x : 0) + sum_k v_k coef_k; xout = x (res unused)
+ * Errors, SLUAMD_EINVAL with a message: an unknown op, n < 1, nv outside the range of the op, vstride odd or < ns, a null pointer the op uses. */
+#define SLUAMD_KRYLOV_DOTS 0
+#define SLUAMD_KRYLOV_AXPYS 1
+#define SLUAMD_KRYLOV_SCALE 2
+#define SLUAMD_KRYLOV_COMBINE 3
+int sluamd_krylov_selftest(int op, int z, int64_t n, int32_t nv, int64_t vstride, const double *V, const double *x, const double *coef, double h, int add,
+                           double *xout, double *res);
 
 /* Blocked refinement: the contract of sluamd_p[dz]gsrfs3d_trans[_dev] -- trans, B, X, ldb, ldx, nrhs, the ordering, berr[j], equilibrated handles, grid
  * handles (replicated form, collective; transposed calls after sluamd_PlanTransposedSweeps) -- with all right-hand sides carried through the loop TOGETHER,

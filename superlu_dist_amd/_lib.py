@@ -74,6 +74,7 @@ EXPORTS = [
     "sluamd_pdgsrfs3d_trans", "sluamd_pdgsrfs3d_trans_dev", "sluamd_pzgsrfs3d_trans", "sluamd_pzgsrfs3d_trans_dev",
     "sluamd_pdgsrfs3d_block", "sluamd_pdgsrfs3d_block_dev", "sluamd_pzgsrfs3d_block", "sluamd_pzgsrfs3d_block_dev",
     "sluamd_default_gmres", "sluamd_pdgsrfs3d_gmres", "sluamd_pdgsrfs3d_gmres_dev", "sluamd_pzgsrfs3d_gmres", "sluamd_pzgsrfs3d_gmres_dev",
+    "sluamd_krylov_selftest",
     "sluamd_dEquilibrate", "sluamd_zEquilibrate", "sluamd_GetScalings",
     "sluamd_dEquilibrateWith", "sluamd_zEquilibrateWith", "sluamd_dLargeDiag", "sluamd_zLargeDiag", "sluamd_SetRowPerm",
     "sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev",
@@ -183,6 +184,8 @@ def bind(L):
     for name in ("sluamd_pdgsrfs3d_gmres", "sluamd_pdgsrfs3d_gmres_dev", "sluamd_pzgsrfs3d_gmres", "sluamd_pzgsrfs3d_gmres_dev"):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Gmres), P_dbl, P_int, P_int]
+    if hasattr(L, "sluamd_krylov_selftest"):         # (op, z, n, nv, vstride, V, x, coef, h, add, xout, res)
+        L.sluamd_krylov_selftest.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int64, P_dbl, P_dbl, P_dbl, C.c_double, C.c_int, P_dbl, P_dbl]
     # equilibration and the expert driver's solve phase: only in the product library (the CPU test build has no equilibration kernels)
     for name in ("sluamd_dEquilibrate", "sluamd_zEquilibrate"):
         if hasattr(L, name):

@@ -11,6 +11,8 @@
 // No floating-point atomics: the results repeat bit for bit.
 // GM_GRID x GM_BLOCK units are one full sweep of the grid: 262144 units = 524288 doubles or 262144 complex16 values; beyond that the grid-stride loops wrap
 // (tests/gmres_cases.py: LARGE_N = 524288 + 4097 is the first size class that does).
+// Tested one operation at a time, exactly, through sluamd_krylov_selftest (sluamd_gmres.cpp): tests/test_gpu_krylov_kernels.py; the constants below are
+// restated in tests/krylov_cases.py.
 
 #define GM_BLOCK 256
 #define GM_GRID 1024

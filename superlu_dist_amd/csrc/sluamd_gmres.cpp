@@ -26,6 +26,7 @@ const int GM_RES = 2 * 2 * GM_MAX_RESTART + 2;      // results behind the slab: 
 
 struct Work {                                       // the Krylov workspace of one call
     int64_t ns = 0, nu = 0;                         // doubles / 16-byte units per vector
+    int64_t vstride = 0;                            // doubles from one basis vector to the next: ns in a handle's workspace, the caller's choice in the self-test
     double *V = nullptr, *z = nullptr, *w = nullptr, *x0 = nullptr, *zero = nullptr, *slab = nullptr, *res = nullptr;
 };
 
@@ -36,6 +37,7 @@ int ensure_work(Handle *H, int restart, bool z, Work &W)
     const int64_t n = H->hs.n;
     W.ns = z ? 2 * n : ((n + 1) & ~(int64_t) 1);
     W.nu = W.ns / 2;
+    W.vstride = W.ns;
     const int64_t nvec = (int64_t) restart + 5;
     if (!H->d_gm_work.p || H->gm_restart < restart) {
         if (int rc = H->d_gm_work.alloc(nvec * W.ns, H->device, "the Krylov basis of the GMRES refinement")) { H->gm_restart = 0; return rc; }
@@ -53,6 +55,38 @@ int ensure_work(Handle *H, int restart, bool z, Work &W)
     return 0;
 }
 
+// The three loops over more basis vectors than one launch takes, written once: the cycle and sluamd_krylov_selftest run the Krylov kernels through them alone.
+// h[0 .. nb vs) = V[0 .. nb)^H w (device memory, vs doubles per coefficient): the dots GM_CHUNK vectors at a time, vector c0 + k into the slots
+// (c0 + k) vs .., then ONE k_gm_sum over all of them.  norm_slot >= 0: ||w||^2 as well, its partials from the first launch (the only one when nb == 0),
+// its sum into *nrm
+void basis_dots(hipStream_t s, bool z, const Work &W, int nb, int norm_slot, double *h, double *nrm)
+{
+    const int vs = z ? 2 : 1;
+    for (int c0 = 0; c0 < std::max(nb, norm_slot >= 0 ? 1 : 0); c0 += GM_CHUNK)
+        geng::dots(s, z, W.nu, W.V + (int64_t) c0 * W.vstride, W.vstride, std::min(GM_CHUNK, nb - c0), W.w, W.slab, c0 * vs, c0 == 0 ? norm_slot : -1);
+    geng::sum(s, W.nu, W.slab, 0, nb * vs, h);
+    if (norm_slot >= 0) geng::sum(s, W.nu, W.slab, norm_slot, 1, nrm);
+}
+
+// w -= V[0 .. nb) h, h in device memory as basis_dots left it; every launch stores the partials of ||w||^2 of ITS new w into GM_SLOT_NAXPY: the last one's stay
+void basis_axpys(hipStream_t s, bool z, const Work &W, int nb, const double *h)
+{
+    const int vs = z ? 2 : 1;
+    for (int c0 = 0; c0 < nb; c0 += GM_CHUNK)
+        geng::axpys(s, z, W.nu, W.V + (int64_t) c0 * W.vstride, W.vstride, std::min(GM_CHUNK, nb - c0), W.w, h + (int64_t) c0 * vs, W.slab, GM_SLOT_NAXPY);
+}
+
+// u = (add ? u : 0) + V[0 .. nb) y, y on the host: `add` decides for the first launch alone, every later one adds to what the launches before it left
+void basis_combine(hipStream_t s, bool z, const Work &W, int nb, double *u, const cplx *y, bool add)
+{
+    for (int c0 = 0; c0 < nb; c0 += GM_CHUNK) {
+        double yc[2 * GM_CHUNK];
+        const int nv = std::min(GM_CHUNK, nb - c0);
+        for (int k = 0; k < nv; ++k) { yc[2 * k] = y[c0 + k].real(); yc[2 * k + 1] = y[c0 + k].imag(); }
+        geng::combine(s, z, W.nu, W.V + (int64_t) c0 * W.vstride, W.vstride, nv, u, yc, add || c0 > 0);
+    }
+}
+
 // One cycle on the residual in W.w (overwritten): the correction u = M^-1 V y ends up in W.z and is added to x.  `solves`: applications of the factors so far
 // for this right-hand side, at least two short of the budget on entry.  Returns 1, with the residual untouched, when its 2-norm is not a positive finite
 // double: the caller then takes the plain step.  Returns 2, with X untouched and one application spent, when the first Krylov vector maps to zero: the
@@ -65,8 +99,7 @@ template <class K> int gmres_cycle(Handle *H, const Work &W, const sluamd_gmres_
     const size_t vbytes = sizeof(double) * (size_t) W.ns;
     double hres[GM_RES];
     // beta = ||r||_2, v_0 = r / beta
-    geng::dots(s, z, W.nu, W.V, W.ns, 0, W.w, W.slab, 0, GM_SLOT_NDOT);
-    geng::sum(s, W.nu, W.slab, GM_SLOT_NDOT, 1, W.res);
+    basis_dots(s, z, W, 0, GM_SLOT_NDOT, W.res, W.res);
     HIPCHK(hipMemcpyAsync(hres, W.res, sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     const double beta = std::sqrt(hres[0]);
@@ -88,11 +121,8 @@ template <class K> int gmres_cycle(Handle *H, const Work &W, const sluamd_gmres_
         // CGS2: h = V^H w', w' -= V h, twice, the coefficients staying on the device between the two launches of a pass
         for (int pass = 0; pass < 2; ++pass) {
             double *h = W.res + (int64_t) pass * nb * vs;
-            for (int c0 = 0; c0 < nb; c0 += GM_CHUNK)
-                geng::dots(s, z, W.nu, W.V + (int64_t) c0 * W.ns, W.ns, std::min(GM_CHUNK, nb - c0), W.w, W.slab, c0 * vs, -1);   // (the norm CGS2 uses is k_gm_axpys')
-            geng::sum(s, W.nu, W.slab, 0, nb * vs, h);
-            for (int c0 = 0; c0 < nb; c0 += GM_CHUNK)
-                geng::axpys(s, z, W.nu, W.V + (int64_t) c0 * W.ns, W.ns, std::min(GM_CHUNK, nb - c0), W.w, h + (int64_t) c0 * vs, W.slab, GM_SLOT_NAXPY);
+            basis_dots(s, z, W, nb, -1, h, nullptr);                // (the norm CGS2 uses is k_gm_axpys')
+            basis_axpys(s, z, W, nb, h);
         }
         geng::sum(s, W.nu, W.slab, GM_SLOT_NAXPY, 1, W.res + 2 * (int64_t) nb * vs);
         HIPCHK(hipMemcpyAsync(hres, W.res, sizeof(double) * (size_t) (2 * nb * vs + 1), hipMemcpyDeviceToHost, s));
@@ -129,12 +159,7 @@ template <class K> int gmres_cycle(Handle *H, const Work &W, const sluamd_gmres_
         for (int k = i + 1; k < kdim; ++k) t -= R[(size_t) i * m + k] * y[k];
         y[i] = t / R[(size_t) i * m + i];
     }
-    for (int c0 = 0; c0 < kdim; c0 += GM_CHUNK) {
-        double yc[2 * GM_CHUNK];
-        const int nv = std::min(GM_CHUNK, kdim - c0);
-        for (int k = 0; k < nv; ++k) { yc[2 * k] = y[c0 + k].real(); yc[2 * k + 1] = y[c0 + k].imag(); }
-        geng::combine(s, z, W.nu, W.V + (int64_t) c0 * W.ns, W.ns, nv, W.z, yc, c0 > 0);
-    }
+    basis_combine(s, z, W, kdim, W.z, y.data(), false);
     if (int rc = K::solve(H, W.z, n)) return rc;
     ++solves;
     K::update(s, H, W.z, Xc);
@@ -264,6 +289,63 @@ int sluamd_pzgsrfs3d_gmres_dev(sluamd_handle_t h, int trans, const sluamd_double
                                const sluamd_gmres_t *opt, double *berr, int32_t *steps, int32_t *solves)
 {
     return gmres_entry(h, trans, d_B, ldb, d_X, ldx, nrhs, opt, berr, steps, solves, true, false, "sluamd_pzgsrfs3d_gmres_dev");
+}
+
+// test hook (contract: include/superlu_dist_amd.h): one operation of the Krylov kernels through the loops gmres_cycle runs them through, on a workspace of its
+// own laid out as ensure_work's -- [v_0 .. v_nv | x | dst], zero-filled vectors -- with NaN wherever the cycle's layout has no memory of a vector (the gap
+// behind a basis vector when vstride > ns) and wherever a result is expected (dst, the partials slab, the result words): all bits set is a NaN
+int sluamd_krylov_selftest(int op, int zi, int64_t n, int32_t nv, int64_t vstride, const double *V, const double *x, const double *coef, double h, int add,
+                           double *xout, double *res)
+{
+    const std::string me = "sluamd_krylov_selftest: ";
+    const bool z = zi != 0, basis = op != SLUAMD_KRYLOV_SCALE;
+    const int vs = z ? 2 : 1, lo = op == SLUAMD_KRYLOV_AXPYS || op == SLUAMD_KRYLOV_COMBINE ? 1 : 0;
+    if (op < SLUAMD_KRYLOV_DOTS || op > SLUAMD_KRYLOV_COMBINE) { set_error(me + "unknown operation"); return SLUAMD_EINVAL; }
+    if (n < 1 || n > INT32_MAX) { set_error(me + "n must lie in [1, 2^31)"); return SLUAMD_EINVAL; }
+    Work W;
+    W.ns = z ? 2 * n : ((n + 1) & ~(int64_t) 1);
+    W.nu = W.ns / 2;
+    if (!basis) { nv = 0; vstride = W.ns; }
+    if (nv < lo || nv > GM_MAX_RESTART) { set_error(me + "nv must lie in [" + std::to_string(lo) + ", 64] for this operation"); return SLUAMD_EINVAL; }
+    if ((vstride & 1) || vstride < W.ns) { set_error(me + "vstride must be even and at least the padded length of a vector"); return SLUAMD_EINVAL; }
+    const bool wants_coef = op == SLUAMD_KRYLOV_AXPYS || op == SLUAMD_KRYLOV_COMBINE, wants_res = op == SLUAMD_KRYLOV_DOTS || op == SLUAMD_KRYLOV_AXPYS;
+    if (!x || !xout || (nv > 0 && !V) || (wants_coef && !coef) || (wants_res && !res)) { set_error(me + "null pointer"); return SLUAMD_EINVAL; }
+    if (int rc = check_device(-1)) return rc;
+    W.vstride = vstride;
+    DevBuf<double> work, part;
+    const int64_t nwork = nv * vstride + 2 * W.ns, npart = (int64_t) GM_SLOTS * GM_GRID + GM_RES;
+    if (int rc = work.alloc(nwork, -1, "the vectors of the Krylov self-test")) return rc;
+    if (int rc = part.alloc(npart, -1, "the partial sums of the Krylov self-test")) return rc;
+    W.V = work.p; W.w = work.p + nv * vstride;
+    double *dst = W.w + W.ns;
+    W.slab = part.p; W.res = part.p + (int64_t) GM_SLOTS * GM_GRID;
+    hipStream_t s = 0;
+    const size_t vbytes = sizeof(double) * (size_t) W.ns, nbytes = sizeof(double) * (size_t) (n * vs);
+    HIPCHK(hipMemsetAsync(part.p, 0xFF, sizeof(double) * (size_t) npart, s));
+    HIPCHK(hipMemsetAsync(work.p, 0xFF, sizeof(double) * (size_t) nwork, s));
+    for (int k = 0; k <= nv; ++k) {                             // the basis vectors, then x
+        double *d = k < nv ? W.V + (int64_t) k * vstride : W.w;
+        HIPCHK(hipMemsetAsync(d, 0, vbytes, s));
+        HIPCHK(hipMemcpy(d, k < nv ? V + (int64_t) k * n * vs : x, nbytes, hipMemcpyHostToDevice));
+    }
+    if (op == SLUAMD_KRYLOV_DOTS) {
+        basis_dots(s, z, W, nv, GM_SLOT_NDOT, W.res, W.res + nv * vs);
+        HIPCHK(hipMemcpy(res, W.res, sizeof(double) * (size_t) (nv * vs + 1), hipMemcpyDeviceToHost));
+    } else if (op == SLUAMD_KRYLOV_AXPYS) {                     // the coefficients where a pass of CGS2 has them, the norm where the cycle sums it
+        HIPCHK(hipMemcpy(W.res, coef, sizeof(double) * (size_t) (nv * vs), hipMemcpyHostToDevice));
+        basis_axpys(s, z, W, nv, W.res);
+        geng::sum(s, W.nu, W.slab, GM_SLOT_NAXPY, 1, W.res + 2 * (int64_t) nv * vs);
+        HIPCHK(hipMemcpy(res, W.res + 2 * (int64_t) nv * vs, sizeof(double), hipMemcpyDeviceToHost));
+    } else if (op == SLUAMD_KRYLOV_SCALE) {
+        geng::scale(s, W.nu, dst, W.w, h);
+    } else {
+        std::vector<cplx> y((size_t) nv);
+        for (int k = 0; k < nv; ++k) y[k] = cplx(coef[k * vs], z ? coef[k * vs + 1] : 0.0);
+        basis_combine(s, z, W, nv, W.w, y.data(), add != 0);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(xout, basis ? W.w : dst, vbytes, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 }  // extern "C"
