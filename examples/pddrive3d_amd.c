@@ -186,7 +186,7 @@ static int run_batch(int64_t n, const int *rp, const int *ci, const double *v, l
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { fprintf(stderr, "usage: %s N [-nd] [--equil] [--rowperm] [--refine gmres] [--steps K] | N --batch K | file.dat [--equil] [--rowperm] [--steps K] | file.mtx [--equil] [--rowperm] [--steps K]\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s N [-nd] [--equil] [--rowperm] [--refine gmres|extra] [--steps K] | N --batch K | file.dat [--equil] [--rowperm] [--steps K] | file.mtx [--equil] [--rowperm] [--steps K]\n", argv[0]); return 2; }
     if (sluamd_device_count() < 1) { fprintf(stderr, "no HIP device: this library has no CPU fallback\n"); return 3; }
     int64_t n; int *rp, *ci; double *v;
     char *end;
@@ -195,9 +195,11 @@ int main(int argc, char **argv)
     int equil = 0;                                            /* --equil: Equil = YES (pdgsequ + pdlaqgs on the device, scaled solve) */
     for (int a = 2; a < argc; ++a) if (!strcmp(argv[a], "--equil")) equil = 1;
     int gmres = 0;                                            /* --refine gmres: the refinement of the first solve is sluamd_pdgsrfs3d_gmres (GMRES preconditioned by the factors) */
+    int extra = 0;                                            /* --refine extra: sluamd_pdgsrfs3d_extra (IterRefine = SLU_EXTRA: the residual in twice the working precision) */
     for (int a = 2; a + 1 < argc; ++a) if (!strcmp(argv[a], "--refine")) {
-        if (strcmp(argv[a + 1], "gmres")) { fprintf(stderr, "--refine takes gmres\n"); return 2; }
-        gmres = 1;
+        if (!strcmp(argv[a + 1], "gmres")) gmres = 1;
+        else if (!strcmp(argv[a + 1], "extra")) extra = 1;
+        else { fprintf(stderr, "--refine takes gmres or extra\n"); return 2; }
     }
     int rowperm = 0;                                          /* --rowperm: RowPerm = LargeDiag_MC64 (matching on the device + host, its scalings, solve in A's ordering) */
     for (int a = 2; a < argc; ++a) if (!strcmp(argv[a], "--rowperm")) rowperm = 1;
@@ -283,6 +285,8 @@ int main(int argc, char **argv)
      * perm_c run inside the library; a single rank holds all n rows) */
     double *x = (double *) malloc(sizeof(double) * n);
     double berr = 0.0; int32_t steps = 0, gsolves = 0;
+    sluamd_xrefine_t xr = {0.0, 0.0, 0, 0};
+    if (extra && (equil || rowperm)) { fprintf(stderr, "--refine extra: not with --equil / --rowperm in this example (solve with refine = 0, then refine the scaled system)\n"); return 2; }
     if (gmres && (equil || rowperm)) { fprintf(stderr, "--refine gmres: not with --equil / --rowperm in this example (solve with refine = 0, then refine the scaled system)\n"); return 2; }
     if (equil || rowperm) {   /* the expert driver's solve phase: B scaled by R, solve, refinement on the scaled system, X scaled by C */
         CHECK(sluamd_pdgssvx3d_solve(h, SLUAMD_NOTRANS, b, n, x, n, 1, 1, &berr, &steps));
@@ -292,6 +296,7 @@ int main(int argc, char **argv)
         /* IterRefine = SLU_DOUBLE */
         CHECK(sluamd_dAttachMatrix(h, (sluamd_int_t) n, rp, ci, v, perm_c));
         if (gmres) CHECK(sluamd_pdgsrfs3d_gmres(h, SLUAMD_NOTRANS, b, n, x, n, 1, NULL, &berr, &steps, &gsolves));   /* NULL: restart 20, 100 solves, 2^-30 */
+        else if (extra) { CHECK(sluamd_pdgsrfs3d_extra(h, SLUAMD_NOTRANS, b, n, x, n, 1, &berr, &xr)); steps = xr.steps; }
         else CHECK(sluamd_pdgsrfs3d(h, b, n, x, n, 1, &berr, &steps));
     }
 
@@ -310,6 +315,8 @@ int main(int argc, char **argv)
     printf("FACTOR time %.3f ms  (%.1f GFLOP/s)   SOLVE time %.3f ms   refinement steps %d  berr %.2e\n", st.t_factor_ms,
            flops / (st.t_factor_ms * 1e-3) / 1e9, st.t_solve_ms, steps, berr);
     printf("||X-Xtrue||/||X|| = %e   ||b-Ax||_2/||b||_2 = %e\n", err / xn, sqrt(rn / bn));
+    if (extra) printf("extra-precise refinement: berr %.2e  steps %d  dxrel %.3e  state %s  (forward error estimate dxrel / (1 - rho) = %.3e)\n", berr, xr.steps, xr.dxrel,
+                      xr.state == SLUAMD_XR_CONVERGED ? "CONVERGED" : xr.state == SLUAMD_XR_NO_PROGRESS ? "NO_PROGRESS" : "LIMIT", xr.dxrel / (1.0 - xr.rho));
     if (gmres) printf("GMRES refinement: outer steps %d  applications of the factors %d\n", steps, gsolves);
     int bad_steps = 0;
     double *v2 = nsteps > 0 ? (double *) malloc(sizeof(double) * (size_t) (rp[n] ? rp[n] : 1)) : NULL;

@@ -430,6 +430,53 @@ int sluamd_pzgsrfs3d_block(sluamd_handle_t h, int trans, const sluamd_doublecomp
 int sluamd_pzgsrfs3d_block_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
                                int64_t ldx, int32_t nrhs, double *berr, int32_t *steps);
 
+/* Extra-precise refinement, IterRefine = SLU_EXTRA ("accumulate residual in extra precision"): for systems whose condition number approaches 1 / eps.  The
+ * calls above stop on the backward error, and berr <= eps is reached while the forward error is still about cond(A) eps: the rounded fp64 residual limits
+ * what a correction can gain.  Here the residual of every step is accumulated in twice the working precision (per entry the product's error by a fused
+ * multiply-add and the sum's by TwoSum, carried in a compensation word; one rounding at the end of the row), the correction is the solve with the resident
+ * factors, and the loop watches the corrections.  With ndx = max_i abs1(dx_i) and nx = max_i abs1(x_i) of the x the correction belongs to (abs1 = |re| + |im|),
+ * per right-hand side:
+ *     residual (extra) -> berr;  after 20 steps: LIMIT.  dx = solve;  ndx == 0: CONVERGED.  After the first step, 2 ndx > the previous ndx (or at any step
+ *     an ndx that is not finite): NO_PROGRESS, dx is dropped.  x += dx;  ndx <= eps nx (eps = 2^-53): one closing residual pass, CONVERGED.
+ * The factor 2 is the one the reference's rule applies to berr.  berr[j] always belongs to the returned X.  x itself stays fp64: the result is the fp64
+ * neighbourhood of the solution, a few ulps in the largest component for cond(A) up to about 1 / eps, not a doubled x.
+ * out (may be NULL): nrhs entries.  steps = corrections applied; state as below; dxrel = ndx / nx of the last correction COMPUTED (a dropped one included;
+ * 0 when ndx == 0); rho = the largest ratio of successive ndx among the corrections applied (0 with fewer than two).  dxrel / (1 - rho) ESTIMATES the
+ * relative forward error max|x - x*| / max|x| of the returned X (the tail of a geometric series of corrections); it is an estimate, not a bound.
+ * trans, B, X, ldb, ldx, nrhs, berr, the ordering, equilibrated handles (the attached, scaled system is refined): the contract of
+ * sluamd_p[dz]gsrfs3d_trans[_dev].  nrhs == 0 returns 0 and writes nothing.  Device memory: two words on the first call of a handle, released with the
+ * attached matrix.  No floating-point atomics: two calls return the same bits wherever the solves do.
+ * Errors beyond those of sluamd_p[dz]gsrfs3d_trans, SLUAMD_EINVAL with a message: a handle of a multi-rank grid; the handle of a batch. */
+#define SLUAMD_XR_CONVERGED 0
+#define SLUAMD_XR_NO_PROGRESS 1
+#define SLUAMD_XR_LIMIT 2
+typedef struct sluamd_xrefine {
+    double  dxrel, rho;
+    int32_t steps, state;
+} sluamd_xrefine_t;
+int sluamd_pdgsrfs3d_extra(sluamd_handle_t h, int trans, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr,
+                           sluamd_xrefine_t *out);
+int sluamd_pdgsrfs3d_extra_dev(sluamd_handle_t h, int trans, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs,
+                               double *berr, sluamd_xrefine_t *out);
+int sluamd_pzgsrfs3d_extra(sluamd_handle_t h, int trans, const sluamd_doublecomplex *B, int64_t ldb, sluamd_doublecomplex *X,
+                           int64_t ldx, int32_t nrhs, double *berr, sluamd_xrefine_t *out);
+int sluamd_pzgsrfs3d_extra_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_B, int64_t ldb, sluamd_doublecomplex *d_X,
+                               int64_t ldx, int32_t nrhs, double *berr, sluamd_xrefine_t *out);
+/* R = B - op(A) X of the ATTACHED matrix in the caller's ordering (B, X, R column-major, ld in values, R apart from B and X), and berr[j] (may be NULL) =
+ * the componentwise backward error of column j as the refinement computes it.  extra = 0: the refinement's fp64 pass, bitwise (the same row text);
+ * extra != 0: the pass of sluamd_p[dz]gsrfs3d_extra, every r_i one rounding of the exact residual up to second-order terms.  Any handle with an attached
+ * matrix (on a grid every rank holds the complete matrix and computes the same).  nrhs == 0 returns 0.
+ * Errors, SLUAMD_EINVAL with a message: null B, X or R, a leading dimension below n, trans outside {0, 1, 2}, a handle of the other precision, no
+ * attached matrix. */
+int sluamd_dResidual(sluamd_handle_t h, int trans, int extra, const double *B, int64_t ldb, const double *X, int64_t ldx, int32_t nrhs, double *R,
+                     int64_t ldr, double *berr);
+int sluamd_dResidual_dev(sluamd_handle_t h, int trans, int extra, const double *d_B, int64_t ldb, const double *d_X, int64_t ldx, int32_t nrhs,
+                         double *d_R, int64_t ldr, double *berr);
+int sluamd_zResidual(sluamd_handle_t h, int trans, int extra, const sluamd_doublecomplex *B, int64_t ldb, const sluamd_doublecomplex *X, int64_t ldx,
+                     int32_t nrhs, sluamd_doublecomplex *R, int64_t ldr, double *berr);
+int sluamd_zResidual_dev(sluamd_handle_t h, int trans, int extra, const sluamd_doublecomplex *d_B, int64_t ldb, const sluamd_doublecomplex *d_X,
+                         int64_t ldx, int32_t nrhs, sluamd_doublecomplex *d_R, int64_t ldr, double *berr);
+
 /* ---- Equil = YES: row / column equilibration on the device and the solve phase of the expert driver in the caller's ordering and
  * scaling (pdgsequ + pdlaqgs at the head of pdgssvx3d, SRC/double/pdgssvx3d.c:673-729; B scaled by R before the solve, :1450-1465;
  * X scaled by C after it, :1806-1821, the roles swapped for a transposed system).  For handles made by

@@ -57,6 +57,14 @@ class Gmres(C.Structure):
     _fields_ = [("restart", C.c_int32), ("max_solves", C.c_int32), ("inner_tol", C.c_double)]
 
 
+class XRefine(C.Structure):
+    """sluamd_xrefine_t"""
+    _fields_ = [("dxrel", C.c_double), ("rho", C.c_double), ("steps", C.c_int32), ("state", C.c_int32)]
+
+
+XR_STATES = ("CONVERGED", "NO_PROGRESS", "LIMIT")      # SLUAMD_XR_CONVERGED / _NO_PROGRESS / _LIMIT
+
+
 class RowPerm(C.Structure):
     """sluamd_rowperm_t"""
     _fields_ = [("info", C.c_int32), ("rounds", C.c_int32), ("matched_device", C.c_int64), ("augmentations", C.c_int64)]
@@ -75,6 +83,8 @@ EXPORTS = [
     "sluamd_pdgsrfs3d_block", "sluamd_pdgsrfs3d_block_dev", "sluamd_pzgsrfs3d_block", "sluamd_pzgsrfs3d_block_dev",
     "sluamd_default_gmres", "sluamd_pdgsrfs3d_gmres", "sluamd_pdgsrfs3d_gmres_dev", "sluamd_pzgsrfs3d_gmres", "sluamd_pzgsrfs3d_gmres_dev",
     "sluamd_krylov_selftest",
+    "sluamd_pdgsrfs3d_extra", "sluamd_pdgsrfs3d_extra_dev", "sluamd_pzgsrfs3d_extra", "sluamd_pzgsrfs3d_extra_dev",
+    "sluamd_dResidual", "sluamd_dResidual_dev", "sluamd_zResidual", "sluamd_zResidual_dev",
     "sluamd_dEquilibrate", "sluamd_zEquilibrate", "sluamd_GetScalings",
     "sluamd_dEquilibrateWith", "sluamd_zEquilibrateWith", "sluamd_dLargeDiag", "sluamd_zLargeDiag", "sluamd_SetRowPerm",
     "sluamd_pdgssvx3d_solve", "sluamd_pdgssvx3d_solve_dev", "sluamd_pzgssvx3d_solve", "sluamd_pzgssvx3d_solve_dev",
@@ -186,6 +196,13 @@ def bind(L):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Gmres), P_dbl, P_int, P_int]
     if hasattr(L, "sluamd_krylov_selftest"):         # (op, z, n, nv, vstride, V, x, coef, h, add, xout, res)
         L.sluamd_krylov_selftest.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int32, C.c_int64, P_dbl, P_dbl, P_dbl, C.c_double, C.c_int, P_dbl, P_dbl]
+    # extra-precise refinement and the residual on its own: only in the product library (their kernels have no CPU restatement)
+    for name in ("sluamd_pdgsrfs3d_extra", "sluamd_pdgsrfs3d_extra_dev", "sluamd_pzgsrfs3d_extra", "sluamd_pzgsrfs3d_extra_dev"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, P_dbl, C.POINTER(XRefine)]
+    for name in ("sluamd_dResidual", "sluamd_dResidual_dev", "sluamd_zResidual", "sluamd_zResidual_dev"):
+        if hasattr(L, name):       # (h, trans, extra, B, ldb, X, ldx, nrhs, R, ldr, berr)
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, P_dbl]
     # equilibration and the expert driver's solve phase: only in the product library (the CPU test build has no equilibration kernels)
     for name in ("sluamd_dEquilibrate", "sluamd_zEquilibrate"):
         if hasattr(L, name):

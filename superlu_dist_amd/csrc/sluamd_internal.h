@@ -392,6 +392,9 @@ struct Handle {
     // blocked refinement (sluamd_brefine.cpp), allocated on the first such call: r_perm of a panel of 16 columns, one berr word per column of the panel, and
     // (host form only) the panel of B and of X.  They go with the attached matrix (free_rfs)
     DevBuf<double> d_rfs_bwork, d_rfs_bstage; DevBuf<unsigned long long> d_rfs_bs;
+    // extra-precise refinement (sluamd_xrefine.cpp), allocated on the first such call: the two norm words of a step, max abs1(dx) and max abs1(x).  They go
+    // with the attached matrix (free_rfs)
+    DevBuf<unsigned long long> d_xr_s;
     bool batch_owned = false;                               // the handle of a batch object (sluamd_BatchHandle lends it out)
     void *h_pinned = nullptr; size_t pinned_bytes = 0;      // bounded pinned staging buffer (value upload / download)
     bool z = false;                                         // complex16 (doublecomplex) values: 16-byte elements

@@ -35,14 +35,19 @@ template <class V> __device__ __forceinline__ void rfs_term(V &ax, double &t, co
     rfs_mad(ax, a, xv);
     t += rfs_abs1(a) * rfs_abs1(xv);
 }
-template <class V> __device__ __forceinline__ double rfs_quot(const V ax, double t, const V bval, double safe1, double safe2, V &r)
+// (rfs_ratio: the end of the row for a residual r that is already formed -- the extra-precise pass, sluamd_xkernels.inc, rounds its own)
+template <class V> __device__ __forceinline__ double rfs_ratio(const V r, double t, const V bval, double safe1, double safe2)
 {
-    r = rfs_sub(bval, ax);
     t += rfs_abs1(bval);
     const double ar = rfs_abs1(r);
     if (t > safe2) return ar / t;
     if (t != 0.0) return (safe1 + ar) / t;
     return 0.0;
+}
+template <class V> __device__ __forceinline__ double rfs_quot(const V ax, double t, const V bval, double safe1, double safe2, V &r)
+{
+    r = rfs_sub(bval, ax);
+    return rfs_ratio(r, t, bval, safe1, safe2);
 }
 
 // r = bval - sum_e op(a_e) x[xi[e]] over the entries [e0, e1); returns the row's backward error q (0 for a row whose weight is 0).  ap (POS only): the

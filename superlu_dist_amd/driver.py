@@ -251,6 +251,7 @@ class LUHandle:
         self.nnz = None                                   # entries of the CSR the handle was created from (from_symbolic sets it)
         self.device = -1                                  # HIP device ordinal given at creation (-1: the device that was current)
         self.rowperm_pos = None                           # pdgssvx3d(rowperm=...): the handle was made from Pr A; values in A's order go through this map
+        self.refine_rho = None                            # pdgsrfs3d(method="extra"): per column the largest ratio of successive corrections of the last call
 
     @staticmethod
     def _opts(replace_tiny=False, deterministic=False, device=-1, info_rule=0):
@@ -383,9 +384,17 @@ class LUHandle:
         are checked as for trans = "T" / "C"; ValueError also for another method, or for restart / inner_tol / max_solves with method="plain".
         pzgsrfs3d on a complex16 handle (complex b and x).  trans = "T" / "C": the transposed / conjugate-transposed system A^T x = b, A^H x = b of
         the attached matrix (sluamd_p[dz]gsrfs3d_trans), x e.g. from pdgstrs3d(trans=...).  ValueError, before any library call:
-        a trans other than "N", "T", "C"; b or x of another dtype than the handle's; shapes that differ or are not (n,) / (n, nrhs)."""
+        a trans other than "N", "T", "C"; b or x of another dtype than the handle's; shapes that differ or are not (n,) / (n, nrhs).
+        method="extra": IterRefine = SLU_EXTRA (sluamd_p[dz]gsrfs3d_extra) -- the residual of every step accumulated in twice the working precision, the
+        loop stopped by the corrections instead of berr; returns (x, berr[nrhs], steps[nrhs], dxrel[nrhs], state[nrhs]): state 0 / 1 / 2 = CONVERGED /
+        NO_PROGRESS / LIMIT (_lib.XR_STATES), dxrel = max|dx| / max|x| of the last correction computed.  self.refine_rho[nrhs] then holds the largest ratio
+        of successive corrections, and dxrel / (1 - rho) estimates -- it does not bound -- the relative forward error.  b and x are checked as for
+        trans = "T" / "C"; not with block=True, restart, inner_tol or max_solves (ValueError)."""
         _check_block(block, method)
         opt = _gmres_opt(method, restart, inner_tol, max_solves)
+        if method == "extra":
+            x, berr, steps, dxrel, state, self.refine_rho = _gsrfs3d_extra(self._h, self.z, b, x, trans, self.n)
+            return x, berr, steps, dxrel, state
         if opt is not None:
             return _gsrfs3d_gmres(self._h, self.z, b, x, trans, self.n, opt)
         if block:
@@ -394,12 +403,30 @@ class LUHandle:
 
     pzgsrfs3d = pdgsrfs3d
 
+    def residual(self, b, x, trans="N", extra=False):
+        """r = b - op(A) x of the attached matrix in the caller's ordering and its componentwise backward error: (r, berr[nrhs]) (sluamd_[dz]Residual).
+        extra=False: the refinement's fp64 pass, bitwise; extra=True: the doubled accumulation of method="extra", every r_i one rounding of the exact
+        residual up to second-order terms.  b and x are checked as for pdgsrfs3d(trans="T")."""
+        return _residual(self._h, self.z, b, x, trans, extra, self.n)
+
+    def residual_dev(self, d_b, ldb, d_x, ldx, nrhs, d_r, ldr, trans="N", extra=False):
+        """sluamd_[dz]Residual_dev: b, x, r device pointers (column-major, ld in values); returns berr[nrhs]"""
+        berr = np.zeros(max(int(nrhs), 1))
+        name = "sluamd_zResidual_dev" if self.z else "sluamd_dResidual_dev"
+        _lib.check(_lib.entry(name)(self._h, _trans_code(trans), 1 if extra else 0, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), C.c_void_p(d_r),
+                                    int(ldr), _pd(berr)), name)
+        return berr[:int(nrhs)]
+
     def pdgsrfs3d_dev(self, d_b, ldb, d_x, ldx, nrhs, trans="N", method="plain", restart=None, inner_tol=None, max_solves=None, block=False):
         """sluamd_p[dz]gsrfs3d_dev: b, x device pointers (column-major, ld in values); x refined in place.  Returns (berr[nrhs], steps).
         block=True: sluamd_p[dz]gsrfs3d_block_dev, returns (berr[nrhs], steps[nrhs]); not with method="gmres" (ValueError).
-        trans = "T" / "C": sluamd_p[dz]gsrfs3d_trans_dev.  method="gmres": sluamd_p[dz]gsrfs3d_gmres_dev, returns (berr[nrhs], steps, solves[nrhs])."""
+        trans = "T" / "C": sluamd_p[dz]gsrfs3d_trans_dev.  method="gmres": sluamd_p[dz]gsrfs3d_gmres_dev, returns (berr[nrhs], steps, solves[nrhs]).
+        method="extra": sluamd_p[dz]gsrfs3d_extra_dev, returns (berr[nrhs], steps[nrhs], dxrel[nrhs], state[nrhs]); self.refine_rho as pdgsrfs3d."""
         _check_block(block, method)
         opt = _gmres_opt(method, restart, inner_tol, max_solves)
+        if method == "extra":
+            berr, steps, dxrel, state, self.refine_rho = _gsrfs3d_extra_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans)
+            return berr, steps, dxrel, state
         if opt is not None:
             return _gsrfs3d_gmres_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans, opt)
         if block:
@@ -544,6 +571,8 @@ def _gsrfs3d_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans="N"):
 def _check_block(block, method):
     if block and method == "gmres":
         raise ValueError("block=True belongs to method='plain': the GMRES refinement takes one right-hand side at a time")
+    if block and method == "extra":
+        raise ValueError("block=True belongs to method='plain': the extra-precise refinement takes one right-hand side at a time")
 
 
 def _gsrfs3d_block(h, z, b, x, trans, n):
@@ -574,14 +603,14 @@ def _gsrfs3d_block_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans):
 
 
 def _gmres_opt(method, restart, inner_tol, max_solves):
-    """None for method="plain"; else sluamd_gmres_t with the library's defaults where an argument is None.  ValueError: another method, options without
-    method="gmres".  (The ranges are the library's to check: SLUAMD_EINVAL -> RuntimeError.)"""
-    if method == "plain":
+    """None for method="plain" and "extra"; else sluamd_gmres_t with the library's defaults where an argument is None.  ValueError: another method, options
+    without method="gmres".  (The ranges are the library's to check: SLUAMD_EINVAL -> RuntimeError.)"""
+    if method in ("plain", "extra"):
         if restart is not None or inner_tol is not None or max_solves is not None:
             raise ValueError("restart, inner_tol and max_solves belong to method='gmres'")
         return None
     if method != "gmres":
-        raise ValueError(f"method must be 'plain' or 'gmres', not {method!r}")
+        raise ValueError(f"method must be 'plain', 'gmres' or 'extra', not {method!r}")
     from ._lib import Gmres
     o = Gmres()
     _lib.entry("sluamd_default_gmres")(C.byref(o))
@@ -619,6 +648,62 @@ def _gsrfs3d_gmres_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans, opt):
     name = "sluamd_pzgsrfs3d_gmres_dev" if z else "sluamd_pdgsrfs3d_gmres_dev"
     _lib.check(_lib.entry(name)(h, t, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), C.byref(opt), _pd(berr), C.byref(steps), _pi(solves)), name)
     return berr[:int(nrhs)], steps.value, solves[:int(nrhs)]
+
+
+def _xrefine_out(out, nrhs):
+    """sluamd_xrefine_t[nrhs] -> steps, dxrel, state, rho as arrays"""
+    o = out[:nrhs]
+    return (np.array([v.steps for v in o], dtype=np.int32), np.array([v.dxrel for v in o], dtype=np.float64),
+            np.array([v.state for v in o], dtype=np.int32), np.array([v.rho for v in o], dtype=np.float64))
+
+
+def _gsrfs3d_extra(h, z, b, x, trans, n):
+    """sluamd_p[dz]gsrfs3d_extra on host arrays: (x, berr[nrhs], steps[nrhs], dxrel[nrhs], state[nrhs], rho[nrhs])"""
+    t = _trans_code(trans)
+    dt = np.complex128 if z else np.float64
+    for what, a in (("b", b), ("x", x)):
+        if np.asarray(a).dtype != np.dtype(dt):
+            raise ValueError(f"pdgsrfs3d(method='extra'): the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
+    if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
+        raise ValueError(f"pdgsrfs3d(method='extra'): b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
+    b = np.asfortranarray(np.array(b, dtype=dt)); x = np.asfortranarray(np.array(x, dtype=dt))
+    if b.ndim == 1:
+        b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
+    nrhs = b.shape[1]
+    berr = np.zeros(max(nrhs, 1)); out = (_lib.XRefine * max(nrhs, 1))()
+    name = "sluamd_pzgsrfs3d_extra" if z else "sluamd_pdgsrfs3d_extra"
+    _lib.check(_lib.entry(name)(h, t, b.ctypes.data_as(C.c_void_p), max(b.shape[0], 1), x.ctypes.data_as(C.c_void_p), max(x.shape[0], 1), nrhs, _pd(berr), out), name)
+    steps, dxrel, state, rho = _xrefine_out(out, nrhs)
+    return x, berr[:nrhs], steps, dxrel, state, rho
+
+
+def _gsrfs3d_extra_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans):
+    t = _trans_code(trans)
+    nrhs = int(nrhs)
+    berr = np.zeros(max(nrhs, 1)); out = (_lib.XRefine * max(nrhs, 1))()
+    name = "sluamd_pzgsrfs3d_extra_dev" if z else "sluamd_pdgsrfs3d_extra_dev"
+    _lib.check(_lib.entry(name)(h, t, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), nrhs, _pd(berr), out), name)
+    return (berr[:nrhs],) + _xrefine_out(out, nrhs)
+
+
+def _residual(h, z, b, x, trans, extra, n):
+    """sluamd_[dz]Residual on host arrays: (r, berr[nrhs])"""
+    t = _trans_code(trans)
+    dt = np.complex128 if z else np.float64
+    for what, a in (("b", b), ("x", x)):
+        if np.asarray(a).dtype != np.dtype(dt):
+            raise ValueError(f"residual: the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
+    if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
+        raise ValueError(f"residual: b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
+    one = np.ndim(b) == 1
+    b = np.asfortranarray(np.asarray(b, dtype=dt).reshape(np.shape(b)[0], -1)); x = np.asfortranarray(np.asarray(x, dtype=dt).reshape(b.shape))
+    nrhs = b.shape[1]
+    r = np.zeros_like(b, order="F"); berr = np.zeros(max(nrhs, 1))
+    name = "sluamd_zResidual" if z else "sluamd_dResidual"
+    ld = max(b.shape[0], 1)
+    _lib.check(_lib.entry(name)(h, t, 1 if extra else 0, b.ctypes.data_as(C.c_void_p), ld, x.ctypes.data_as(C.c_void_p), ld, nrhs, r.ctypes.data_as(C.c_void_p), ld,
+                                _pd(berr)), name)
+    return (r[:, 0] if one else r), berr[:nrhs]
 
 
 EQUED = "NRCB"      # SLUAMD_EQUED_N / _R / _C / _B
@@ -770,13 +855,19 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
     refine="block": the refinement is the blocked one (LUHandle.pdgsrfs3d(block=True): all right-hand sides together, one solve per step); `refine_steps` in
     the stats is then an array, every column's own count.  With the forms that refine through gssvx_solve (equil, rowperm) the solve runs with refine=0 and
     the blocked refinement follows on the attached system (equil: the scaled one, as for "gmres"); not with rowperm (ValueError).
+    refine="extra": IterRefine = SLU_EXTRA (LUHandle.pdgsrfs3d(method="extra")): `refine_steps` is an array, and `refine_dxrel`, `refine_state` and
+    `refine_rho` (arrays per column) join `berr` in the stats.  With equil=True the scaled system is refined as for "gmres", and dxrel measures the scaled
+    x'.  Not with grid or rowperm (ValueError).
     Returns (x, info, stats[, handle, symb])."""
     block = isinstance(refine, str) and refine == "block"
     if block and rowperm is not None:
         raise ValueError("refine='block' is not part of the rowperm form of this driver -- keep the handle and call LUHandle.pdgsrfs3d(block=True)")
-    gmres = isinstance(refine, str) and not block
+    extra = isinstance(refine, str) and refine == "extra"
+    if extra and ((grid is not None and tuple(grid) != (1, 1, 1)) or rowperm is not None):
+        raise ValueError("refine='extra' is not part of the grid and rowperm forms of this driver -- keep the handle and call LUHandle.pdgsrfs3d(method='extra')")
+    gmres = isinstance(refine, str) and not block and not extra
     if gmres and refine != "gmres":
-        raise ValueError(f"refine must be False, True, 'gmres' or 'block', not {refine!r}")
+        raise ValueError(f"refine must be False, True, 'gmres', 'block' or 'extra', not {refine!r}")
     if gmres and ((grid is not None and tuple(grid) != (1, 1, 1)) or rowperm is not None):
         raise ValueError("refine='gmres' is not part of the grid and rowperm forms of this driver -- keep the handle and call LUHandle.pdgsrfs3d(method='gmres')")
     if refine and _trans_code(trans):
@@ -808,6 +899,9 @@ def pdgssvx3d(n, rowptr, colind, nzval, b, perm_c=None, relax=32, maxsup=256, re
         h.attach_matrix(n, rowptr, colind, nzval, symb.perm_c)
         if gmres:
             x, st["berr"], st["refine_steps"], st["refine_solves"] = h.pdgsrfs3d(b, x, method="gmres")
+        elif extra:
+            x, st["berr"], st["refine_steps"], st["refine_dxrel"], st["refine_state"] = h.pdgsrfs3d(b, x, method="extra")
+            st["refine_rho"] = h.refine_rho
         else:
             x, berr, steps = h.pdgsrfs3d(b, x, block=block)
             st["berr"] = berr; st["refine_steps"] = steps
@@ -908,8 +1002,8 @@ def _gssvx3d_equil(h, symb, n, rowptr, colind, nzval, b, keep, refine, trans):
     """the Equil = YES path of pdgssvx3d: equilibrate on the device, thresh from the scaled matrix's 1-norm, factor, expert solve"""
     eq = h.equilibrate(n, rowptr, colind, nzval, symb.perm_c)
     info = h.pdgstrf3d(0.5 * float(np.finfo(np.float32).eps) * eq["anorm"])
-    gmres, block = refine == "gmres", refine == "block"
-    out = h.gssvx_solve(b, trans=trans, refine=refine and not gmres and not block)
+    gmres, block, extra = refine == "gmres", refine == "block", refine == "extra"
+    out = h.gssvx_solve(b, trans=trans, refine=refine and not gmres and not block and not extra)
     st = h.stats()
     st.update(equed=eq["equed"], rowcnd=eq["rowcnd"], colcnd=eq["colcnd"], amax=eq["amax"])
     if eq["info"] > 0:
@@ -919,6 +1013,12 @@ def _gssvx3d_equil(h, symb, n, rowptr, colind, nzval, b, keep, refine, trans):
         r, c = h.scalings()
         bs = np.asfortranarray(np.array(b, dtype=x.dtype).reshape(x.shape) * r[:, None])
         xs, st["berr"], st["refine_steps"], st["refine_solves"] = h.pdgsrfs3d(bs, np.asfortranarray(x / c[:, None]), method="gmres")
+        x = np.asfortranarray(xs * c[:, None])
+    elif extra:                                                 # (as "gmres": the scaled system)
+        r, c = h.scalings()
+        bs = np.asfortranarray(np.array(b, dtype=x.dtype).reshape(x.shape) * r[:, None])
+        xs, st["berr"], st["refine_steps"], st["refine_dxrel"], st["refine_state"] = h.pdgsrfs3d(bs, np.asfortranarray(x / c[:, None]), method="extra")
+        st["refine_rho"] = h.refine_rho
         x = np.asfortranarray(xs * c[:, None])
     elif block:
         x, st["berr"], st["refine_steps"] = _refine_scaled(h, b, x, block=True)

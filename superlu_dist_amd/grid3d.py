@@ -220,12 +220,16 @@ class GridHandle:
         from .driver import _attach_matrix
         _attach_matrix(self._h, self.z, n, rowptr, colind, nzval, perm_c)
 
-    def pdgsrfs3d(self, b, x, trans="N", block=False):
+    def pdgsrfs3d(self, b, x, trans="N", block=False, method="plain"):
         """Iterative refinement, replicated form (collective): the complete b and initial x (original ordering) on every rank;
         returns (the complete refined x, berr[nrhs], steps) -- the same on every rank.  pzgsrfs3d on a complex16 handle.
         trans = "T" / "C": the system A^T x = b / A^H x = b of the attached matrix (sluamd_p[dz]gsrfs3d_trans; after plan_transposed()), with LUHandle.pdgsrfs3d's argument checks.
-        block=True: the blocked form (sluamd_p[dz]gsrfs3d_block), steps = every column's own count [nrhs]."""
+        block=True: the blocked form (sluamd_p[dz]gsrfs3d_block), steps = every column's own count [nrhs].
+        method: "plain" only -- the GMRES and the extra-precise refinement (LUHandle.pdgsrfs3d(method="gmres" / "extra")) do not run on grids (ValueError)."""
         from .driver import _gsrfs3d, _gsrfs3d_block
+        if method != "plain":
+            raise ValueError(f"GridHandle.pdgsrfs3d(method={method!r}): grids refine with method='plain'; the extra-precise and the GMRES refinement need a "
+                             "1 x 1 x 1 LUHandle")
         if block:
             return _gsrfs3d_block(self._h, self.z, b, x, trans, self.n)
         return _gsrfs3d(self._h, self.z, b, x, trans, self.n)
