@@ -698,6 +698,43 @@ int sluamd_zBatchSolve_dev(sluamd_batch_t b, int trans, const sluamd_doublecompl
 sluamd_handle_t sluamd_BatchHandle(sluamd_batch_t b);
 void sluamd_BatchDestroy(sluamd_batch_t b);
 
+/* ---- The adjoint value gradient: sensitivities of a solve with respect to the stored values of A, from the attached pattern (PDE-constrained optimisation,
+ * implicit layers, parameter fitting around sluamd_[dz]UpdateValues).  For X = op(A)^-1 B and a real scalar loss with gradient Gbar = d loss / d conj(X) (the
+ * convention of PyTorch's complex autograd; for real data simply d loss / d X), the gradient with respect to B is one solve with the adjoint operator, Lam, and the
+ * gradient with respect to the stored entry e = (i, j) of A is a sampled outer product of Lam and X:
+ *   SLUAMD_NOTRANS (A X = B):    G[e] = - sum_r Lam[i, r] conj(X[j, r]),   Lam = A^-H Gbar              (sluamd_p[dz]gssvx3d_solve with SLUAMD_CONJ)
+ *   SLUAMD_TRANS   (A^T X = B):  G[e] = - sum_r conj(X[i, r]) Lam[j, r],   Lam = conj(A)^-1 Gbar = conj(A^-1 conj(Gbar))    (SLUAMD_NOTRANS on conj(Gbar), conjugated)
+ *   SLUAMD_CONJ    (A^H X = B):  G[e] = - sum_r X[i, r] conj(Lam[j, r]),   Lam = A^-1 Gbar               (SLUAMD_NOTRANS)
+ * Real handles: conjugation is the identity, and SLUAMD_TRANS is SLUAMD_CONJ.  trans names the system that was SOLVED; the caller computes Lam.
+ * G[nnz]: in the entry order of the CSR the handle was created from, which is the attached one (sluamd_[dz]AttachMatrix / sluamd_[dz]Equilibrate); a duplicated
+ * (i, j) receives the full value in each of its entries (the derivative of a matrix whose duplicates sum).  Lam and X: n x nrhs, column-major, leading dimensions
+ * ldl, ldx >= n counted in values, in the caller's ordering and scaling -- what sluamd_p[dz]gssvx3d_solve returns, so an equilibrated handle needs nothing
+ * special: the call reads only the PATTERN of the attached matrix, neither its values nor the factors (the handle need not be factored).
+ * One thread per stored entry writes G[e], the sum over r ascending in fused multiply-adds, no atomics: two calls return the same bits.  nrhs > 32 runs in panels
+ * of 32 right-hand sides, every panel after the first accumulating into G in that order.  nrhs == 0 zero-fills G.
+ * The first call builds, on the device, the row of every entry (4 bytes each); the host form stages Lam, X and G through a block the handle keeps (it grows
+ * only); both belong to the attached matrix and go with it.  Both forms synchronise the handle's stream before returning; what produced the device blocks on
+ * another stream must be complete before the call.
+ * Errors, all SLUAMD_EINVAL with a message: null handle or pointers, nrhs < 0, ldl or ldx < n, a trans other than the three, a handle of the other precision
+ * (the message names the twin), no attached matrix, a grid handle, a handle that carries a row permutation (sluamd_SetRowPerm: its entries are those of Pr A),
+ * the handle of a batch.
+ * sluamd_[dz]BatchAdjointValues[_dev]: the same for every matrix of a batch in one launch -- matrix k's Lam, X and G at k strideL, k strideX, k strideG (values;
+ * strideL >= ldl (nrhs - 1) + m, strideX likewise, strideG >= nnz of ONE matrix), the shared pattern read once. */
+int sluamd_dAdjointValues(sluamd_handle_t h, int trans, const double *Lam, int64_t ldl, const double *X, int64_t ldx, int32_t nrhs, double *G);
+int sluamd_dAdjointValues_dev(sluamd_handle_t h, int trans, const double *d_Lam, int64_t ldl, const double *d_X, int64_t ldx, int32_t nrhs, double *d_G);
+int sluamd_zAdjointValues(sluamd_handle_t h, int trans, const sluamd_doublecomplex *Lam, int64_t ldl, const sluamd_doublecomplex *X, int64_t ldx, int32_t nrhs,
+                          sluamd_doublecomplex *G);
+int sluamd_zAdjointValues_dev(sluamd_handle_t h, int trans, const sluamd_doublecomplex *d_Lam, int64_t ldl, const sluamd_doublecomplex *d_X, int64_t ldx,
+                              int32_t nrhs, sluamd_doublecomplex *d_G);
+int sluamd_dBatchAdjointValues(sluamd_batch_t b, int trans, const double *Lam, int64_t ldl, int64_t strideL, const double *X, int64_t ldx, int64_t strideX,
+                               int32_t nrhs, double *G, int64_t strideG);
+int sluamd_dBatchAdjointValues_dev(sluamd_batch_t b, int trans, const double *d_Lam, int64_t ldl, int64_t strideL, const double *d_X, int64_t ldx, int64_t strideX,
+                                   int32_t nrhs, double *d_G, int64_t strideG);
+int sluamd_zBatchAdjointValues(sluamd_batch_t b, int trans, const sluamd_doublecomplex *Lam, int64_t ldl, int64_t strideL, const sluamd_doublecomplex *X,
+                               int64_t ldx, int64_t strideX, int32_t nrhs, sluamd_doublecomplex *G, int64_t strideG);
+int sluamd_zBatchAdjointValues_dev(sluamd_batch_t b, int trans, const sluamd_doublecomplex *d_Lam, int64_t ldl, int64_t strideL, const sluamd_doublecomplex *d_X,
+                                   int64_t ldx, int64_t strideX, int32_t nrhs, sluamd_doublecomplex *d_G, int64_t strideG);
+
 /* ------------------------------------------------------------------------------------------------
  * Process grids: nprow x npcol x npdep ranks, one rank per GPU (gridinfo3d_t, superlu_defs.h:385-420).
  *

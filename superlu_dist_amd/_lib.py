@@ -93,6 +93,8 @@ EXPORTS = [
     "sluamd_dBatchSolve", "sluamd_dBatchSolve_dev", "sluamd_BatchHandle", "sluamd_BatchDestroy",
     "sluamd_zBatchCreate", "sluamd_zBatchUpdateValues", "sluamd_zBatchUpdateValues_dev", "sluamd_zBatchFactor", "sluamd_zBatchEquilibrate",
     "sluamd_zBatchSolve", "sluamd_zBatchSolve_dev",
+    "sluamd_dAdjointValues", "sluamd_dAdjointValues_dev", "sluamd_zAdjointValues", "sluamd_zAdjointValues_dev",
+    "sluamd_dBatchAdjointValues", "sluamd_dBatchAdjointValues_dev", "sluamd_zBatchAdjointValues", "sluamd_zBatchAdjointValues_dev",
     "sluamd_comm_rccl_unique_id", "sluamd_comm_create_rccl", "sluamd_comm_create_callbacks", "sluamd_comm_create_local",
     "sluamd_comm_selftest", "sluamd_comm_rank", "sluamd_comm_size", "sluamd_comm_destroy", "sluamd_dCreateLUHandleGrid",
     "sluamd_dCreateLUHandleFromSymbGrid", "sluamd_zCreateLUHandleGrid", "sluamd_zCreateLUHandleFromSymbGrid",
@@ -249,6 +251,13 @@ def bind(L):
         L.sluamd_zBatchFactor.argtypes = L.sluamd_dBatchFactor.argtypes
         L.sluamd_zBatchEquilibrate.argtypes = L.sluamd_dBatchEquilibrate.argtypes
         L.sluamd_zBatchSolve.argtypes = L.sluamd_zBatchSolve_dev.argtypes = L.sluamd_dBatchSolve.argtypes
+    # the adjoint value gradient: only in the product library (its kernels have no CPU restatement)
+    for name in ("sluamd_dAdjointValues", "sluamd_dAdjointValues_dev", "sluamd_zAdjointValues", "sluamd_zAdjointValues_dev"):
+        if hasattr(L, name):       # (h, trans, Lam, ldl, X, ldx, nrhs, G)
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    for name in ("sluamd_dBatchAdjointValues", "sluamd_dBatchAdjointValues_dev", "sluamd_zBatchAdjointValues", "sluamd_zBatchAdjointValues_dev"):
+        if hasattr(L, name):       # (b, trans, Lam, ldl, strideL, X, ldx, strideX, nrhs, G, strideG)
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64]
     L.sluamd_PlanTransposedSweeps.argtypes = [C.c_void_p]
     L.sluamd_plan_xlists.argtypes = [C.c_void_p, C.c_int, P_int, C.c_int64, C.POINTER(C.c_int64)]
     L.sluamd_comm_rccl_unique_id.argtypes = [C.c_void_p]

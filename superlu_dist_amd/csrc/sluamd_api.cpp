@@ -476,6 +476,7 @@ void free_rfs(Handle *H)
     H->d_gm_work.reset(); H->d_gm_part.reset(); H->gm_restart = 0;            // (and the Krylov workspace of sluamd_p[dz]gsrfs3d_gmres)
     H->d_rfs_bwork.reset(); H->d_rfs_bstage.reset(); H->d_rfs_bs.reset();     // (and the panels of sluamd_p[dz]gsrfs3d_block)
     H->d_xr_s.reset();                                                       // (and the norm words of sluamd_p[dz]gsrfs3d_extra)
+    H->d_adj_erow.reset(); H->d_adj_stage.reset();                           // (and the entry -> row array and the staging block of sluamd_[dz]AdjointValues)
     H->rfs_nnz = 0;
     H->rfs_z = false;
 }

@@ -39,6 +39,10 @@ struct sluamd_batch_s {
     bool factored = false;
 };
 
+namespace sluamd {
+void batch_shape(sluamd_batch_t b, int *m, int *count, int64_t *nnz, bool *z) { *m = b->m; *count = b->count; *nnz = b->nnz; *z = b->z; }
+}
+
 namespace {
 
 void batch_free(sluamd_batch_t b)

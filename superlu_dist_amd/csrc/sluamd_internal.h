@@ -395,6 +395,9 @@ struct Handle {
     // extra-precise refinement (sluamd_xrefine.cpp), allocated on the first such call: the two norm words of a step, max abs1(dx) and max abs1(x).  They go
     // with the attached matrix (free_rfs)
     DevBuf<unsigned long long> d_xr_s;
+    // adjoint value gradient (sluamd_adjoint.cpp), allocated on the first such call: the row of every entry of the attached CSR (of the first matrix's entries
+    // on a batch's handle) and the staging block of the host forms [Lam | X | G] (grows only).  They go with the attached matrix (free_rfs)
+    DevBuf<int> d_adj_erow; DevBuf<double> d_adj_stage;
     bool batch_owned = false;                               // the handle of a batch object (sluamd_BatchHandle lends it out)
     void *h_pinned = nullptr; size_t pinned_bytes = 0;      // bounded pinned staging buffer (value upload / download)
     bool z = false;                                         // complex16 (doublecomplex) values: 16-byte elements
@@ -602,6 +605,8 @@ int reset_store(Handle *H, bool scatter);
 // a 1 x 1 x 1 handle (z: complex16) planned for the structure `s` whose value arena is zero-filled and that keeps no map of any matrix's entries
 // (sluamd_api.cpp): the batch object (sluamd_batch.cpp) distributes the values of its matrices itself, through the entry map of ONE of them
 int create_symb_handle_empty(sluamd_handle_t *out, sluamd_symb_t s, const sluamd_options_t *opt, bool z);
+// order, matrices, entries of ONE matrix and precision of a batch object (sluamd_batch.cpp, which alone knows its layout): what sluamd_adjoint.cpp needs of it
+void batch_shape(sluamd_batch_t b, int *m, int *count, int64_t *nnz, bool *z);
 
 }  // namespace sluamd
 

@@ -252,6 +252,7 @@ class LUHandle:
         self.device = -1                                  # HIP device ordinal given at creation (-1: the device that was current)
         self.rowperm_pos = None                           # pdgssvx3d(rowperm=...): the handle was made from Pr A; values in A's order go through this map
         self.refine_rho = None                            # pdgsrfs3d(method="extra"): per column the largest ratio of successive corrections of the last call
+        self.attached_nnz = None                          # entries of the matrix attach_matrix attached (adjoint_values returns that many); None: self.nnz
 
     @staticmethod
     def _opts(replace_tiny=False, deterministic=False, device=-1, info_rule=0):
@@ -373,6 +374,7 @@ class LUHandle:
     def attach_matrix(self, n, rowptr, colind, nzval, perm_c):
         """Device copy of the ORIGINAL matrix (CSR) + perm_c for pdgsrfs3d (sluamd_dAttachMatrix, or sluamd_zAttachMatrix on a complex16 handle)."""
         _attach_matrix(self._h, self.z, n, rowptr, colind, nzval, perm_c)
+        self.attached_nnz = int(np.asarray(rowptr)[int(n)])
 
     def pdgsrfs3d(self, b, x, trans="N", method="plain", restart=None, inner_tol=None, max_solves=None, block=False):
         """Iterative refinement of x (original ordering) for the attached matrix; returns (x, berr[nrhs], steps).
@@ -464,6 +466,28 @@ class LUHandle:
         """the same on device pointers (ld in values); d_b is not modified; returns (berr, steps) when refine"""
         return _gssvx_solve_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans, refine)
 
+    def adjoint_values(self, lam, x, trans="N"):
+        """The gradient of a loss through x = op(A)^-1 b with respect to the stored values of A (sluamd_[dz]AdjointValues): lam = the adjoint solution, x = the
+        forward solution, both (n,) or (n, nrhs) in the caller's ordering and scaling; trans = the system that was solved.  Returns G[nnz] in the entry order
+        of the CSR the handle was created from; the formulas per trans are at the declaration in include/superlu_dist_amd.h.  Needs an attached matrix
+        (attach_matrix or equilibrate), no factors.  ValueError, before any library call: a trans other than "N", "T", "C"; lam or x of another dtype than the
+        handle's; shapes that differ or are not (n,) / (n, nrhs)."""
+        t = _trans_code(trans)
+        dt = np.complex128 if self.z else np.float64
+        lam, x = _adjoint_pair("adjoint_values", dt, lam, x, (self.n,))
+        nrhs = 1 if lam.ndim == 1 else lam.shape[1]
+        lam = np.asfortranarray(lam.reshape(self.n, nrhs)); x = np.asfortranarray(x.reshape(self.n, nrhs))
+        g = np.zeros(self.nnz if self.attached_nnz is None else self.attached_nnz, dtype=dt)
+        name = "sluamd_zAdjointValues" if self.z else "sluamd_dAdjointValues"
+        ld = max(self.n, 1)
+        _lib.check(_lib.entry(name)(self._h, t, lam.ctypes.data_as(C.c_void_p), ld, x.ctypes.data_as(C.c_void_p), ld, lam.shape[1], g.ctypes.data_as(C.c_void_p)), name)
+        return g
+
+    def adjoint_values_dev(self, d_lam, ldl, d_x, ldx, nrhs, d_g, trans="N"):
+        """sluamd_[dz]AdjointValues_dev: lam, x (column-major, ld in values) and g[nnz] device pointers; what produced them must be complete"""
+        name = "sluamd_zAdjointValues_dev" if self.z else "sluamd_dAdjointValues_dev"
+        _lib.check(_lib.entry(name)(self._h, _trans_code(trans), C.c_void_p(d_lam), int(ldl), C.c_void_p(d_x), int(ldx), int(nrhs), C.c_void_p(d_g)), name)
+
     def set_profile(self, on=True):
         _lib.load().sluamd_set_profile(self._h, int(on))
 
@@ -512,6 +536,19 @@ def _trans_code(trans):
         return {"N": 0, "T": 1, "C": 2}[str(trans).upper()]
     except KeyError:
         raise ValueError(f"trans must be 'N', 'T' or 'C', not {trans!r}") from None
+
+
+def _adjoint_pair(who, dt, lam, x, lead):
+    """lam and x of adjoint_values as arrays; ValueError (before any library call) for another dtype, shapes that differ or are not lead + () / lead + (nrhs,)"""
+    lam, x = np.asarray(lam), np.asarray(x)
+    for what, a in (("lam", lam), ("x", x)):
+        if a.dtype != np.dtype(dt):
+            raise ValueError(f"{who}: the handle holds {np.dtype(dt).name} values, {what} is {a.dtype}")
+        if not (a.flags.c_contiguous or a.flags.f_contiguous):
+            raise ValueError(f"{who}: {what} is not contiguous")
+    if lam.shape != x.shape or lam.ndim not in (len(lead), len(lead) + 1) or lam.shape[:len(lead)] != tuple(lead):
+        raise ValueError(f"{who}: lam and x must both be {tuple(lead)} or {tuple(lead) + ('nrhs',)}, got {lam.shape} and {x.shape}")
+    return lam, x
 
 
 def _check_store_dtype(store, z):
@@ -1123,6 +1160,33 @@ class BatchHandle:
                    self._fn("Solve"))
         x = X.transpose(0, 2, 1)
         return (np.ascontiguousarray(x[:, :, 0]) if one else np.ascontiguousarray(x)), (berr[:, :nrhs] if refine else None), steps
+
+    def solve_dev(self, d_b, ldb, stride_b, d_x, ldx, stride_x, nrhs, trans="N"):
+        """sluamd_[dz]BatchSolve_dev without refinement: matrix k's column-major block at d_b + k stride_b / d_x + k stride_x (device pointers; ld and strides
+        in values); d_b is not modified"""
+        name = self._fn("Solve_dev")
+        _lib.check(_lib.entry(name)(self._b, _trans_code(trans), C.c_void_p(d_b), int(ldb), int(stride_b), C.c_void_p(d_x), int(ldx), int(stride_x), int(nrhs), 0,
+                                    None, None), name)
+
+    def adjoint_values(self, lam, x, trans="N"):
+        """LUHandle.adjoint_values for every matrix of the batch (sluamd_[dz]BatchAdjointValues): lam, x [count, n] or [count, n, nrhs] -> G [count, nnz]"""
+        t = _trans_code(trans)
+        lam, x = _adjoint_pair("adjoint_values", self._dt, lam, x, (self.count, self.n))
+        nrhs = 1 if lam.ndim == 2 else lam.shape[2]
+        Lm = np.ascontiguousarray(lam.reshape(self.count, self.n, nrhs).transpose(0, 2, 1))      # [count, nrhs, n]: every matrix's block column-major
+        Xm = np.ascontiguousarray(x.reshape(self.count, self.n, nrhs).transpose(0, 2, 1))
+        g = np.zeros((self.count, self.nnz), dtype=self._dt)
+        name = self._fn("AdjointValues")
+        ld = max(self.n, 1)
+        _lib.check(_lib.entry(name)(self._b, t, Lm.ctypes.data_as(C.c_void_p), ld, ld * nrhs, Xm.ctypes.data_as(C.c_void_p), ld, ld * nrhs, nrhs,
+                                    g.ctypes.data_as(C.c_void_p), self.nnz), name)
+        return g
+
+    def adjoint_values_dev(self, d_lam, ldl, stride_l, d_x, ldx, stride_x, nrhs, d_g, stride_g, trans="N"):
+        """sluamd_[dz]BatchAdjointValues_dev on device pointers (ld and strides in values)"""
+        name = self._fn("AdjointValues_dev")
+        _lib.check(_lib.entry(name)(self._b, _trans_code(trans), C.c_void_p(d_lam), int(ldl), int(stride_l), C.c_void_p(d_x), int(ldx), int(stride_x), int(nrhs),
+                                    C.c_void_p(d_g), int(stride_g)), name)
 
     def handle(self):
         """the batch's handle, borrowed (an LUHandle-shaped view for stats / setup_times / plan_table; it must not outlive the batch)"""
