@@ -89,7 +89,7 @@ int adjoint_entry(sluamd_handle_t h, int trans, const void *Lv, int64_t ldl, con
     }
     if (H->grid.size() > 1) { set_error(me + "the adjoint value gradient needs a 1 x 1 x 1 handle"); return SLUAMD_EINVAL; }
     if (H->batch_owned) { set_error(me + "the handle belongs to a batch (sluamd_BatchHandle): call sluamd_" + (z ? "z" : "d") + "BatchAdjointValues"); return SLUAMD_EINVAL; }
-    if (int rc = z ? rfs_checks<Rfs<true, 0>>(H) : rfs_checks<Rfs<false, 0>>(H)) return rc;
+    if (int rc = rfs_checks(H)) return rc;
     if (H->d_rp_pr.p) { set_error(me + "the handle carries a row permutation (sluamd_SetRowPerm): its entries are those of Pr A, not of the caller's matrix"); return SLUAMD_EINVAL; }
     HIPCHK(hipSetDevice(H->device));
     const double *Lam = static_cast<const double *>(Lv), *X = static_cast<const double *>(Xv);

@@ -517,12 +517,12 @@ extern "C" {
 
 int sluamd_pdgsrfs3d_dev(sluamd_handle_t h, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    return rfs_entry<Rfs<false, 0>>(h, d_B, ldb, d_X, ldx, nrhs, berr, steps, false, "sluamd_pdgsrfs3d_dev");
+    return rfs_plain<Rfs<false, 0>>({h, SLUAMD_NOTRANS, d_B, ldb, d_X, ldx, nrhs, berr, false, false, "sluamd_pdgsrfs3d_dev"}, steps);
 }
 
 int sluamd_pdgsrfs3d(sluamd_handle_t h, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps)
 {
-    return rfs_entry<Rfs<false, 0>>(h, B, ldb, X, ldx, nrhs, berr, steps, true, "sluamd_pdgsrfs3d");
+    return rfs_plain<Rfs<false, 0>>({h, SLUAMD_NOTRANS, B, ldb, X, ldx, nrhs, berr, false, true, "sluamd_pdgsrfs3d"}, steps);
 }
 
 void sluamd_dDestroyLUHandle(sluamd_handle_t h)

@@ -3,7 +3,9 @@
 // factors with nrhs = 1 and one update per column and step.  One pass of the sweeps serves 16 right-hand sides, so here a panel of RFS_PANEL = 16 columns goes
 // through the loop together: per step ONE residual pass over the active columns, one K::solve with nrhs = the columns that continue, one update of exactly
 // those.  Per column everything is rfs_dev's: the residual and berr (the block kernel runs the column kernel's text), the decision rfs_continue with the
-// column's own lstres and count, the update; a column that has stopped is never read or written again.  Written once over the policies K of rfs_dispatch.
+// column's own lstres and count, the update; a column that has stopped is never read or written again.  Written once over the policies K of rfs_dispatch;
+// the entry is rfs_frame's with this method's facts.  The panel loop (per-column lstres and count, the active list) and the host staging (16-column panels
+// through a buffer of their own, hipMemcpy2D) stay here: folding either into the column forms' would take a mode flag.
 // A file of its own: the CPU test build (oracle/Makefile) links a fixed list of the host sources, none of which may reference a symbol of this file.
 #include <vector>
 #include "sluamd_refine.h"
@@ -114,20 +116,17 @@ template <class K> int brfs_host(Handle *H, const double *B, int64_t ldb, double
 
 int brefine_entry(sluamd_handle_t h, int trans, const void *Bv, int64_t ldb, void *Xv, int64_t ldx, int32_t nrhs, double *berr, int32_t *steps, bool z, bool host, const char *name)
 {
-    const int c = check_solve_args(h, trans, Bv, ldb, Xv, ldx, nrhs, berr, true, z, name, "refinement");
-    if (c < 0) return c;
-    const std::string me = std::string(name) + ": ";
-    Handle *H = &h->H;
-    if (H->batch_owned) { set_error(me + "the handle belongs to a batch (sluamd_BatchHandle): the blocked refinement does not run on batches"); return SLUAMD_EINVAL; }
-    if (int rc = z ? rfs_checks<Rfs<true, 0>>(H) : rfs_checks<Rfs<false, 0>>(H)) return rc;
-    if (H->grid.size() > 1 && !H->comm) { set_error(me + "handle of a multi-rank grid has no communicator"); return SLUAMD_EINVAL; }
-    if (nrhs == 0) return 0;
-    HIPCHK(hipSetDevice(H->device));
-    if (trans != SLUAMD_NOTRANS) { if (int rc = ensure_tindex(H, name)) return rc; }
-    if (int rc = ensure_panel(H, z ? 2 : 1)) return rc;
-    const double *B = static_cast<const double *>(Bv);
-    double *X = static_cast<double *>(Xv);
-    return rfs_dispatch(z, trans, [&](auto K) { return host ? brfs_host<decltype(K)>(H, B, ldb, X, ldx, nrhs, berr, steps) : brfs_dev<decltype(K)>(H, B, ldb, X, ldx, nrhs, berr, steps); });
+    const RfsCall a = {h, trans, Bv, ldb, Xv, ldx, nrhs, berr, z, host, name};
+    if (const int c = rfs_args(a); c < 0) return c;
+    const RfsMethod m = {"blocked", true, false, false, nullptr};      // runs on grids, not on batches; nrhs == 0 writes nothing
+    return rfs_frame<RfsAnyForm>(m, a,
+        [&](Handle *H) {
+            // (no creation call leaves such a handle: both refuse a multi-rank grid without a communicator)
+            if (H->grid.size() > 1 && !H->comm) { set_error(std::string(name) + ": handle of a multi-rank grid has no communicator"); return (int) SLUAMD_EINVAL; }
+            return ensure_panel(H, z ? 2 : 1);
+        },
+        [&](auto K, Handle *H) { return brfs_host<decltype(K)>(H, a.b(), ldb, a.x(), ldx, nrhs, berr, steps); },
+        [&](auto K, Handle *H) { return brfs_dev<decltype(K)>(H, a.b(), ldb, a.x(), ldx, nrhs, berr, steps); });
 }
 
 }  // namespace

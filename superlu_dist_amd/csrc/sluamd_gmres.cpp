@@ -1,6 +1,7 @@
 // sluamd_gmres.cpp -- GMRES refinement preconditioned by the resident factors: sluamd_p[dz]gsrfs3d_gmres[_dev] (contract: include/superlu_dist_amd.h;
-// the algorithm, CGS2, the reduction order and the storage: DESIGN.md "GMRES refinement").  The outer loop is rfs_dev's (sluamd_refine.h) with the same policies
-// K -- the true residual and berr by K::residual, the same stop rule, K::update -- and the correction K::solve(r) replaced by one cycle of right-preconditioned
+// the algorithm, CGS2, the reduction order and the storage: DESIGN.md "GMRES refinement").  The entry frame, the host staging and the outer loop are
+// sluamd_refine.h's (rfs_frame_by_column, rfs_dev) with the same policies K -- the true residual and berr by K::residual, the same stop rule, K::update --
+// and, as the step of that loop, the correction K::solve(r) replaced by one cycle of right-preconditioned
 // GMRES on A1 d = r in the permuted space, A1 = Pc op(A) Pc^T, M = L U, d_0 = 0.  K::solve is the only way into the sweeps.
 //   A1 z from the policy kernels: x0 = 0; K::update(x0 += Pc^T z); K::residual(x0, b = 0) = Pc (0 - op(A) x0) = -A1 z.  The sign is not undone by a pass of
 //   its own: CGS2 runs on w' = -w (every coefficient comes out negated, the norm does not), the host negates the Hessenberg column and v_{j+1} = w' / (-h).
@@ -166,79 +167,36 @@ template <class K> int gmres_cycle(Handle *H, const Work &W, const sluamd_gmres_
     return 0;
 }
 
-// d_B, d_X: device-resident, original ordering, column-major (ld in values); the loop of rfs_dev with the correction of a step replaced
-template <class K> int gmres_dev(sluamd_handle_t h, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, const sluamd_gmres_t &o, double *berr, int32_t *steps,
+// d_B, d_X: device-resident, original ordering, column-major (ld in values): rfs_dev with the residual in W.w and the step below.  solves_out[nrhs], may be
+// null: the applications of the factors per column, at most o.max_solves
+template <class K> int gmres_dev(Handle *H, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int32_t nrhs, const sluamd_gmres_t &o, double *berr, int32_t *steps,
                                  int32_t *solves_out)
 {
-    Handle *H = &h->H;
-    HIPCHK(hipSetDevice(H->device));
     Work W;
     if (int rc = ensure_work(H, o.restart, K::z, W)) return rc;
-    const int vs = K::z ? 2 : 1;
-    const int n = (int) H->hs.n;
-    const RfsGuards g = rfs_guards(n);
-    hipStream_t s = H->stream;
-    int count = 0;
-    for (int j = 0; j < nrhs; ++j) {
-        const double *Bc = d_B + (size_t) j * ldb * vs;
-        double *Xc = d_X + (size_t) j * ldx * vs;
-        double lstres = 3.0;
-        int solves = 0;
-        count = 0;
-        for (;;) {
-            HIPCHK(hipMemsetAsync(H->d_rfs_s.p, 0, sizeof(unsigned long long), s));
-            K::residual(s, H, Xc, Bc, W.w, g.safe1, g.safe2);
-            double sv = 0.0;
-            HIPCHK(hipMemcpyAsync(&sv, H->d_rfs_s.p, sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            berr[j] = sv;
-            if (!(rfs_continue(sv, lstres, count) && solves < o.max_solves)) break;
-            // one application left: a cycle needs two (an iteration and the end of the cycle), so the step is the plain one
-            const int rc = o.max_solves - solves < 2 ? 1 : gmres_cycle<K>(H, W, o, Xc, g.safe1, g.safe2, solves);
-            if (rc < 0) return rc;
-            if (rc == 2) break;
-            if (rc == 1) {
-                if (int rs = K::solve(H, W.w, n)) return rs;
-                ++solves;
-                K::update(s, H, W.w, Xc);
-            }
-            lstres = sv;
-            ++count;
+    const RfsGuards g = rfs_guards(H->hs.n);
+    std::vector<int32_t> own(solves_out ? 0 : (size_t) nrhs);
+    int32_t *solves = solves_out ? solves_out : own.data();
+    std::fill(solves, solves + nrhs, 0);
+    return rfs_dev<K>(H, d_B, ldb, d_X, ldx, nrhs, W.w, berr, steps, [&](int j, double *Xc, double *r, double) -> int {
+        if (solves[j] >= o.max_solves) return RFS_STOP;             // the budget ends the column like the stop rule does
+        // one application left: a cycle needs two (an iteration and the end of the cycle), so the step is the plain one
+        const int rc = o.max_solves - solves[j] < 2 ? 1 : gmres_cycle<K>(H, W, o, Xc, g.safe1, g.safe2, solves[j]);
+        if (rc < 0) return rc;
+        if (rc == 2) return RFS_STOP;
+        if (rc == 1) {
+            if (int rs = rfs_plain_step<K>(H, Xc, r)) return rs;
+            ++solves[j];
         }
-        if (solves_out) solves_out[j] = solves;
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-    if (steps) *steps = count;
-    return 0;
-}
-
-// B, X: host memory; one column at a time through the resident work vectors of the plain refinement (r_perm | b | x), as rfs_host
-template <class K> int gmres_host(sluamd_handle_t h, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, const sluamd_gmres_t &o, double *berr, int32_t *steps,
-                                  int32_t *solves)
-{
-    Handle *H = &h->H;
-    HIPCHK(hipSetDevice(H->device));
-    const int vs = K::z ? 2 : 1;
-    const int64_t n = H->hs.n;
-    const size_t col = sizeof(double) * (size_t) n * vs;
-    double *d_b = H->d_rfs_work.p + (size_t) n * vs, *d_x = H->d_rfs_work.p + 2 * (size_t) n * vs;
-    int last = 0;
-    for (int j = 0; j < nrhs; ++j) {
-        HIPCHK(hipMemcpy(d_b, B + (size_t) j * ldb * vs, col, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_x, X + (size_t) j * ldx * vs, col, hipMemcpyHostToDevice));
-        if (int rc = gmres_dev<K>(h, d_b, n, d_x, n, 1, o, berr + j, &last, solves ? solves + j : nullptr)) return rc;
-        HIPCHK(hipMemcpy(X + (size_t) j * ldx * vs, d_x, col, hipMemcpyDeviceToHost));
-    }
-    if (steps) *steps = last;
-    return 0;
+        return RFS_STEPPED;
+    });
 }
 
 int gmres_entry(sluamd_handle_t h, int trans, const void *Bv, int64_t ldb, void *Xv, int64_t ldx, int32_t nrhs, const sluamd_gmres_t *opt, double *berr, int32_t *steps,
                 int32_t *solves, bool z, bool host, const char *name)
 {
-    const int c = check_solve_args(h, trans, Bv, ldb, Xv, ldx, nrhs, berr, true, z, name, "refinement");
-    if (c < 0) return c;
+    const RfsCall a = {h, trans, Bv, ldb, Xv, ldx, nrhs, berr, z, host, name};
+    if (const int c = rfs_args(a); c < 0) return c;
     const std::string me = std::string(name) + ": ";
     sluamd_gmres_t o;
     sluamd_default_gmres(&o);
@@ -246,15 +204,11 @@ int gmres_entry(sluamd_handle_t h, int trans, const void *Bv, int64_t ldb, void 
     if (o.restart < 1 || o.restart > GM_MAX_RESTART) { set_error(me + "restart must lie in [1, 64]"); return SLUAMD_EINVAL; }
     if (o.max_solves < 1) { set_error(me + "max_solves must be at least 1"); return SLUAMD_EINVAL; }
     if (!(o.inner_tol > 0.0 && o.inner_tol < 1.0)) { set_error(me + "inner_tol must lie in (0, 1)"); return SLUAMD_EINVAL; }
-    Handle *H = &h->H;
-    if (H->grid.size() > 1) { set_error(me + "the GMRES refinement needs a 1 x 1 x 1 handle (grid handles refine with sluamd_p[dz]gsrfs3d[_trans])"); return SLUAMD_EINVAL; }
-    if (H->batch_owned) { set_error(me + "the handle belongs to a batch (sluamd_BatchHandle): the GMRES refinement does not run on batches"); return SLUAMD_EINVAL; }
-    if (int rc = z ? rfs_checks<Rfs<true, 0>>(H) : rfs_checks<Rfs<false, 0>>(H)) return rc;
-    if (nrhs == 0) { if (steps) *steps = 0; return 0; }
-    if (trans != SLUAMD_NOTRANS) { if (int rc = ensure_tindex(H, name)) return rc; }
-    const double *B = static_cast<const double *>(Bv);
-    double *X = static_cast<double *>(Xv);
-    return rfs_dispatch(z, trans, [&](auto K) { return host ? gmres_host<decltype(K)>(h, B, ldb, X, ldx, nrhs, o, berr, steps, solves) : gmres_dev<decltype(K)>(h, B, ldb, X, ldx, nrhs, o, berr, steps, solves); });
+    const RfsMethod m = {"GMRES", false, false, false, steps};                // (the options above: before these) neither on grids nor on batches; nrhs == 0 writes *steps = 0
+    return rfs_frame_by_column<RfsAnyForm>(m, a, [](Handle *) { return 0; },   // (the Krylov workspace: ensure_work, per call of gmres_dev -- it clears the pad every time)
+        [&](auto K, Handle *H, const double *d_B, int64_t ldb_, double *d_X, int64_t ldx_, int32_t nr, int j0) {
+            return gmres_dev<decltype(K)>(H, d_B, ldb_, d_X, ldx_, nr, o, berr + j0, steps, solves ? solves + j0 : nullptr);
+        });
 }
 
 }  // namespace

@@ -2,7 +2,8 @@
 // matrix on its own, sluamd_[dz]Residual[_dev] (contract: include/superlu_dist_amd.h; the loop and why berr cannot stop it: DESIGN.md "Extra-precise
 // refinement").  The residual of a step is accumulated in twice the working precision (sluamd_xkernels.inc, included here), the correction and the update are
 // the policies' K::solve and K::update (sluamd_refine.h), and the loop watches the corrections: it ends when one is below eps relative to x, when one fails
-// to halve, or after ITMAX steps.  x stays fp64.
+// to halve, or after ITMAX steps.  x stays fp64.  That stop rule keeps the loop (xrfs_dev) apart from rfs_dev; the entries, the pass (rfs_berr_pass around this
+// file's residual launch) and the host staging are sluamd_refine.h's.
 // A file of its own: the CPU test build (oracle/Makefile) links a fixed list of the host sources, none of which may reference a symbol of this file.
 #include <algorithm>
 #include <cmath>
@@ -19,12 +20,7 @@ constexpr int XR_ITMAX = 20;                                    // pdgsrfs.c:371
 // the pass of a step: r_out = b - op(A) x with the output index pc (null: the caller's ordering); returns the backward error in *sv
 template <class K> int xr_pass(Handle *H, bool extra, const double *x, const double *b, const int *pc, double *r_out, const RfsGuards &g, double *sv)
 {
-    hipStream_t s = H->stream;
-    HIPCHK(hipMemsetAsync(H->d_rfs_s.p, 0, sizeof(unsigned long long), s));
-    xeng::residual(s, K::z, K::trans == 2, extra, rfs_mat(H, K::trans != 0), x, b, pc, r_out, H->d_rfs_s.p, g.safe1, g.safe2);
-    HIPCHK(hipMemcpyAsync(sv, H->d_rfs_s.p, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    return rfs_berr_pass(H, sv, [&](hipStream_t s) { xeng::residual(s, K::z, K::trans == 2, extra, rfs_mat(H, K::trans != 0), x, b, pc, r_out, H->d_rfs_s.p, g.safe1, g.safe2); });
 }
 
 // d_B, d_X: device-resident, original ordering, column-major (ld in values); X holds the initial solution and is refined in place
@@ -71,61 +67,36 @@ template <class K> int xrfs_dev(Handle *H, const double *d_B, int64_t ldb, doubl
     return 0;
 }
 
-// B, X: host memory; one column at a time through the resident work vectors of the plain refinement (r_perm | b | x), as rfs_host
-template <class K> int xrfs_host(Handle *H, const double *B, int64_t ldb, double *X, int64_t ldx, int32_t nrhs, double *berr, sluamd_xrefine_t *out)
-{
-    const int vs = K::z ? 2 : 1;
-    const int64_t n = H->hs.n;
-    const size_t col = sizeof(double) * (size_t) n * vs;
-    double *d_b = H->d_rfs_work.p + (size_t) n * vs, *d_x = H->d_rfs_work.p + 2 * (size_t) n * vs;
-    for (int j = 0; j < nrhs; ++j) {
-        HIPCHK(hipMemcpy(d_b, B + (size_t) j * ldb * vs, col, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_x, X + (size_t) j * ldx * vs, col, hipMemcpyHostToDevice));
-        if (int rc = xrfs_dev<K>(H, d_b, n, d_x, n, 1, berr + j, out ? out + j : nullptr)) return rc;
-        HIPCHK(hipMemcpy(X + (size_t) j * ldx * vs, d_x, col, hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-
 int xrefine_entry(sluamd_handle_t h, int trans, const void *Bv, int64_t ldb, void *Xv, int64_t ldx, int32_t nrhs, double *berr, sluamd_xrefine_t *out, bool z, bool host,
                   const char *name)
 {
-    const int c = check_solve_args(h, trans, Bv, ldb, Xv, ldx, nrhs, berr, true, z, name, "refinement");
-    if (c < 0) return c;
-    const std::string me = std::string(name) + ": ";
-    Handle *H = &h->H;
-    if (H->grid.size() > 1) { set_error(me + "the extra-precise refinement needs a 1 x 1 x 1 handle (grid handles refine with sluamd_p[dz]gsrfs3d[_trans])"); return SLUAMD_EINVAL; }
-    if (H->batch_owned) { set_error(me + "the handle belongs to a batch (sluamd_BatchHandle): the extra-precise refinement does not run on batches"); return SLUAMD_EINVAL; }
-    if (int rc = z ? rfs_checks<Rfs<true, 0>>(H) : rfs_checks<Rfs<false, 0>>(H)) return rc;
-    if (nrhs == 0) return 0;
-    HIPCHK(hipSetDevice(H->device));
-    if (trans != SLUAMD_NOTRANS) { if (int rc = ensure_tindex(H, name)) return rc; }
-    if (!H->d_xr_s.p) { if (int rc = H->d_xr_s.alloc(2, H->device, "the norm words of the extra-precise refinement")) return rc; }
-    const double *B = static_cast<const double *>(Bv);
-    double *X = static_cast<double *>(Xv);
-    return rfs_dispatch(z, trans, [&](auto K) { return host ? xrfs_host<decltype(K)>(H, B, ldb, X, ldx, nrhs, berr, out) : xrfs_dev<decltype(K)>(H, B, ldb, X, ldx, nrhs, berr, out); });
+    const RfsCall a = {h, trans, Bv, ldb, Xv, ldx, nrhs, berr, z, host, name};
+    if (const int c = rfs_args(a); c < 0) return c;
+    const RfsMethod m = {"extra-precise", false, false, false, nullptr};   // neither on grids nor on batches; nrhs == 0 writes nothing
+    return rfs_frame_by_column<RfsAnyForm>(m, a,
+        [](Handle *H) { return H->d_xr_s.p ? 0 : H->d_xr_s.alloc(2, H->device, "the norm words of the extra-precise refinement"); },
+        [&](auto K, Handle *H, const double *d_B, int64_t ldb_, double *d_X, int64_t ldx_, int32_t nr, int j0) {
+            return xrfs_dev<decltype(K)>(H, d_B, ldb_, d_X, ldx_, nr, berr + j0, out ? out + j0 : nullptr);
+        });
 }
 
-// R = B - op(A) X, column by column; host: through the resident work vectors (r | b | x)
+// R = B - op(A) X, column by column; host: through the resident work vectors (r | b | x), r copied back
 template <class K> int residual_cols(Handle *H, bool extra, const double *B, int64_t ldb, const double *X, int64_t ldx, int32_t nrhs, double *R, int64_t ldr, double *berr,
                                      bool host)
 {
     const int vs = K::z ? 2 : 1;
-    const int64_t n = H->hs.n;
-    const RfsGuards g = rfs_guards(n);
-    const size_t col = sizeof(double) * (size_t) n * vs;
-    double *d_r = H->d_rfs_work.p, *d_b = d_r + (size_t) n * vs, *d_x = d_r + 2 * (size_t) n * vs;
-    for (int j = 0; j < nrhs; ++j) {
-        const double *Bc = B + (size_t) j * ldb * vs, *Xc = X + (size_t) j * ldx * vs;
-        double *Rc = R + (size_t) j * ldr * vs;
+    const RfsGuards g = rfs_guards(H->hs.n);
+    auto column = [&](int j, const double *b, const double *x, double *r) {
         double sv = 0.0;
-        if (host) {
-            HIPCHK(hipMemcpy(d_b, Bc, col, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(d_x, Xc, col, hipMemcpyHostToDevice));
-        }
-        if (int rc = xr_pass<K>(H, extra, host ? d_x : Xc, host ? d_b : Bc, nullptr, host ? d_r : Rc, g, &sv)) return rc;
-        if (host) HIPCHK(hipMemcpy(Rc, d_r, col, hipMemcpyDeviceToHost));
+        if (int rc = xr_pass<K>(H, extra, x, b, nullptr, r, g, &sv)) return rc;
         if (berr) berr[j] = sv;
+        return 0;
+    };
+    if (host) {
+        if (int rc = rfs_staged(H, B, ldb, X, ldx, nrhs, R, ldr, 0, [&](int j, const double *d_b, const double *d_x) { return column(j, d_b, d_x, H->d_rfs_work.p); })) return rc;
+    } else {
+        for (int j = 0; j < nrhs; ++j)
+            if (int rc = column(j, B + (size_t) j * ldb * vs, X + (size_t) j * ldx * vs, R + (size_t) j * ldr * vs)) return rc;
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -144,13 +115,12 @@ int residual_entry(sluamd_handle_t h, int trans, int extra, const void *Bv, int6
         set_error(me + (z ? "double" : "complex16") + " handle: call " + twin);
         return SLUAMD_EINVAL;
     }
-    if (int rc = z ? rfs_checks<Rfs<true, 0>>(H) : rfs_checks<Rfs<false, 0>>(H)) return rc;
-    if (nrhs == 0) return 0;
-    HIPCHK(hipSetDevice(H->device));
-    if (trans != SLUAMD_NOTRANS) { if (int rc = ensure_tindex(H, name)) return rc; }
-    const double *B = static_cast<const double *>(Bv), *X = static_cast<const double *>(Xv);
+    // its own argument checks above (a third block R, berr optional); from here the frame.  X is only read
+    const RfsCall a = {h, trans, Bv, ldb, const_cast<void *>(Xv), ldx, nrhs, berr, z, host, name};
+    const RfsMethod m = {nullptr, true, true, false, nullptr};
     double *R = static_cast<double *>(Rv);
-    return rfs_dispatch(z, trans, [&](auto K) { return residual_cols<decltype(K)>(H, extra != 0, B, ldb, X, ldx, nrhs, R, ldr, berr, host); });
+    auto cols = [&](auto K, Handle *H_) { return residual_cols<decltype(K)>(H_, extra != 0, a.b(), ldb, a.x(), ldx, nrhs, R, ldr, berr, host); };
+    return rfs_frame<RfsAnyForm>(m, a, [](Handle *) { return 0; }, cols, cols);
 }
 
 }  // namespace

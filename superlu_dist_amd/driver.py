@@ -394,14 +394,10 @@ class LUHandle:
         trans = "T" / "C"; not with block=True, restart, inner_tol or max_solves (ValueError)."""
         _check_block(block, method)
         opt = _gmres_opt(method, restart, inner_tol, max_solves)
+        out = _refine(self._h, self.z, "block" if block else method, self.n, b, x, trans, opt)
         if method == "extra":
-            x, berr, steps, dxrel, state, self.refine_rho = _gsrfs3d_extra(self._h, self.z, b, x, trans, self.n)
-            return x, berr, steps, dxrel, state
-        if opt is not None:
-            return _gsrfs3d_gmres(self._h, self.z, b, x, trans, self.n, opt)
-        if block:
-            return _gsrfs3d_block(self._h, self.z, b, x, trans, self.n)
-        return _gsrfs3d(self._h, self.z, b, x, trans, self.n)
+            *out, self.refine_rho = out
+        return tuple(out)
 
     pzgsrfs3d = pdgsrfs3d
 
@@ -426,14 +422,10 @@ class LUHandle:
         method="extra": sluamd_p[dz]gsrfs3d_extra_dev, returns (berr[nrhs], steps[nrhs], dxrel[nrhs], state[nrhs]); self.refine_rho as pdgsrfs3d."""
         _check_block(block, method)
         opt = _gmres_opt(method, restart, inner_tol, max_solves)
+        out = _refine_call(self._h, self.z, "block" if block else method, False, trans, d_b, ldb, d_x, ldx, nrhs, opt)
         if method == "extra":
-            berr, steps, dxrel, state, self.refine_rho = _gsrfs3d_extra_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans)
-            return berr, steps, dxrel, state
-        if opt is not None:
-            return _gsrfs3d_gmres_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans, opt)
-        if block:
-            return _gsrfs3d_block_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans)
-        return _gsrfs3d_dev(self._h, self.z, d_b, ldb, d_x, ldx, nrhs, trans)
+            *out, self.refine_rho = out
+        return tuple(out)
 
     pzgsrfs3d_dev = pdgsrfs3d_dev
 
@@ -569,74 +561,28 @@ def _attach_matrix(h, z, n, rowptr, colind, nzval, perm_c):
         _lib.check(_lib.load().sluamd_dAttachMatrix(h, int(n), _pi(rp), _pi(ci), _pd(v), _pi(pc)), "sluamd_dAttachMatrix")
 
 
-def _gsrfs3d(h, z, b, x, trans="N", n=None):
-    t = _trans_code(trans)
-    dt = np.complex128 if z else np.float64
-    if t:                                                   # the transposed forms refuse what the untransposed call converts (ValueError, before any library call)
+def _rhs_pair(who, z, b, x, n, strict=True):
+    """b and x of a refinement or residual call as Fortran-ordered copies of the handle's dtype, promoted to 2-D: (b, x, one), one = they came as vectors.
+    strict: ValueError (before any library call, the message starting with `who`) for another dtype, shapes that differ or are not (n,) / (n, nrhs);
+    strict=False is the plain untransposed call, which converts instead."""
+    dt = np.dtype(np.complex128 if z else np.float64)
+    if strict:
         for what, a in (("b", b), ("x", x)):
-            if np.asarray(a).dtype != np.dtype(dt):
-                raise ValueError(f"pdgsrfs3d(trans={trans!r}): the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
+            if np.asarray(a).dtype != dt:
+                raise ValueError(f"{who}: the handle holds {dt.name} values, {what} is {np.asarray(a).dtype}")
         if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
-            raise ValueError(f"pdgsrfs3d(trans={trans!r}): b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
+            raise ValueError(f"{who}: b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
     b = np.asfortranarray(np.array(b, dtype=dt)); x = np.asfortranarray(np.array(x, dtype=dt))
-    if b.ndim == 1:
+    one = b.ndim == 1
+    if one:
         b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
-    berr = np.zeros(b.shape[1]); steps = C.c_int32(0)
-    if t:
-        name = "sluamd_pzgsrfs3d_trans" if z else "sluamd_pdgsrfs3d_trans"
-        _lib.check(_lib.entry(name)(h, t, b.ctypes.data_as(C.c_void_p), b.shape[0], x.ctypes.data_as(C.c_void_p), x.shape[0], b.shape[1], _pd(berr),
-                                    C.byref(steps)), name)
-        return x, berr, steps.value
-    name = "sluamd_pzgsrfs3d" if z else "sluamd_pdgsrfs3d"
-    _lib.check(_lib.entry(name)(h, b.ctypes.data_as(C.c_void_p) if z else _pd(b), b.shape[0], x.ctypes.data_as(C.c_void_p) if z else _pd(x),
-                                x.shape[0], b.shape[1], _pd(berr), C.byref(steps)), name)
-    return x, berr, steps.value
-
-
-def _gsrfs3d_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans="N"):
-    t = _trans_code(trans)
-    berr = np.zeros(max(int(nrhs), 1)); steps = C.c_int32(0)
-    if t:
-        name = "sluamd_pzgsrfs3d_trans_dev" if z else "sluamd_pdgsrfs3d_trans_dev"
-        _lib.check(_lib.entry(name)(h, t, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), _pd(berr), C.byref(steps)), name)
-        return berr[:int(nrhs)], steps.value
-    name = "sluamd_pzgsrfs3d_dev" if z else "sluamd_pdgsrfs3d_dev"
-    _lib.check(_lib.entry(name)(h, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), _pd(berr), C.byref(steps)), name)
-    return berr[:int(nrhs)], steps.value
+    return b, x, one
 
 
 def _check_block(block, method):
-    if block and method == "gmres":
-        raise ValueError("block=True belongs to method='plain': the GMRES refinement takes one right-hand side at a time")
-    if block and method == "extra":
-        raise ValueError("block=True belongs to method='plain': the extra-precise refinement takes one right-hand side at a time")
-
-
-def _gsrfs3d_block(h, z, b, x, trans, n):
-    """sluamd_p[dz]gsrfs3d_block on host arrays: (x, berr[nrhs], steps[nrhs])"""
-    t = _trans_code(trans)
-    dt = np.complex128 if z else np.float64
-    for what, a in (("b", b), ("x", x)):
-        if np.asarray(a).dtype != np.dtype(dt):
-            raise ValueError(f"pdgsrfs3d(block=True): the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
-    if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
-        raise ValueError(f"pdgsrfs3d(block=True): b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
-    b = np.asfortranarray(np.array(b, dtype=dt)); x = np.asfortranarray(np.array(x, dtype=dt))
-    if b.ndim == 1:
-        b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
-    nrhs = b.shape[1]
-    berr = np.zeros(max(nrhs, 1)); steps = np.zeros(max(nrhs, 1), dtype=np.int32)
-    name = "sluamd_pzgsrfs3d_block" if z else "sluamd_pdgsrfs3d_block"
-    _lib.check(_lib.entry(name)(h, t, b.ctypes.data_as(C.c_void_p), max(b.shape[0], 1), x.ctypes.data_as(C.c_void_p), max(x.shape[0], 1), nrhs, _pd(berr), _pi(steps)), name)
-    return x, berr[:nrhs], steps[:nrhs]
-
-
-def _gsrfs3d_block_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans):
-    t = _trans_code(trans)
-    berr = np.zeros(max(int(nrhs), 1)); steps = np.zeros(max(int(nrhs), 1), dtype=np.int32)
-    name = "sluamd_pzgsrfs3d_block_dev" if z else "sluamd_pdgsrfs3d_block_dev"
-    _lib.check(_lib.entry(name)(h, t, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), _pd(berr), _pi(steps)), name)
-    return berr[:int(nrhs)], steps[:int(nrhs)]
+    if block and method in ("gmres", "extra"):
+        noun = "GMRES" if method == "gmres" else "extra-precise"
+        raise ValueError(f"block=True belongs to method='plain': the {noun} refinement takes one right-hand side at a time")
 
 
 def _gmres_opt(method, restart, inner_tol, max_solves):
@@ -660,33 +606,6 @@ def _gmres_opt(method, restart, inner_tol, max_solves):
     return o
 
 
-def _gsrfs3d_gmres(h, z, b, x, trans, n, opt):
-    t = _trans_code(trans)
-    dt = np.complex128 if z else np.float64
-    for what, a in (("b", b), ("x", x)):
-        if np.asarray(a).dtype != np.dtype(dt):
-            raise ValueError(f"pdgsrfs3d(method='gmres'): the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
-    if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
-        raise ValueError(f"pdgsrfs3d(method='gmres'): b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
-    b = np.asfortranarray(np.array(b, dtype=dt)); x = np.asfortranarray(np.array(x, dtype=dt))
-    if b.ndim == 1:
-        b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
-    nrhs = b.shape[1]
-    berr = np.zeros(max(nrhs, 1)); steps = C.c_int32(0); solves = np.zeros(max(nrhs, 1), dtype=np.int32)
-    name = "sluamd_pzgsrfs3d_gmres" if z else "sluamd_pdgsrfs3d_gmres"
-    _lib.check(_lib.entry(name)(h, t, b.ctypes.data_as(C.c_void_p), max(b.shape[0], 1), x.ctypes.data_as(C.c_void_p), max(x.shape[0], 1), nrhs, C.byref(opt), _pd(berr),
-                                C.byref(steps), _pi(solves)), name)
-    return x, berr[:nrhs], steps.value, solves[:nrhs]
-
-
-def _gsrfs3d_gmres_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans, opt):
-    t = _trans_code(trans)
-    berr = np.zeros(max(int(nrhs), 1)); steps = C.c_int32(0); solves = np.zeros(max(int(nrhs), 1), dtype=np.int32)
-    name = "sluamd_pzgsrfs3d_gmres_dev" if z else "sluamd_pdgsrfs3d_gmres_dev"
-    _lib.check(_lib.entry(name)(h, t, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), int(nrhs), C.byref(opt), _pd(berr), C.byref(steps), _pi(solves)), name)
-    return berr[:int(nrhs)], steps.value, solves[:int(nrhs)]
-
-
 def _xrefine_out(out, nrhs):
     """sluamd_xrefine_t[nrhs] -> steps, dxrel, state, rho as arrays"""
     o = out[:nrhs]
@@ -694,46 +613,56 @@ def _xrefine_out(out, nrhs):
             np.array([v.state for v in o], dtype=np.int32), np.array([v.rho for v in o], dtype=np.float64))
 
 
-def _gsrfs3d_extra(h, z, b, x, trans, n):
-    """sluamd_p[dz]gsrfs3d_extra on host arrays: (x, berr[nrhs], steps[nrhs], dxrel[nrhs], state[nrhs], rho[nrhs])"""
+def _refine_call(h, z, form, host, trans, b, ldb, x, ldx, nrhs, opt=None):
+    """One call of sluamd_p[dz]gsrfs3d{,_trans,_block,_gmres,_extra}{,_dev}.  form: "plain" (with trans != "N": the _trans entry), "block", "gmres" (opt: its
+    sluamd_gmres_t) or "extra"; b, x: Fortran-ordered arrays (host) or device pointers as integers.  Returns berr[nrhs] and the form's outputs --
+    plain: steps; block: steps[nrhs]; gmres: steps, solves[nrhs]; extra: steps[nrhs], dxrel[nrhs], state[nrhs], rho[nrhs]"""
     t = _trans_code(trans)
-    dt = np.complex128 if z else np.float64
-    for what, a in (("b", b), ("x", x)):
-        if np.asarray(a).dtype != np.dtype(dt):
-            raise ValueError(f"pdgsrfs3d(method='extra'): the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
-    if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
-        raise ValueError(f"pdgsrfs3d(method='extra'): b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
-    b = np.asfortranarray(np.array(b, dtype=dt)); x = np.asfortranarray(np.array(x, dtype=dt))
-    if b.ndim == 1:
-        b = np.asfortranarray(b[:, None]); x = np.asfortranarray(x[:, None])
-    nrhs = b.shape[1]
-    berr = np.zeros(max(nrhs, 1)); out = (_lib.XRefine * max(nrhs, 1))()
-    name = "sluamd_pzgsrfs3d_extra" if z else "sluamd_pdgsrfs3d_extra"
-    _lib.check(_lib.entry(name)(h, t, b.ctypes.data_as(C.c_void_p), max(b.shape[0], 1), x.ctypes.data_as(C.c_void_p), max(x.shape[0], 1), nrhs, _pd(berr), out), name)
-    steps, dxrel, state, rho = _xrefine_out(out, nrhs)
-    return x, berr[:nrhs], steps, dxrel, state, rho
+    nrhs, m = int(nrhs), max(int(nrhs), 1)
+    berr = np.zeros(m)
+    if host:                                                # (sluamd_pdgsrfs3d alone is bound with double pointers)
+        typed = form == "plain" and not t and not z
+        pb, px = (_pd(b), _pd(x)) if typed else (b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p))
+    else:
+        pb, px = C.c_void_p(b), C.c_void_p(x)
+    blocks = (pb, int(ldb), px, int(ldx), nrhs)
+    steps = C.c_int32(0); per = np.zeros(m, dtype=np.int32)         # the call's step count / a count per column
+    if form == "plain" and not t:
+        suffix, args = "", (h,) + blocks + (_pd(berr), C.byref(steps))
+    elif form == "plain":
+        suffix, args = "_trans", (h, t) + blocks + (_pd(berr), C.byref(steps))
+    elif form == "block":
+        suffix, args = "_block", (h, t) + blocks + (_pd(berr), _pi(per))
+    elif form == "gmres":
+        suffix, args = "_gmres", (h, t) + blocks + (None if opt is None else C.byref(opt), _pd(berr), C.byref(steps), _pi(per))
+    else:
+        out = (_lib.XRefine * m)()
+        suffix, args = "_extra", (h, t) + blocks + (_pd(berr), out)
+    name = "sluamd_p%sgsrfs3d%s%s" % ("z" if z else "d", suffix, "" if host else "_dev")
+    _lib.check(_lib.entry(name)(*args), name)
+    berr = berr[:nrhs]
+    if form == "plain":
+        return berr, steps.value
+    if form == "block":
+        return berr, per[:nrhs]
+    if form == "gmres":
+        return berr, steps.value, per[:nrhs]
+    return (berr,) + _xrefine_out(out, nrhs)
 
 
-def _gsrfs3d_extra_dev(h, z, d_b, ldb, d_x, ldx, nrhs, trans):
+def _refine(h, z, form, n, b, x, trans="N", opt=None):
+    """_refine_call on host arrays: (x,) + its outputs; b and x through _rhs_pair under the form's name -- the plain untransposed call converts them,
+    every other form refuses what it would have to convert"""
     t = _trans_code(trans)
-    nrhs = int(nrhs)
-    berr = np.zeros(max(nrhs, 1)); out = (_lib.XRefine * max(nrhs, 1))()
-    name = "sluamd_pzgsrfs3d_extra_dev" if z else "sluamd_pdgsrfs3d_extra_dev"
-    _lib.check(_lib.entry(name)(h, t, C.c_void_p(d_b), int(ldb), C.c_void_p(d_x), int(ldx), nrhs, _pd(berr), out), name)
-    return (berr[:nrhs],) + _xrefine_out(out, nrhs)
+    who = {"plain": f"pdgsrfs3d(trans={trans!r})", "block": "pdgsrfs3d(block=True)", "gmres": "pdgsrfs3d(method='gmres')", "extra": "pdgsrfs3d(method='extra')"}[form]
+    b, x, _ = _rhs_pair(who, z, b, x, n, strict=form != "plain" or bool(t))
+    return (x,) + _refine_call(h, z, form, True, trans, b, max(b.shape[0], 1), x, max(x.shape[0], 1), b.shape[1], opt)
 
 
 def _residual(h, z, b, x, trans, extra, n):
     """sluamd_[dz]Residual on host arrays: (r, berr[nrhs])"""
     t = _trans_code(trans)
-    dt = np.complex128 if z else np.float64
-    for what, a in (("b", b), ("x", x)):
-        if np.asarray(a).dtype != np.dtype(dt):
-            raise ValueError(f"residual: the handle holds {np.dtype(dt).name} values, {what} is {np.asarray(a).dtype}")
-    if np.shape(b) != np.shape(x) or np.ndim(b) not in (1, 2) or (n is not None and np.shape(b)[0] != n):
-        raise ValueError(f"residual: b and x must both be ({n},) or ({n}, nrhs), got {np.shape(b)} and {np.shape(x)}")
-    one = np.ndim(b) == 1
-    b = np.asfortranarray(np.asarray(b, dtype=dt).reshape(np.shape(b)[0], -1)); x = np.asfortranarray(np.asarray(x, dtype=dt).reshape(b.shape))
+    b, x, one = _rhs_pair("residual", z, b, x, n)
     nrhs = b.shape[1]
     r = np.zeros_like(b, order="F"); berr = np.zeros(max(nrhs, 1))
     name = "sluamd_zResidual" if z else "sluamd_dResidual"
@@ -803,17 +732,15 @@ def _equilibrate(h, z, n, rowptr, colind, nzval, perm_c, with_rc=None):
     pc = np.ascontiguousarray(perm_c, dtype=np.int32)
     v = np.ascontiguousarray(nzval, dtype=np.complex128 if z else np.float64)
     e = _lib.Equil()
+    given = ()
     if with_rc is not None:
         r, c = (None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in with_rc)
         for what, a in (("r", r), ("c", c)):
             if a is not None and a.shape != (int(n),):
                 raise ValueError(f"equilibrate_with: {what} must have shape ({int(n)},), got {a.shape}")
-        name = "sluamd_zEquilibrateWith" if z else "sluamd_dEquilibrateWith"
-        _lib.check(_lib.entry(name)(h, int(n), _pi(rp), _pi(ci), v.ctypes.data_as(C.c_void_p), _pi(pc), None if r is None else _pd(r),
-                                    None if c is None else _pd(c), C.byref(e)), name)
-        return dict(equed=EQUED[e.equed], info=int(e.info), rowcnd=float(e.rowcnd), colcnd=float(e.colcnd), amax=float(e.amax), anorm=float(e.anorm))
-    name = "sluamd_zEquilibrate" if z else "sluamd_dEquilibrate"
-    _lib.check(_lib.entry(name)(h, int(n), _pi(rp), _pi(ci), v.ctypes.data_as(C.c_void_p), _pi(pc), C.byref(e)), name)
+        given = (None if r is None else _pd(r), None if c is None else _pd(c))
+    name = ("sluamd_zEquilibrate" if z else "sluamd_dEquilibrate") + ("With" if given else "")
+    _lib.check(_lib.entry(name)(h, int(n), _pi(rp), _pi(ci), v.ctypes.data_as(C.c_void_p), _pi(pc), *given, C.byref(e)), name)
     return dict(equed=EQUED[e.equed], info=int(e.info), rowcnd=float(e.rowcnd), colcnd=float(e.colcnd), amax=float(e.amax), anorm=float(e.anorm))
 
 

@@ -226,13 +226,11 @@ class GridHandle:
         trans = "T" / "C": the system A^T x = b / A^H x = b of the attached matrix (sluamd_p[dz]gsrfs3d_trans; after plan_transposed()), with LUHandle.pdgsrfs3d's argument checks.
         block=True: the blocked form (sluamd_p[dz]gsrfs3d_block), steps = every column's own count [nrhs].
         method: "plain" only -- the GMRES and the extra-precise refinement (LUHandle.pdgsrfs3d(method="gmres" / "extra")) do not run on grids (ValueError)."""
-        from .driver import _gsrfs3d, _gsrfs3d_block
+        from .driver import _refine
         if method != "plain":
             raise ValueError(f"GridHandle.pdgsrfs3d(method={method!r}): grids refine with method='plain'; the extra-precise and the GMRES refinement need a "
                              "1 x 1 x 1 LUHandle")
-        if block:
-            return _gsrfs3d_block(self._h, self.z, b, x, trans, self.n)
-        return _gsrfs3d(self._h, self.z, b, x, trans, self.n)
+        return _refine(self._h, self.z, "block" if block else "plain", self.n, b, x, trans)
 
     pzgsrfs3d = pdgsrfs3d
 
