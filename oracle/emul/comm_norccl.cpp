@@ -42,6 +42,11 @@ struct EmulStreamComm : Comm {
     {
         // one group: every send is published first, then the receives wait for their messages, then the sends wait to be taken --
         // two ranks that send to each other in the same group cannot block each other (ncclGroupStart / ncclGroupEnd)
+        if (emul_trace_on()) {     // issue-order trace: the group as the driver put it together, peers and lengths
+            std::string g;
+            for (auto &o : ops) g += std::string(o.is_recv ? " recv " : " send ") + std::to_string(o.peer) + ":" + std::to_string(o.bytes);
+            emul_trace(s, "exchange%s", g.c_str());
+        }
         std::vector<std::shared_ptr<SMsg>> mine;
         auto world = w;
         const int P = w->size, self = me;

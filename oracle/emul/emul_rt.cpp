@@ -15,6 +15,7 @@
 // being waited for; the work units inside one launch (Schur tiles, update units) run in a shuffled order.  A missing event wait or a host read without synchronisation in the drivers (look-ahead schedule of
 // pdgstrf3d, panel exchanges, sweeps) becomes a wrong result under one of these orders -- tests/test_stream_order.py.
 #include <atomic>
+#include <cstdarg>
 #include <cstdio>
 #include <deque>
 #include <map>
@@ -22,6 +23,7 @@
 #include <memory>
 #include <mutex>
 #include <random>
+#include <string>
 #include <thread>
 #include <vector>
 #include "sluamd_rt.h"
@@ -156,7 +158,44 @@ emul_stream_s *null_stream()      // the calling thread's legacy default stream 
     if (!t_null) { t_null = new emul_stream_s(); t_null->owner = my_tid(); g_streams.push_back(t_null); }
     return t_null;
 }
+
+// ---- issue-order trace (per thread: the ranks of a thread grid issue side by side) ----
+thread_local bool t_trace = false;
+thread_local std::string t_trace_text;
+thread_local std::map<const void *, int> t_stream_names, t_event_names;
+std::string trace_name(std::map<const void *, int> &names, char kind, const void *p)
+{
+    auto it = names.find(p);
+    if (it == names.end()) it = names.emplace(p, (int) names.size()).first;
+    return kind + std::to_string(it->second);
+}
+std::string stream_name(hipStream_t s) { return trace_name(t_stream_names, 's', s); }     // (the null stream is a name like any other)
+std::string event_name(hipEvent_t e) { return trace_name(t_event_names, 'e', e); }
 }  // namespace
+
+bool emul_trace_on() { return t_trace; }
+void emul_trace(hipStream_t s, const char *fmt, ...)
+{
+    if (!t_trace) return;
+    va_list ap, ap2;
+    va_start(ap, fmt);
+    va_copy(ap2, ap);
+    std::string line((size_t) std::vsnprintf(nullptr, 0, fmt, ap) + 1, '\0');
+    va_end(ap);
+    std::vsnprintf(&line[0], line.size(), fmt, ap2);
+    va_end(ap2);
+    line.pop_back();
+    t_trace_text += line;
+    t_trace_text += " @" + stream_name(s) + "\n";
+}
+// on != 0: start a new trace of the calling thread (text and names start over); 0: stop, the text stays for the dump
+extern "C" void sluamd_emul_trace(int on)
+{
+    t_trace = on != 0;
+    if (t_trace) { t_trace_text.clear(); t_stream_names.clear(); t_event_names.clear(); }
+}
+// the calling thread's trace; the pointer holds until that thread's next trace call
+extern "C" const char *sluamd_emul_trace_dump() { return t_trace_text.c_str(); }
 
 void emul_enqueue(hipStream_t s, std::function<void()> f)
 {
@@ -304,6 +343,7 @@ hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hip
 }
 hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t st)
 {
+    emul_trace(st, "hipMemsetAsync v=%d bytes=%zu", v, n);
     if (n) emul_enqueue(st, [d, v, n] { std::memset(d, v, n); });
     return hipSuccess;
 }
@@ -322,6 +362,7 @@ hipError_t hipStreamDestroy(hipStream_t s) { return hipStreamSynchronize(s); }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned)
 {
     Guard lk;
+    if (t_trace) emul_trace(s, "hipStreamWaitEvent %s", event_name(e).c_str());
     emul_stream_s *st = s ? s : null_stream();
     if (g_mode == 0 || !e->st || e->st == st || e->st->done >= e->seq) return hipSuccess;   // never recorded / same stream / already complete
     emul_op o; o.wait_on = e->st; o.wait_seq = e->seq;
@@ -332,6 +373,7 @@ hipError_t hipEventCreate(hipEvent_t *e) { *e = new emul_event_s(); return hipSu
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
 {
     Guard lk;
+    if (t_trace) emul_trace(s, "hipEventRecord %s", event_name(e).c_str());
     auto tp = e->t;
     if (g_mode == 0) { *tp = std::chrono::steady_clock::now(); e->st = nullptr; return hipSuccess; }
     emul_stream_s *st = s ? s : null_stream();

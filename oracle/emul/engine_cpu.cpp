@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 #include <vector>
 #include "sluamd_internal.h"
 
@@ -726,35 +727,52 @@ void rows_copy(hipStream_t, double *v, int64_t ldv, int nrhs, const int *idx, in
 
 int setup() { return 0; }
 
+// Issue-order trace (emul_rt.cpp): every entry point the factorisation drivers call logs its name, the scalar arguments that decide the launch, which of its
+// optional tables are absent, and panel_site as the driver left it -- before any early return, so that a launch the restatement skips is still on record
+static std::string site()
+{
+    char b[64];
+    std::snprintf(b, sizeof(b), "site=%d,%d,%d,%d", panel_site.level, panel_site.nn, panel_site.part, panel_site.bulk);
+    return b;
+}
+#define TRACE(s, ...) do { if (emul_trace_on()) emul_trace(s, __VA_ARGS__); } while (0)
+
 void diag_lu(hipStream_t s, const DevTables &T, const int *nodes, int nn, int max_nsupc, int flags, double thresh, int *info)
 {
+    TRACE(s, "diag_lu nn=%d max_nsupc=%d flags=%d thresh=%g %s", nn, max_nsupc, flags, thresh, site().c_str());
     emul_enqueue(s, [=] { impl::diag_lu(s, T, nodes, nn, max_nsupc, flags, thresh, info); });
 }
 
 void diag_inv(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int ntask)
 {
+    TRACE(s, "diag_inv nn=%d ntask=%d %s", nn, ntask, site().c_str());
     emul_enqueue(s, [=] { impl::diag_inv(s, T, nodes, prefix, nn, ntask); });
 }
 
 void panel_trsm(hipStream_t s, const DevTables &T, const int *nodes, const int *lprefix, const int *uprefix, int nn, int nl, int nu, int rs, int max_nsupc, const int2 *units)
 {
+    TRACE(s, "panel_trsm nn=%d nl=%d nu=%d rs=%d max_nsupc=%d nodes=%d units=%d lds_strip=%d %s", nn, nl, nu, rs, max_nsupc, nodes != nullptr, units != nullptr, (int) trsm_lds_strip, site().c_str());
     emul_enqueue(s, [=] { impl::panel_trsm(s, T, nodes, lprefix, uprefix, nn, nl, nu, rs, max_nsupc, units); });
 }
 
 void panel_gemm(hipStream_t s, const DevTables &T, const int *nodes, const int *lprefix, const int *uprefix, int nn, int nl, int nu, int max_nsupc, const int2 *units)
 {
+    TRACE(s, "panel_gemm nn=%d nl=%d nu=%d max_nsupc=%d nodes=%d units=%d %s", nn, nl, nu, max_nsupc, nodes != nullptr, units != nullptr, site().c_str());
     emul_enqueue(s, [=] { impl::panel_gemm(s, T, nodes, lprefix, uprefix, nn, nl, nu, max_nsupc, units); });
 }
 
 void schur(hipStream_t s, int cfg, const DevTables &T, const int *nodes, const int *prefix, int nn, int id_base, int ntiles, int *info, const int4 *ulist, int prio,
-           const int *, int mmode, int /* ksplit: shares of K per tile on the device; the restatement computes a tile once */, const int *, int /* XCD ranges: a device mapping */)
+           const int *tmaps, int mmode, int ksplit /* shares of K per tile on the device; the restatement computes a tile once */, const int *xoff, int xmax /* XCD ranges: a device mapping */)
 {
+    TRACE(s, "schur cfg=%d nn=%d id_base=%d ntiles=%d prio=%d mmode=%d ksplit=%d xmax=%d nodes=%d ulist=%d tmaps=%d xoff=%d", cfg, nn, id_base, ntiles, prio, mmode, ksplit, xmax,
+          nodes != nullptr, ulist != nullptr, tmaps != nullptr, xoff != nullptr);
     if (mmode == 1) return;     // build pass of the per-tile records: the restatement reads the tables every time
     emul_enqueue(s, [=] { impl::schur(s, cfg, T, nodes, prefix, nn, id_base, ntiles, info, ulist, prio); });
 }
 
 void full_inv(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, int nn, int nwork, int max_nsupc)
 {
+    TRACE(s, "full_inv nn=%d nwork=%d max_nsupc=%d %s", nn, nwork, max_nsupc, site().c_str());
     emul_enqueue(s, [=] { impl::full_inv(s, T, nodes, prefix, nn, nwork, max_nsupc); });
 }
 
@@ -819,12 +837,14 @@ void axpy(hipStream_t s, int64_t n, double a, const double *x, double *y)
 
 void add_atomic(hipStream_t s, int64_t n, const double *x, double *y)
 {
+    TRACE(s, "add_atomic n=%lld", (long long) n);
     if (n <= 0) return;
     emul_enqueue(s, [=] { impl::add_atomic(s, n, x, y); });
 }
 
 void pack_diag(hipStream_t s, const DevTables &T, const int *nodes, const int *prefix, const int64_t *off, int nn, int nwork, double *stage, int vs)
 {
+    TRACE(s, "pack_diag nn=%d nwork=%d vs=%d %s", nn, nwork, vs, site().c_str());
     emul_enqueue(s, [=] { impl::pack_diag(s, T, nodes, prefix, off, nn, nwork, stage, vs); });
 }
 
@@ -938,17 +958,21 @@ static void zsolve_diag(bool lower, const DevTables &T, const int *nodes, int nn
 }
 }  // namespace impl
 
-void zdiag_lu(hipStream_t s, const DevTables &T, const int *nodes, int nn, int, int replace_tiny, double thresh, int *info)
+void zdiag_lu(hipStream_t s, const DevTables &T, const int *nodes, int nn, int max_nsupc, int replace_tiny, double thresh, int *info)
 {
+    TRACE(s, "zdiag_lu nn=%d max_nsupc=%d replace_tiny=%d thresh=%g %s", nn, max_nsupc, replace_tiny, thresh, site().c_str());
     emul_enqueue(s, [=] { impl::zdiag_lu(T, nodes, nn, replace_tiny, thresh, info); });
 }
-void zpanel_trsm(hipStream_t s, const DevTables &T, const int *nodes, const int *, const int *, int nn, int, int, int)
+void zpanel_trsm(hipStream_t s, const DevTables &T, const int *nodes, const int *, const int *, int nn, int nl, int nu, int max_nsupc)
 {
+    TRACE(s, "zpanel_trsm nn=%d nl=%d nu=%d max_nsupc=%d %s", nn, nl, nu, max_nsupc, site().c_str());
     emul_enqueue(s, [=] { impl::zpanel_trsm(T, nodes, nn); });
 }
-void zschur(hipStream_t s, int, const DevTables &T, const int *nodes, const int *prefix, int nn, int id_base, int ntiles, int *info, const int4 *ulist, int,
-            const int *, int mmode, const int *, int)
+void zschur(hipStream_t s, int cfg, const DevTables &T, const int *nodes, const int *prefix, int nn, int id_base, int ntiles, int *info, const int4 *ulist, int prio,
+            const int *tmaps, int mmode, const int *xoff, int xmax)
 {
+    TRACE(s, "zschur cfg=%d nn=%d id_base=%d ntiles=%d prio=%d mmode=%d xmax=%d nodes=%d ulist=%d tmaps=%d xoff=%d", cfg, nn, id_base, ntiles, prio, mmode, xmax,
+          nodes != nullptr, ulist != nullptr, tmaps != nullptr, xoff != nullptr);
     if (ntiles <= 0 || mmode == 1) return;
     emul_enqueue(s, [=] { impl::schur_t<impl::zc>(T, nodes, prefix, nn, id_base, ntiles, info, ulist); });
 }
@@ -996,6 +1020,7 @@ void zsweep_fused(hipStream_t s, bool lower, const DevTables &T, const int *node
 // merged chain groups: the same gather and products as the device kernels, element by element
 void grp_gather(hipStream_t s, const DevTables &T, const GrpDesc *gd, double *scr)
 {
+    TRACE(s, "grp_gather");
     emul_enqueue(s, [=] {
         const GrpDesc g = *gd;
         const int nG = g.nG;
@@ -1038,6 +1063,7 @@ void grp_gather(hipStream_t s, const DevTables &T, const GrpDesc *gd, double *sc
 }
 void gemm_batched(hipStream_t s, const DevTables &T, const GemmDesc *descs, const int4 *tiles, int ntiles, double *scr)
 {
+    TRACE(s, "gemm_batched ntiles=%d", ntiles);
     if (ntiles <= 0) return;
     emul_enqueue(s, [=] {
         for (int t = 0; t < ntiles; ++t) {

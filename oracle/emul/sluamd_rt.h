@@ -32,6 +32,12 @@ void emul_enqueue(hipStream_t s, std::function<void()> f);
 void emul_enqueue_when(hipStream_t s, std::function<bool()> ready, std::function<void()> f);
 // adversarial modes: a permutation seed for the work units INSIDE one launch (0 in immediate mode = issue order)
 unsigned emul_launch_seed();
+// Issue-order trace of the CALLING thread (sluamd_emul_trace / sluamd_emul_trace_dump, emul_rt.cpp): one line per call in the order the
+// host issued it, whatever order the scheduler runs the work in.  The runtime logs its own event records, event waits and asynchronous
+// memsets; the CPU engine and the stream-ordered transport log theirs through emul_trace, which appends " @<stream>" to the line.
+// Streams and events are named by their first appearance in the trace (s0, s1, ... / e0, e1, ...); no address ever enters a line.
+bool emul_trace_on();
+void emul_trace(hipStream_t s, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 hipError_t hipMalloc(void **p, size_t n);
 hipError_t hipFree(void *p);

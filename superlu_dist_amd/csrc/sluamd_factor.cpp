@@ -46,11 +46,11 @@ static int exchange(Handle *H, const std::vector<XMsg> &sends, const std::vector
     return c->end(s);
 }
 
-// One elimination forest, level by level.  Serial mode (profiling / deterministic): everything on one stream.
-// Look-ahead mode (default): the Schur update of level l is split into the tiles that feed level l+1's panels
-// ("urgent", explicit list) and the rest; the panel kernels of level l+1 -- and on an XY layer their two exchange
-// phases -- run on a high-priority stream as soon as the urgent tiles are done and overlap with the rest: the GPU form of
-// the reference's look-ahead pipeline (dsparseTreeFactor_ASYNC, dtreeFactorization.c:381-706, num_lookaheads).
+// One elimination forest, level by level (run_factor_sched).  Serial program (profiling / deterministic / SLUAMD_NO_LOOKAHEAD): everything on one
+// stream (factor_serial).  Look-ahead program (default, factor_lookahead): the Schur update of level l is split into the tiles that feed level l+1's
+// panels ("urgent", explicit list) and the rest; the panel kernels of level l+1 -- and on an XY layer their two exchange phases -- run on a
+// high-priority stream as soon as the urgent tiles are done and overlap with the rest: the GPU form of the reference's look-ahead pipeline
+// (dsparseTreeFactor_ASYNC, dtreeFactorization.c:381-706, num_lookaheads).  Both programs are written with the steps of FactorRun.
 static hipEvent_t red_wait_event(const Handle *H, int64_t lend, int64_t uend);     // pipelined Z reduction, below
 
 // Inverse of the block triangle of one merged chain group (Handle::groups) into its pair of T.inv: zero fill, gather (diagonal blocks = the members' Linv / Uinv,
@@ -61,79 +61,105 @@ static void group_inverse(Handle *H, int gi, hipStream_t st)
     hipMemsetAsync(H->T.inv + G.ginv, 0, sizeof(double) * (size_t) 2 * G.nG * G.nG, st);
     hipMemsetAsync(H->d_gscr.p, 0, sizeof(double) * (size_t) (2 * GRP_SCR), st);       // LG | UG (the sums TL / TU are written before they are read)
     eng::grp_gather(st, H->T, H->d_grpdesc + gi, H->d_gscr.p);
+    int launches = 1;   // the gather
     for (int q = 0; q + 1 < 7; ++q)
-        if (G.tile_off[q + 1] > G.tile_off[q]) { eng::gemm_batched(st, H->T, H->d_gemmdesc, H->d_gemmtiles + G.tile_off[q], G.tile_off[q + 1] - G.tile_off[q], H->d_gscr.p); H->st.num_launches++; }
-    H->st.num_launches += 1;
+        if (G.tile_off[q + 1] > G.tile_off[q]) { eng::gemm_batched(st, H->T, H->d_gemmdesc, H->d_gemmtiles + G.tile_off[q], G.tile_off[q + 1] - G.tile_off[q], H->d_gscr.p); ++launches; }
+    H->st.num_launches += launches;
 }
 
-static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
+// One Schur launch of a tile-size group (big: 128 x 128 tiles) -- the build of the per-tile records and every update come through here: the precision picks
+// the kernel and its cfg (complex16: k_schur on the real embedding).  The records have the layout of cfg 0 / 2 whatever the 4-wave switch says
+static int tile_rec_ints(const Handle *H, bool big) { return eng::schur_rec_ints(big ? 0 : 2, H->z); }
+static void schur_launch(Handle *H, hipStream_t st, bool big, const int *nodes, const int *prefix, int nn, int id_base, int ntile, const int4 *ulist, int prio,
+                         const int *tmaps, int mmode, int ksplit = 1, const int *xoff = nullptr, int xmax = 0)
 {
-    const DevTables &T = H->T;
-    const bool xy = H->grid.Pr * H->grid.Pc > 1;
-    const bool lookahead = !H->profile && !H->opt.deterministic && !H->env.no_lookahead;
-    const bool gemm_panels = !H->env.trsm_panels && !H->z;   // XY layers: the peers of a diagonal block invert the copy they receive (full_inv on SNF_HAS_DIAG)
-    hipStream_t s = H->stream, ps = lookahead ? H->pstream : H->stream;
-    int rc_x = 0;
+    if (H->z) eng::zschur(st, big ? 0 : 1, H->T, nodes, prefix, nn, id_base, ntile, H->d_info.p, ulist, prio, tmaps, mmode, xoff, xmax);
+    else eng::schur(st, big ? (H->env.schur_4waves ? 1 : 0) : 2, H->T, nodes, prefix, nn, id_base, ntile, H->d_info.p, ulist, prio, tmaps, mmode, ksplit, xoff, xmax);
+}
+
+// per-tile records of the list schedules (k_schur mmode 1 / 2): built once per schedule, on its first factorisation
+static void ensure_tile_records(Handle *H, LevelSched &S)
+{
+    if (S.maps_state != 0) return;
+    S.maps_state = -1;
+    if (H->env.no_tile_maps || H->opt.deterministic || S.ulist.h.empty()) return;
+    S.m_off.assign(2 * S.nlevels + 1, 0);
+    for (int l = 0; l < S.nlevels; ++l)
+        for (int g = 0; g < 2; ++g) {
+            const int64_t cnt = S.u_off[(2 * l + g) * 4 + 4] - S.u_off[(2 * l + g) * 4];
+            S.m_off[2 * l + g + 1] = S.m_off[2 * l + g] + cnt * tile_rec_ints(H, g == 0);
+        }
+    const size_t bytes = sizeof(int) * (size_t) S.m_off[2 * S.nlevels];
+    size_t fr = 0, tot = 0;
+    hipMemGetInfo(&fr, &tot);
+    // the records are an accelerator, not a requirement: leave a tenth of the device free.  (Chunks the arena pool holds for later handles count as free:
+    // they go back to the driver when the records need the room.)
+    const size_t cached = devpool_cached_bytes(H->device);
+    if (bytes > 0 && bytes + tot / 10 >= fr && bytes + tot / 10 < fr + cached) { devpool_trim(H->device); hipMemGetInfo(&fr, &tot); }
+    // (the one caller that ignores dev_alloc's verdict: without the records the tiles chase their tables)
+    if (bytes > 0 && bytes + tot / 10 < fr && S.d_tmaps.alloc(S.m_off[2 * S.nlevels], H->device, "the tile records of the Schur update") != 0) set_error("");
+    if (!S.d_tmaps) return;
+    for (int l = 0; l < S.nlevels; ++l)
+        for (int g = 0; g < 2; ++g) {
+            const int u0 = S.u_off[(2 * l + g) * 4], nu = S.u_off[(2 * l + g) * 4 + 4] - u0;
+            if (nu) schur_launch(H, H->stream, g == 0, nullptr, nullptr, 0, 0, nu, S.ulist.d + u0, 0, S.d_tmaps.p + S.m_off[2 * l + g], 1);
+        }
+    S.maps_state = 1;
+    H->st.bytes_device += (int64_t) bytes;
+}
+
+// One factorisation of one forest: what both stream programs share -- the handle and its schedule, the switches, the streams, and the steps of a level
+// as member functions.  panel(l) comes in two parts: panel_diag needs only the diagonal blocks of level l to be up to date, panel_solve the whole panels.
+struct FactorRun {
+    Handle *const H;
+    LevelSched &S;
+    const DevTables &T;
+    const double thresh;
+    const bool xy, lookahead;
+    const bool gemm_panels;     // XY layers: the peers of a diagonal block invert the copy they receive (full_inv on SNF_HAS_DIAG)
     // Tail of the panel chain (1 x 1 layers): on the last `trsm_tail` single-supernode levels -- the top separator, where the trailing
     // update is shorter than the chain diag LU -> Linv / Uinv -> panel GEMM -> urgent tiles -- the panel solves run as blocked
     // substitutions on the 32 x 32 inverses the diagonal kernel leaves behind (k_panel_trsm), so that the full inverses (which the
     // triangular solves still want) leave the chain: they are computed beside it on the bulk stream
-    const int trsm_tail = (gemm_panels && !xy) ? H->env.trsm_tail : 0;
-    eng::trsm_lds_strip = H->env.trsm_lds_strip;   // (thread-local, like panel_site: read by eng::panel_trsm on this thread)
-    auto tail_level = [&](int l) { return trsm_tail > 0 && l >= S.nlevels - trsm_tail && S.lvl_off[l + 1] - S.lvl_off[l] == 1; };
-    auto deferred_inv = [&](hipStream_t st, int l) {
-        const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
-        eng::panel_site = {l, nn, -1, 1};
-        eng::full_inv(st, T, S.nodes.d + n0, S.finv_prefix.d + po, nn, S.finv_prefix.h[po + nn], S.max_nsupc[l]);
-        H->st.num_launches++;
-    };
-    int cur_level = 0, cur_pass = 0;
-    // per-tile records of the list schedules (k_schur mmode 1 / 2): built once per schedule, on its first factorisation
-    if (S.maps_state == 0) {
-        S.maps_state = -1;
-        if (!H->env.no_tile_maps && !H->opt.deterministic && !S.ulist.h.empty()) {
-            S.m_off.assign(2 * S.nlevels + 1, 0);
-            for (int l = 0; l < S.nlevels; ++l)
-                for (int g = 0; g < 2; ++g) {
-                    const int64_t cnt = S.u_off[(2 * l + g) * 4 + 4] - S.u_off[(2 * l + g) * 4];
-                    S.m_off[2 * l + g + 1] = S.m_off[2 * l + g] + cnt * eng::schur_rec_ints(g == 0 ? 0 : 2, H->z);
-                }
-            const size_t bytes = sizeof(int) * (size_t) S.m_off[2 * S.nlevels];
-            size_t fr = 0, tot = 0;
-            hipMemGetInfo(&fr, &tot);
-            // the records are an accelerator, not a requirement: leave a tenth of the device free.  (Chunks the arena pool holds for later handles count as free:
-            // they go back to the driver when the records need the room.)
-            const size_t cached = devpool_cached_bytes(H->device);
-            if (bytes > 0 && bytes + tot / 10 >= fr && bytes + tot / 10 < fr + cached) { devpool_trim(H->device); hipMemGetInfo(&fr, &tot); }
-            // (the one caller that ignores dev_alloc's verdict: without the records the tiles chase their tables)
-            if (bytes > 0 && bytes + tot / 10 < fr && S.d_tmaps.alloc(S.m_off[2 * S.nlevels], H->device, "the tile records of the Schur update") != 0) set_error("");
-            if (S.d_tmaps) {
-                for (int l = 0; l < S.nlevels; ++l)
-                    for (int g = 0; g < 2; ++g) {
-                        const int u0 = S.u_off[(2 * l + g) * 4], nu = S.u_off[(2 * l + g) * 4 + 4] - u0;
-                        if (!nu) continue;
-                        if (H->z) eng::zschur(s, g == 0 ? 0 : 1, T, nullptr, nullptr, 0, 0, nu, H->d_info.p, S.ulist.d + u0, 0, S.d_tmaps.p + S.m_off[2 * l + g], 1);
-                        else eng::schur(s, g == 0 ? (H->env.schur_4waves ? 1 : 0) : 2, T, nullptr, nullptr, 0, 0, nu, H->d_info.p, S.ulist.d + u0, 0, S.d_tmaps.p + S.m_off[2 * l + g], 1);
-                    }
-                S.maps_state = 1;
-                H->st.bytes_device += (int64_t) bytes;
-            }
-        }
+    const int trsm_tail;
+    const bool has_groups;      // merged chain groups of the sweeps (Handle::lvl_groups) belong to the schedule of the first forest
+    // the stream program's streams (factor_lookahead); the serial program runs everything on s
+    const hipStream_t s, ps, us, u2s;
+    int rc_x = 0;               // first failure of an XY exchange: later exchanges are skipped, the level loop returns it
+    int cur_level = 0, cur_pass = 0;         // (profile dump) where the next Schur launch stands
+    std::vector<int64_t> lv_lend, lv_uend;   // pipelined Z reduction: the own L / U slots of DAG level l end at these arena offsets (own slots are laid out level by level)
+
+    FactorRun(Handle *H_, LevelSched &S_, double thresh_)
+        : H(H_), S(S_), T(H_->T), thresh(thresh_), xy(H_->grid.Pr * H_->grid.Pc > 1), lookahead(!H_->profile && !H_->opt.deterministic && !H_->env.no_lookahead),
+          gemm_panels(!H_->env.trsm_panels && !H_->z), trsm_tail((gemm_panels && !xy) ? H_->env.trsm_tail : 0), has_groups(&S_ == &H_->sched[0] && !H_->lvl_groups.empty()),
+          s(H_->stream), ps(lookahead ? H_->pstream : H_->stream), us(lookahead ? H_->ustream : H_->stream), u2s(lookahead ? H_->u2stream : H_->stream)
+    {
+        eng::trsm_lds_strip = H->env.trsm_lds_strip;   // (thread-local, like panel_site: read by eng::panel_trsm on this thread)
     }
-    auto schur = [&](hipStream_t st, bool big, int ntile, const int *nodes, const int *prefix, int nn, int id_base,
-                     const int4 *ulist, int prio = 0, const int *tmaps = nullptr, int ksplit = 1, const int *xoff = nullptr, int xmax = 0) {
-        if (H->profile && H->env.profile_dump) H->schur_rec.push_back({cur_level, cur_pass, big ? 1 : 0, ntile, S.max_nsupc[cur_level]});
-        if (H->profile) { if (H->ev_schur_big.size() <= H->ev_schur_used) H->ev_schur_big.resize(H->ev_schur_used + 1); H->ev_schur_big[H->ev_schur_used] = big ? 1 : 0; }
-        ev_begin(H, H->ev_schur, H->ev_schur_used, st);
-        if (H->z) eng::zschur(st, big ? 0 : 1, T, nodes, prefix, nn, id_base, ntile, H->d_info.p, ulist, prio, tmaps, tmaps ? 2 : 0, xoff, xmax);     // complex16: k_schur on the real embedding
-        else eng::schur(st, big ? (H->env.schur_4waves ? 1 : 0) : 2, T, nodes, prefix, nn, id_base, ntile, H->d_info.p, ulist, prio, tmaps, tmaps ? 2 : 0, ksplit, xoff, xmax);
-        ev_end(H, H->ev_schur, H->ev_schur_used, st);
-        H->st.num_launches++; H->st.schur_launches++; H->st.schur_tiles += ntile;
-    };
-    // panel(l) in two parts: A needs only the diagonal blocks of level l to be up to date, B the whole panels
-    // pipelined Z reduction: the own L / U slots of DAG level l end at these arena offsets (own slots are laid out level by level)
-    std::vector<int64_t> lv_lend, lv_uend;
-    if (!H->red_events.empty()) {
+
+    bool tail_level(int l) const { return trsm_tail > 0 && l >= S.nlevels - trsm_tail && S.lvl_off[l + 1] - S.lvl_off[l] == 1; }
+    // Split panel solves (LevelSched::ps_units, look-ahead schedule only): part 0 = the strips / chunks the level's part-0 tiles read, on the panel stream;
+    // part 1 = all the others, on the urgent-tile stream beside the next level's diagonal LU.  The GPU form of what the reference's look-ahead window does
+    // with its panel factorisations (dsparseTreeFactor_ASYNC, dtreeFactorization.c:381-470: the panels of the look-ahead supernodes first).
+    bool level_split(int l) const { return lookahead && !S.ps_off.empty() && S.ps_off[4 * l + 4] > S.ps_off[4 * l]; }
+
+    hipEvent_t wait_on(hipStream_t waiter, hipStream_t on)   // waiter continues after everything queued on `on`
+    {
+        hipEvent_t e = next_event(H);
+        hipEventRecord(e, on); hipStreamWaitEvent(waiter, e, 0);
+        return e;
+    }
+    // one timed phase of the XY panel exchange on stream st
+    void xchg(hipStream_t st, const std::vector<XMsg> &sends, const std::vector<XMsg> &recvs)
+    {
+        ev_begin(H, H->ev_xchg, H->ev_xchg_used, st);
+        if (!rc_x) rc_x = exchange(H, sends, recvs, st);
+        ev_end(H, H->ev_xchg, H->ev_xchg_used, st);
+    }
+    // pipelined Z reduction: where the own slots of every level end (lv_lend / lv_uend)
+    void reduction_offsets()
+    {
+        if (H->red_events.empty()) { if (H->red_all) hipStreamWaitEvent(s, H->red_all, 0); return; }   // nothing chunk-wise pending: whatever an earlier reduction still adds must be in
         lv_lend.assign(S.nlevels, -1); lv_uend.assign(S.nlevels, -1);
         int64_t le = -1, ue = -1;
         for (int l = 0; l < S.nlevels; ++l) {
@@ -145,49 +171,59 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
             lv_lend[l] = le; lv_uend[l] = ue;
         }
     }
-    else if (H->red_all) hipStreamWaitEvent(s, H->red_all, 0);     // nothing chunk-wise pending: whatever an earlier reduction still adds must be in
-    auto panelA = [&](int l) {
+
+    // Diagonal blocks of level l on the panel stream.  The precision decides the kernel, the value stride and offset of the packed blocks, whether the
+    // inverses follow, and the launch count -- nothing else.  double: Local_Dgstrf2 (+ dinv of the owned blocks), dDiagFactIBCast (dtrfCommWrapper.c:32-118:
+    // diagonal blocks down the process column and along the process row).  complex16: Local_Zgstrf2 (pzgstrf2.c), zDiagFactIBCast (ztrfCommWrapper.c); the
+    // complex panel solves substitute on the factored block: no inverses
+    void panel_diag(int l)
+    {
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
         const int *nodes = S.nodes.d + n0;
-        const int mx = S.max_nsupc[l];
+        const int mx = S.max_nsupc[l], vs = H->z ? 2 : 1;
         eng::panel_site = {l, nn, -1, 0};
         if (!lv_lend.empty()) {   // the panels of this level must hold the partner layer's contributions before they are factored
             hipEvent_t e = red_wait_event(H, lv_lend[l], lv_uend[l]);
             if (e) hipStreamWaitEvent(ps, e, 0);
         }
         ev_begin(H, H->ev_panel, H->ev_panel_used, ps);
-        if (H->z) {   // Local_Zgstrf2 (pzgstrf2.c); the complex panel solves substitute on the factored block: no inverses
-            eng::zdiag_lu(ps, T, nodes, nn, mx, H->opt.replace_tiny_pivot, thresh, H->d_info.p);
-            if (xy) {   // zDiagFactIBCast (ztrfCommWrapper.c): packed diagonal blocks down the process column and along the process row
-                eng::pack_diag(ps, T, nodes, S.dg_prefix.d + po, S.dg_off.d + po, nn, S.dg_prefix.h[po + nn], H->d_val.p + 2 * S.dg_stage_off[l], 2);
-                ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
-                if (!rc_x) rc_x = exchange(H, S.x_diag_send[l], S.x_diag_recv[l], ps);
-                ev_end(H, H->ev_xchg, H->ev_xchg_used, ps);
-            }
-            ev_end(H, H->ev_panel, H->ev_panel_used, ps);
-            H->st.num_launches += 1 + (xy ? 1 : 0);
-            return;
+        if (H->z) eng::zdiag_lu(ps, T, nodes, nn, mx, H->opt.replace_tiny_pivot, thresh, H->d_info.p);
+        else {
+            // bit 2: the single-supernode levels at the top of the tree get the diagonal kernel built for the whole register file (no scratch)
+            const int big_regs = (H->env.diag_tail > 0 && nn == 1 && l >= S.nlevels - H->env.diag_tail) ? 4 : 0;
+            eng::diag_lu(ps, T, nodes, nn, mx, (H->opt.replace_tiny_pivot ? 1 : 0) | (H->env.diag_v1 ? 2 : 0) | big_regs, thresh, H->d_info.p);
         }
-        // bit 2: the single-supernode levels at the top of the tree get the diagonal kernel built for the whole register file (no scratch)
-        const int big_regs = (H->env.diag_tail > 0 && nn == 1 && l >= S.nlevels - H->env.diag_tail) ? 4 : 0;
-        eng::diag_lu(ps, T, nodes, nn, mx, (H->opt.replace_tiny_pivot ? 1 : 0) | (H->env.diag_v1 ? 2 : 0) | big_regs, thresh, H->d_info.p);   // Local_Dgstrf2 (+ dinv of the owned blocks)
-        if (xy) {   // dDiagFactIBCast (dtrfCommWrapper.c:32-118): diagonal blocks down the process column and along the process row
-            eng::pack_diag(ps, T, nodes, S.dg_prefix.d + po, S.dg_off.d + po, nn, S.dg_prefix.h[po + nn], H->d_val.p + S.dg_stage_off[l]);
-            ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
-            if (!rc_x) rc_x = exchange(H, S.x_diag_send[l], S.x_diag_recv[l], ps);
-            ev_end(H, H->ev_xchg, H->ev_xchg_used, ps);
-            eng::diag_inv(ps, T, nodes, S.inv_prefix.d + po, nn, S.inv_prefix.h[po + nn]);   // column / row peers invert the diagonal blocks they received
+        if (xy) {
+            eng::pack_diag(ps, T, nodes, S.dg_prefix.d + po, S.dg_off.d + po, nn, S.dg_prefix.h[po + nn], H->d_val.p + vs * S.dg_stage_off[l], vs);
+            xchg(ps, S.x_diag_send[l], S.x_diag_recv[l]);
+            if (!H->z) eng::diag_inv(ps, T, nodes, S.inv_prefix.d + po, nn, S.inv_prefix.h[po + nn]);   // column / row peers invert the diagonal blocks they received
         }
         const bool inv_here = gemm_panels && !tail_level(l);
         if (inv_here) eng::full_inv(ps, T, nodes, S.finv_prefix.d + po, nn, S.finv_prefix.h[po + nn], mx);   // Linv / Uinv (the solve uses the owner's too)
         ev_end(H, H->ev_panel, H->ev_panel_used, ps);
-        H->st.num_launches += 1 + (inv_here ? 1 : 0) + (xy ? 2 : 0);
-    };
-    // Split panel solves (LevelSched::ps_units, look-ahead schedule only): part 0 = the strips / chunks the level's part-0 tiles read, on the panel stream;
-    // part 1 = all the others, on the urgent-tile stream beside the next level's diagonal LU.  The GPU form of what the reference's look-ahead window does
-    // with its panel factorisations (dsparseTreeFactor_ASYNC, dtreeFactorization.c:381-470: the panels of the look-ahead supernodes first).
-    auto level_split = [&](int l) { return lookahead && !S.ps_off.empty() && S.ps_off[4 * l + 4] > S.ps_off[4 * l]; };
-    auto panelB_part = [&](hipStream_t st, int l, int part) {
+        H->st.num_launches += 1 + (inv_here ? 1 : 0) + (xy ? (H->z ? 1 : 2) : 0);
+    }
+    // Panel solves of level l on the panel stream and their exchange ([dz]IBcastRecvLPanel / [dz]IBcastRecvUPanel).  The precision decides the kernel and the
+    // prefix tables that count its units.  double: the chain-free GEMM form of dLPanelTrSolve / dUPanelTrSolve, or blocked substitution (tail levels,
+    // SLUAMD_TRSM_PANELS).  complex16: zLPanelTrSolve / zUPanelTrSolve (ztrfCommWrapper.c) on 64-row strips / 64-column chunks
+    void panel_solve(int l)
+    {
+        const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
+        const int *nodes = S.nodes.d + n0;
+        const int mx = S.max_nsupc[l];
+        const PlanTable<int> &lp = H->z ? S.zltr_prefix : S.ltr_prefix, &up = H->z ? S.bwd_prefix : S.utr_prefix;
+        const int nl = lp.h[po + nn], nu = up.h[po + nn];
+        eng::panel_site = {l, nn, -1, 0};
+        ev_begin(H, H->ev_panel, H->ev_panel_used, ps);
+        if (H->z) eng::zpanel_trsm(ps, T, nodes, lp.d + po, up.d + po, nn, nl, nu, mx);
+        else if (gemm_panels && !tail_level(l)) eng::panel_gemm(ps, T, nodes, lp.d + po, up.d + po, nn, nl, nu, mx);
+        else eng::panel_trsm(ps, T, nodes, lp.d + po, up.d + po, nn, nl, nu, trsm_rs(*H, (mx + 31) & ~31), mx);
+        if (xy) xchg(ps, S.x_panel_send[l], S.x_panel_recv[l]);
+        ev_end(H, H->ev_panel, H->ev_panel_used, ps);
+        H->st.num_launches += (nl + nu > 0);
+    }
+    void panel_solve_part(hipStream_t st, int l, int part)   // one part of a split level (level_split)
+    {
         const int mx = S.max_nsupc[l];
         const int o0 = S.ps_off[4 * l + 2 * part], o1 = S.ps_off[4 * l + 2 * part + 1], o2 = S.ps_off[4 * l + 2 * part + 2];
         const int nl = o1 - o0, nu = o2 - o1;
@@ -196,58 +232,39 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
         if (gemm_panels && !tail_level(l)) eng::panel_gemm(st, T, nullptr, nullptr, nullptr, 0, nl, nu, mx, S.ps_units.d + o0);
         else eng::panel_trsm(st, T, nullptr, nullptr, nullptr, 0, nl, nu, 64, mx, S.ps_units.d + o0);
         H->st.num_launches++;
-    };
-    auto panelB = [&](int l) {
+    }
+    void deferred_inv(hipStream_t st, int l)   // the full inverses of a tail level, beside the chain
+    {
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0, po = S.lvl_poff[l];
-        const int *nodes = S.nodes.d + n0;
-        const int mx = S.max_nsupc[l];
-        const int nl = S.ltr_prefix.h[po + nn], nu = S.utr_prefix.h[po + nn];
-        eng::panel_site = {l, nn, -1, 0};
-        ev_begin(H, H->ev_panel, H->ev_panel_used, ps);
-        if (H->z) {   // zLPanelTrSolve / zUPanelTrSolve (ztrfCommWrapper.c): 64-row strips / 64-column chunks
-            const int znl = S.zltr_prefix.h[po + nn], znu = S.bwd_prefix.h[po + nn];
-            eng::zpanel_trsm(ps, T, nodes, S.zltr_prefix.d + po, S.bwd_prefix.d + po, nn, znl, znu, mx);
-            if (xy) {
-                ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
-                if (!rc_x) rc_x = exchange(H, S.x_panel_send[l], S.x_panel_recv[l], ps);   // zIBcastRecvLPanel / zIBcastRecvUPanel
-                ev_end(H, H->ev_xchg, H->ev_xchg_used, ps);
-            }
-            ev_end(H, H->ev_panel, H->ev_panel_used, ps);
-            H->st.num_launches += (znl + znu > 0);
-            return;
-        }
-        if (gemm_panels && !tail_level(l)) eng::panel_gemm(ps, T, nodes, S.ltr_prefix.d + po, S.utr_prefix.d + po, nn, nl, nu, mx);   // chain-free GEMM form of dLPanelTrSolve / dUPanelTrSolve
-        else eng::panel_trsm(ps, T, nodes, S.ltr_prefix.d + po, S.utr_prefix.d + po, nn, nl, nu, trsm_rs(*H, (mx + 31) & ~31), mx);
-        if (xy) {
-            ev_begin(H, H->ev_xchg, H->ev_xchg_used, ps);
-            if (!rc_x) rc_x = exchange(H, S.x_panel_send[l], S.x_panel_recv[l], ps);   // dIBcastRecvLPanel / dIBcastRecvUPanel
-            ev_end(H, H->ev_xchg, H->ev_xchg_used, ps);
-        }
-        ev_end(H, H->ev_panel, H->ev_panel_used, ps);
-        H->st.num_launches += (nl + nu > 0);
-    };
-    // Stream program.  Serial mode: everything in order on one stream.  Look-ahead mode, four streams:
-    //   s   (bulk)     : the bulk of Schur(l), level after level                                        -- never waits for a later panel
-    //   us  (urgent 1) : U1(l) [tiles that feed level-(l+1) panels] minus its diagonal-block tiles, which run on ps in front of diag_lu(l+1)
-    //   u2s (urgent 2) : U2(l) [tiles that feed level-(l+2) panels]
-    //   ps  (panels)   : panel(l+1) = diag LU / inverses after U1's diagonal part, panel solves after all of U1(l)
-    // panel(l+1) needs U1(l), U2(l-1) and the bulk of every level <= l-2: while the bulk of one level runs, the panels of the
-    // next TWO levels and the urgent tiles between them are factored beside it.
-    hipStream_t us = lookahead ? H->ustream : H->stream, u2s = lookahead ? H->u2stream : H->stream;
-    if (lookahead && S.nlevels) {
-        hipEvent_t e = next_event(H);    // the side streams must see everything queued so far on the main stream
-        hipEventRecord(e, s); hipStreamWaitEvent(ps, e, 0); hipStreamWaitEvent(us, e, 0); hipStreamWaitEvent(u2s, e, 0);
+        eng::panel_site = {l, nn, -1, 1};
+        eng::full_inv(st, T, S.nodes.d + n0, S.finv_prefix.d + po, nn, S.finv_prefix.h[po + nn], S.max_nsupc[l]);
+        H->st.num_launches++;
+    }
+    void group_inverses(hipStream_t st, int l) { for (int gi : H->lvl_groups[l]) group_inverse(H, gi, st); }   // (has_groups) groups whose last member was factored at level l
+
+    // one timed, counted update launch; tmaps: the tiles read their records
+    void schur(hipStream_t st, bool big, int ntile, const int *nodes, const int *prefix, int nn, int id_base, const int4 *ulist, int prio = 0, const int *tmaps = nullptr,
+               int ksplit = 1, const int *xoff = nullptr, int xmax = 0)
+    {
+        if (H->profile && H->env.profile_dump) H->schur_rec.push_back({cur_level, cur_pass, big ? 1 : 0, ntile, S.max_nsupc[cur_level]});
+        if (H->profile) { if (H->ev_schur_big.size() <= H->ev_schur_used) H->ev_schur_big.resize(H->ev_schur_used + 1); H->ev_schur_big[H->ev_schur_used] = big ? 1 : 0; }
+        ev_begin(H, H->ev_schur, H->ev_schur_used, st);
+        schur_launch(H, st, big, nodes, prefix, nn, id_base, ntile, ulist, prio, tmaps, tmaps ? 2 : 0, ksplit, xoff, xmax);
+        ev_end(H, H->ev_schur, H->ev_schur_used, st);
+        H->st.num_launches++; H->st.schur_launches++; H->st.schur_tiles += ntile;
     }
     // parts p0 .. p1 of level l's tile lists (0 / 1: feed level-(l+1) panels, diagonal blocks first; 2: feed level-(l+2) panels;
     // 3: bulk) as ONE launch per tile-size group -- the parts are contiguous in the list
-    auto list_launch = [&](hipStream_t st, int l, int p0, int p1) {
+    void list_launch(hipStream_t st, int l, int p0, int p1, int pass)
+    {
+        cur_pass = pass;
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0;
         const int nbig = S.n_big[l];
         for (int g = 0; g < 2; ++g) {
             const int cnt = g == 0 ? nbig : nn - nbig;
             if (!cnt) continue;
             const int u0 = S.u_off[(2 * l + g) * 4 + p0], nu = S.u_off[(2 * l + g) * 4 + p1 + 1] - u0;
-            const int *tm = S.maps_state == 1 ? S.d_tmaps.p + S.m_off[2 * l + g] + (int64_t) (u0 - S.u_off[(2 * l + g) * 4]) * eng::schur_rec_ints(g == 0 ? 0 : 2, H->z) : nullptr;
+            const int *tm = S.maps_state == 1 ? S.d_tmaps.p + S.m_off[2 * l + g] + (int64_t) (u0 - S.u_off[(2 * l + g) * 4]) * tile_rec_ints(H, g == 0) : nullptr;
             // the diagonal-block tiles of the next level (part 0, on the panel stream) when they are few: split K over several workgroups per tile
             const int ks = (lookahead && p0 == 0 && p1 == 0 && g == 0 && nu <= 64 && !H->z && !H->env.schur_4waves) ? H->env.ksplit : 1;
             // a launch of the bulk alone: the XCDs' ranges of equal modelled cost (balance_bulk)
@@ -255,10 +272,12 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
             if (nu) schur(st, g == 0, nu, nullptr, nullptr, 0, 0, S.ulist.d + u0, (lookahead && p1 < 3) ? 1 : 0, tm, ks, bal ? S.x_off.d + 10 * (size_t) (2 * l + g) : nullptr,
                           bal ? S.x_off.h[10 * (size_t) (2 * l + g) + 9] : 0);
         }
-    };
+    }
     // deterministic mode: one supernode per launch over its full tile grid -- tiles of one k hit distinct destinations, the
     // summation order is fixed
-    auto grid_launch = [&](hipStream_t st, int l) {
+    void grid_launch(hipStream_t st, int l)
+    {
+        cur_pass = 3;
         const int n0 = S.lvl_off[l], nn = S.lvl_off[l + 1] - n0;
         const int *nodes = S.nodes.d + n0;
         const int nbig = S.n_big[l];
@@ -272,38 +291,56 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
                 if (c) schur(st, g == 0, c, gn, S.tile_prefix.d + so, cnt, S.tile_prefix.h[so + i], nullptr);
             }
         }
-    };
-    auto wait_on = [&](hipStream_t waiter, hipStream_t on) -> hipEvent_t {   // waiter continues after everything queued on `on`
-        hipEvent_t e = next_event(H);
-        hipEventRecord(e, on); hipStreamWaitEvent(waiter, e, 0);
-        return e;
-    };
+    }
+};
+
+// Serial program: everything in order on one stream.  The serial partition of the tiles (also the measurement harness of the Schur kernel): one launch
+// per level and tile-size group; only K-fused levels need their level-(l+1) urgent tiles launched apart, and the bulk is a launch of its own where its
+// XCD ranges are balanced (LevelSched::x_off)
+static int factor_serial(FactorRun &R)
+{
+    Handle *H = R.H;
+    LevelSched &S = R.S;
+    const hipStream_t s = R.s;
+    if (S.nlevels && R.tail_level(0)) R.deferred_inv(s, 0);
+    for (int l = 0; l < S.nlevels; ++l) {
+        R.cur_level = l;
+        if (H->opt.deterministic) R.grid_launch(s, l);
+        else {
+            const bool bal = !S.x_off.h.empty() && (S.x_off.h[10 * (size_t) (2 * l) + 9] > 0 || S.x_off.h[10 * (size_t) (2 * l + 1) + 9] > 0);
+            const bool fused = R.T.defer && S.lvl_defer[l];
+            if (fused) { R.list_launch(s, l, 0, 0, 0); R.list_launch(s, l, 1, 1, 1); }
+            const int p0 = fused ? 2 : 0;      // the parts still to launch: p0 .. 3
+            if (bal) { R.list_launch(s, l, p0, 2, 3); R.list_launch(s, l, 3, 3, 3); }
+            else R.list_launch(s, l, p0, 3, 3);
+        }
+        if (l + 1 < S.nlevels) {
+            R.panel_diag(l + 1); R.panel_solve(l + 1);
+            if (R.tail_level(l + 1)) R.deferred_inv(s, l + 1);
+            if (R.has_groups) R.group_inverses(s, l + 1);
+        }
+        if (R.rc_x) return R.rc_x;
+    }
+    return 0;
+}
+
+// Look-ahead program, four streams (forked from and joined into the main stream by run_factor_sched):
+//   s   (bulk)     : the bulk of Schur(l), level after level                                        -- never waits for a later panel
+//   us  (urgent 1) : U1(l) [tiles that feed level-(l+1) panels] minus its diagonal-block tiles, which run on ps in front of diag_lu(l+1)
+//   u2s (urgent 2) : U2(l) [tiles that feed level-(l+2) panels]
+//   ps  (panels)   : panel(l+1) = diag LU / inverses after U1's diagonal part, panel solves after all of U1(l)
+// panel(l+1) needs U1(l), U2(l-1) and the bulk of every level <= l-2: while the bulk of one level runs, the panels of the
+// next TWO levels and the urgent tiles between them are factored beside it.
+static int factor_lookahead(FactorRun &R)
+{
+    Handle *H = R.H;
+    LevelSched &S = R.S;
+    const hipStream_t s = R.s, ps = R.ps, us = R.us, u2s = R.u2s;
     hipEvent_t e_split_urgent = nullptr; // level l's panels were solved in two parts: the urgent part's event (the rest is queued on us)
     hipEvent_t e_u2_prev = nullptr;      // U2(l-1) done
     hipEvent_t e_bulk_prev = nullptr, e_bulk_prev2 = nullptr;   // bulk(l-1), bulk(l-2) done (stream order: and every earlier one)
-    if (S.nlevels) { panelA(0); panelB(0); if (!lookahead && tail_level(0)) deferred_inv(s, 0); }
     for (int l = 0; l < S.nlevels; ++l) {
-        cur_level = l;
-        const bool more = l + 1 < S.nlevels;
-        if (!lookahead) {
-            // serial partition (also the measurement harness of the Schur kernel, as in rounds 1-2): one launch per level and
-            // tile-size group; only K-fused levels need their level-(l+1) urgent tiles launched apart
-            if (H->opt.deterministic) { cur_pass = 3; grid_launch(s, l); }
-            // (the bulk as its own launch: its XCD ranges are balanced, LevelSched::x_off)
-            else {
-                const bool bal = !S.x_off.h.empty() && (S.x_off.h[10 * (size_t) (2 * l) + 9] > 0 || S.x_off.h[10 * (size_t) (2 * l + 1) + 9] > 0);
-                if (T.defer && S.lvl_defer[l]) { cur_pass = 0; list_launch(s, l, 0, 0); cur_pass = 1; list_launch(s, l, 1, 1); cur_pass = 3; if (bal) { list_launch(s, l, 2, 2); list_launch(s, l, 3, 3); } else list_launch(s, l, 2, 3); }
-                else if (bal) { cur_pass = 3; list_launch(s, l, 0, 2); list_launch(s, l, 3, 3); }
-                else { cur_pass = 3; list_launch(s, l, 0, 3); }
-            }
-            if (more) {
-                panelA(l + 1); panelB(l + 1);
-                if (tail_level(l + 1)) deferred_inv(s, l + 1);
-                if (!H->lvl_groups.empty() && &S == &H->sched[0]) for (int gi : H->lvl_groups[l + 1]) group_inverse(H, gi, s);
-            }
-            if (rc_x) return rc_x;
-            continue;
-        }
+        R.cur_level = l;
         if (e_split_urgent) {
             // level l was solved in two parts: its urgent strips on ps (event e_split_urgent), the others on us, queued there already.  The part-0 tiles
             // below follow the urgent strips in stream order; everything else needs both parts
@@ -318,43 +355,57 @@ static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
             hipEventRecord(e_p, ps);
             hipStreamWaitEvent(us, e_p, 0); hipStreamWaitEvent(u2s, e_p, 0); hipStreamWaitEvent(s, e_p, 0);
         }
-        if (tail_level(l)) deferred_inv(s, l);        // off the chain: the bulk stream waits for panel(l) anyway
-        if (!H->lvl_groups.empty() && &S == &H->sched[0] && !H->lvl_groups[l].empty()) {
+        if (R.tail_level(l)) R.deferred_inv(s, l);        // off the chain: the bulk stream waits for panel(l) anyway
+        if (R.has_groups && !H->lvl_groups[l].empty()) {
             // merged chain groups whose last member was factored at this level: their inverses on a stream of their own, after the members' panels and inverses
-            hipEvent_t e_g = next_event(H);
-            hipEventRecord(e_g, s); hipStreamWaitEvent(H->gstream, e_g, 0);
-            for (int gi : H->lvl_groups[l]) group_inverse(H, gi, H->gstream);
+            R.wait_on(H->gstream, s);
+            R.group_inverses(H->gstream, l);
         }
-        cur_pass = 0; list_launch(ps, l, 0, 0);   // on the panel stream itself: diag_lu(l+1) follows in stream order, no event hop
-        cur_pass = 1; list_launch(us, l, 1, 1);
+        R.list_launch(ps, l, 0, 0, 0);   // on the panel stream itself: diag_lu(l+1) follows in stream order, no event hop
+        R.list_launch(us, l, 1, 1, 1);
         hipEvent_t e_u1 = next_event(H); hipEventRecord(e_u1, us);
-        cur_pass = 2; list_launch(u2s, l, 2, 2);
+        R.list_launch(u2s, l, 2, 2, 2);
         hipEvent_t e_u2 = next_event(H); hipEventRecord(e_u2, u2s);
-        cur_pass = 3; list_launch(s, l, 3, 3);
+        R.list_launch(s, l, 3, 3, 3);
         hipEvent_t e_bulk = next_event(H); hipEventRecord(e_bulk, s);
-        if (more) {
+        if (l + 1 < S.nlevels) {
             if (e_u2_prev) hipStreamWaitEvent(ps, e_u2_prev, 0);
             if (e_bulk_prev2) hipStreamWaitEvent(ps, e_bulk_prev2, 0);
-            if (xy && e_bulk_prev) hipStreamWaitEvent(ps, e_bulk_prev, 0);   // XY layer: the received panels of level l-1 share the scratch copy (level parity) that panel(l+1)'s exchange fills
-            panelA(l + 1);
-            if (level_split(l + 1)) {
+            if (R.xy && e_bulk_prev) hipStreamWaitEvent(ps, e_bulk_prev, 0);   // XY layer: the received panels of level l-1 share the scratch copy (level parity) that panel(l+1)'s exchange fills
+            R.panel_diag(l + 1);
+            if (R.level_split(l + 1)) {
                 hipEvent_t e_pa = next_event(H); hipEventRecord(e_pa, ps);     // diagonal blocks (and inverses) of level l + 1 done
                 hipStreamWaitEvent(ps, e_u1, 0);
-                panelB_part(ps, l + 1, 0);                                     // urgent strips: what diag_lu(l + 2) waits for, through the part-0 tiles
+                R.panel_solve_part(ps, l + 1, 0);                              // urgent strips: what diag_lu(l + 2) waits for, through the part-0 tiles
                 e_split_urgent = next_event(H); hipEventRecord(e_split_urgent, ps);
                 hipStreamWaitEvent(us, e_pa, 0);                               // (after U1(l) in stream order; U2(l - 1) and the bulk of levels <= l - 2 through e_pa)
-                panelB_part(us, l + 1, 1);                                     // the other strips, beside diag_lu(l + 2)
+                R.panel_solve_part(us, l + 1, 1);                              // the other strips, beside diag_lu(l + 2)
             } else {
                 hipStreamWaitEvent(ps, e_u1, 0);
-                panelB(l + 1);
+                R.panel_solve(l + 1);
             }
         }
         e_u2_prev = e_u2; e_bulk_prev2 = e_bulk_prev; e_bulk_prev = e_bulk;
-        if (rc_x) return rc_x;
+        if (R.rc_x) return R.rc_x;
     }
-    if (lookahead && S.nlevels) { wait_on(s, ps); wait_on(s, us); wait_on(s, u2s); if (!H->lvl_groups.empty() && H->gstream) wait_on(s, H->gstream); }
+    return 0;
+}
+
+static int run_factor_sched(Handle *H, LevelSched &S, double thresh)
+{
+    FactorRun R(H, S, thresh);
+    ensure_tile_records(H, S);
+    R.reduction_offsets();
+    const bool side_streams = R.lookahead && S.nlevels;
+    if (side_streams) {    // the side streams must see everything queued so far on the main stream
+        hipEvent_t e = next_event(H);
+        hipEventRecord(e, R.s); hipStreamWaitEvent(R.ps, e, 0); hipStreamWaitEvent(R.us, e, 0); hipStreamWaitEvent(R.u2s, e, 0);
+    }
+    if (S.nlevels) { R.panel_diag(0); R.panel_solve(0); }
+    if (int rc = R.lookahead ? factor_lookahead(R) : factor_serial(R)) return rc;
+    if (side_streams) { R.wait_on(R.s, R.ps); R.wait_on(R.s, R.us); R.wait_on(R.s, R.u2s); if (!H->lvl_groups.empty() && H->gstream) R.wait_on(R.s, H->gstream); }
     HIPCHK(hipGetLastError());
-    return rc_x;
+    return R.rc_x;
 }
 
 static int ensure_xtmp(Handle *H, int64_t doubles) { return H->d_xtmp.reserve(doubles, H->device, "the exchange staging buffer"); }

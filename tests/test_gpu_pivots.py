@@ -54,7 +54,7 @@ def _diag(fs, pos):
 
 def _branches(c, pt, diag_tail=True):
     """the diagonal-LU kernel of every level from the plan's (supernodes, widest) columns.  A copy of the dispatch -- keep it in step with
-    eng::diag_lu / eng::zdiag_lu (sluamd_kernels.hip) and the big_regs flag of panelA (sluamd_factor.cpp) -- at the defaults: k_diag_lu2<1>
+    eng::diag_lu / eng::zdiag_lu (sluamd_kernels.hip) and the big_regs flag of FactorRun::panel_diag (sluamd_factor.cpp) -- at the defaults: k_diag_lu2<1>
     takes single-supernode levels among the last SLUAMD_DIAG_TAIL (64) levels, which every level of these cases is; kz_diag_lu_wave4 is off
     (SLUAMD_ZLU4_MAX_NODES); SLUAMD_DIAG_V1 is not set."""
     out = []
